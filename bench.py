@@ -58,6 +58,57 @@ def make_inputs(n_sym: int, T: int, seed: int, device):
     return {k: torch.from_numpy(v).to(device) for k, v in d.items()}
 
 
+DUMP_MAX_BYTES = 64_000_000
+DUMP_SEED = 0x5EED0003
+
+
+def _finite_split(a: np.ndarray):
+    """-> (a with every non-finite entry set to 0.0, float32 code of what stood there: 0 finite, 1 NULL (the library's null
+    marker, _lib.NULL_BITS), 2 any other NaN, 3 +inf, 4 -inf).  Every dumped file then holds finite numbers only."""
+    from polars_quant_amd._lib import NULL_BITS
+    code = np.select([a.view(np.uint64) == np.uint64(NULL_BITS), np.isnan(a), a == np.inf, a == -np.inf], [1, 2, 3, 4], 0)
+    return np.where(code == 0, a, 0.0), code.astype(np.float32)
+
+
+def dump_outputs(out_dir: Path, suite, summary, n_local: int, T: int) -> None:
+    """--dump-outputs: the step's outputs as a caller receives them, DIR/<name>.npy in float64 (int32 columns converted exactly).
+    A float64 column is written as two finite arrays: <name>.npy with its NULL / NaN / inf entries set to 0.0, and
+    <name>_nonfinite.npy (float32) saying which entries those were (_finite_split).  Every column is cut to the same fixed, seeded
+    sample of symbol rows (first and last symbol always included) so that the files stay under DUMP_MAX_BYTES; the [n, 8] backtest
+    summary is written for every symbol.  DIR/dump.json names the sampled rows."""
+    from polars_quant_amd._spec import PATTERN_NAMES, SPEC
+    cols = {}
+    for name, (_c, _p, outs, _f) in SPEC.items():
+        for (field, _dt), t in zip(outs, suite.out[name]):
+            cols[name if len(outs) == 1 else f"{name}_{field}"] = t
+    cols.update({nm: suite.pat[nm] for nm in PATTERN_NAMES})
+    cols.update(zip(("backtest_position", "backtest_cash", "backtest_equity"), suite.bt))
+    n_f64 = sum(t.dtype == torch.float64 for t in cols.values())
+    per_symbol = (len(cols) * 8 + n_f64 * 4) * T
+    fixed = summary.numel() * 12 + 256 * (len(cols) + n_f64 + 2)   # the summary and its codes, an .npy header (256 B at most) per file
+    k = min(n_local, (DUMP_MAX_BYTES - fixed) // per_symbol)
+    if k < min(n_local, 2):
+        raise SystemExit(f"bench.py --dump-outputs: one symbol's {len(cols)} columns of {T} days exceed {DUMP_MAX_BYTES} bytes")
+    if k == n_local:
+        rows = np.arange(n_local)
+    else:
+        pick = np.random.default_rng(DUMP_SEED).choice(n_local - 2, k - 2, replace=False) + 1
+        rows = np.sort(np.concatenate(([0, n_local - 1], pick)))
+    idx = torch.from_numpy(rows).to(summary.device)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    files = []
+    for name, t in list(cols.items()) + [("backtest_summary", summary)]:
+        a = (t if name == "backtest_summary" else t.index_select(0, idx)).cpu().numpy()
+        if a.dtype == np.float64:
+            a, code = _finite_split(a)
+            np.save(out_dir / f"{name}_nonfinite.npy", code)
+            files.append(f"{name}_nonfinite")
+        np.save(out_dir / f"{name}.npy", a.astype(np.float64))
+        files.append(name)
+    (out_dir / "dump.json").write_text(json.dumps({"symbols": n_local, "days": T, "seed": DUMP_SEED, "sampled_symbols": rows.tolist(),
+                                                   "files": sorted(files)}))
+
+
 def cpu_baseline(sample_syms: int, T: int):
     """the scalar C restatement, -O3 -march=native (built on this host), OpenMP over symbols on every core
     this process may use, on the bench's own data set (all 5000 symbols)."""
@@ -173,7 +224,11 @@ def visible_gpus():
     try:
         n = 0
         for node in sorted(nodes.iterdir()):
-            props = dict(l.split(None, 1) for l in (node / "properties").read_text().splitlines() if " " in l)
+            try:
+                text = (node / "properties").read_text()
+            except PermissionError:   # a host that gives this process some of its GPUs hides the others' nodes: not ours to use
+                continue
+            props = dict(l.split(None, 1) for l in text.splitlines() if " " in l)
             n += int(props.get("simd_count", "0")) > 0
     except Exception:  # noqa: BLE001
         return None
@@ -256,7 +311,13 @@ def main():
     ap.add_argument("--exact-layout", action="store_true", help="run on the caller's row pitch exactly (measures a slow layout as it is)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch / rendezvous / shard ranges only (gloo on the CPU, no GPU work): what `--gpus N` would run where")
+    ap.add_argument("--dump-outputs", metavar="DIR", type=Path, default=None,
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float64, finite: NULL / NaN / inf "
+                         "entries are 0.0 there and coded in DIR/<name>_nonfinite.npy; a seeded sample of symbol rows, 64 MB at most; "
+                         "rank 0's shard)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     default_scaling = args.scaling is None
     if default_scaling:
         args.scaling = "strong" if args.gpus > 1 else "weak"
@@ -413,12 +474,18 @@ def main():
             el = float(tmax.item())
         return el
 
+    last_slot = {}   # id(suite) -> the recording its latest replay ran: whose summary rows the last step wrote
+
     def time_steps(st, ohlcv, n_total, steps, warmup, timing=False, mode="overlapped"):
         if multi and len(getattr(st, "_summaries", [])) < 2:   # two recordings of the step, one per summary buffer
             st.record(ohlcv, summaries=[st.summary, torch.empty_like(st.summary)])
         two = len(st._summaries) == 2
-        # (run() without tensors: the inputs are resident -- where record() re-housed a slow-pitch column, resident means the suite's copy)
-        return time_loop(lambda slot: st.run(slot=slot if two else 0), st._summaries if two else [st.summary, st.summary], n_total,
+
+        def run_slot(slot):
+            last_slot[id(st)] = slot if two else 0
+            # (run() without tensors: the inputs are resident -- where record() re-housed a slow-pitch column, resident means the suite's copy)
+            st.run(slot=slot if two else 0)
+        return time_loop(run_slot, st._summaries if two else [st.summary, st.summary], n_total,
                          steps, warmup, mode, on_timed=(lambda: st.set_timing(True)) if timing else None)
 
     def backtest_only(ohlcv, n_local, n_total, steps, warmup, stride):
@@ -489,6 +556,8 @@ def main():
         mode = "serial" if exchange_modes["serial_ms_per_step"] <= exchange_modes["overlapped_ms_per_step"] else "overlapped"
         exchange_modes["chosen"] = mode
     elapsed = time_steps(suite, ohlcv, n_total, args.steps, args.warmup, timing=True, mode=mode)
+    if args.dump_outputs is not None and rank == 0:   # before anything else replays or closes the suite
+        dump_outputs(args.dump_outputs, suite, suite._summaries[last_slot[id(suite)]], n_local, T)
     gather_check = None
     if multi and comm is not None:   # cross-check, outside the timed region: the C-ABI gather against torch.distributed's
         ref = gather_summaries(suite.summary, n_total)
