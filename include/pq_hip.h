@@ -431,6 +431,34 @@ pq_status pq_factor_ic(pq_ctx *, const pq_batch *, const double *factor, const d
 /* rolling mean of ic over `window` rows (null unless all of them are non-null) and mean / sample std (IR) */
 pq_status pq_rolling_ic(pq_ctx *, const double *ic, int64_t len, int64_t window, double *rolling_ic, double *rolling_ir);
 
+/* ---- rank 3, continued: quantile sorts, long-short legs, turnover, coverage and IC statistics, Factor.quantile / portfolio_sorts /
+ * long_short / factor_mimicking_portfolio / turnover / coverage / ir / ic_win_rate (README.md:1479-1487, :1535-1545, :1589-1599;
+ * README-only, decision D-15 in DESIGN.md section 2).  factor / fwd_return: [n_series][stride], the cross-section as in D-12.  A
+ * symbol whose factor value occupies the tie run [a, b) of the day's ascending sort has m = a + b; labels are uint8 [n_series][stride]
+ * (the inputs' layout; NULL: not written): quantiles floor(m Q / 2n), long / short 1 (long) / 0 (short) / PQ_LABEL_MID, and
+ * PQ_LABEL_OUT outside the cross-section or on a day with n < Q (quantiles) / n < 2 (long / short).  Per group and day (dense
+ * [groups][len]): mean_return (sums over blocks of 256 symbols as in D-12; null where count is 0), count, turnover (new members / count;
+ * null on day 0 and where either day's count is 0); spread / ls_return [len] = top group - bottom group; summary [groups + 1]
+ * [PQ_GROUP_SUMMARY_COLS] = n_days, mean_return, std_return (ddof 1), sharpe (x sqrt(252)), mean_turnover over the non-null days, the
+ * last row for the spread.  n_series <= 100000; above 16384, n_series * len < 2^32.  Uses the context workspace (~10 bytes per cell, ~18
+ * above 16384 series). */
+#define PQ_LABEL_OUT 255
+#define PQ_LABEL_MID 254
+#define PQ_GROUP_SUMMARY_COLS 5
+/* n_quantiles in [2, 20]; mean_return / count / turnover: [n_quantiles][len]; summary: [n_quantiles + 1][5] */
+pq_status pq_factor_quantiles(pq_ctx *, const pq_batch *, const double *factor, const double *fwd_return, int32_t n_quantiles,
+                              uint8_t *labels, double *mean_return, int32_t *count, double *turnover, double *spread, double *summary);
+/* 0 < top_pct, 0 < bottom_pct, top_pct + bottom_pct <= 1; groups 0 = short, 1 = long: mean_return / count / turnover [2][len];
+ * ls_return [len] = long - short; summary [3][5] */
+pq_status pq_factor_long_short(pq_ctx *, const pq_batch *, const double *factor, const double *fwd_return, double top_pct,
+                               double bottom_pct, uint8_t *labels, double *mean_return, int32_t *count, double *turnover,
+                               double *ls_return, double *summary);
+/* coverage [len] = symbols with a non-null finite factor value / n_series */
+pq_status pq_factor_coverage(pq_ctx *, const pq_batch *, const double *factor, double *coverage);
+/* statistics of an IC series over its non-NaN days: out[5] = n_days, mean, std (ddof 1), ir = mean / std (not annualised),
+ * win_rate = #(ic > 0) / n_days; all but n_days null below 2 days, ir null where std is 0 */
+pq_status pq_ic_stats(pq_ctx *, const double *ic, int64_t len, double *out);
+
 /* ---- suites: record many calls, replay them as a few chip-filling grids ----
  * One indicator over N symbols is only N/64 wavefronts -- far too few for 256 CUs -- but a DataFrame query asks
  * for many indicators at once (df.with_columns([...]) in the reference; Polars then calls the plugin once per

@@ -435,6 +435,79 @@ def rolling_ic(ic, window: int):
     return ric, rir
 
 
+def _xsec_inputs(cols):
+    """factor (+ fwd_return) -> device tensors on one row pitch and the Batch that describes them"""
+    ts = [_to_device(c)[0] for c in cols]
+    if any(t.shape != ts[0].shape for t in ts):
+        raise ValueError("factor and fwd_return must have the same shape")
+    ts = _same_layout(ts)
+    return ts, _batch_of(ts[0])
+
+
+def _factor_groups(fn_name, factor, fwd_return, n_groups, scalars, labels):
+    (f, r), b = _xsec_inputs([factor, fwd_return])
+    dev = f.device
+    n, T = f.shape
+    out = {
+        "mean_return": torch.empty((n_groups, T), dtype=torch.float64, device=dev),
+        "count": torch.empty((n_groups, T), dtype=torch.int32, device=dev),
+        "turnover": torch.empty((n_groups, T), dtype=torch.float64, device=dev),
+        "spread": torch.empty(T, dtype=torch.float64, device=dev),
+        "summary": torch.empty((n_groups + 1, SUMMARY_COLS), dtype=torch.float64, device=dev),
+    }
+    lab = torch.empty((n, b.stride), dtype=torch.uint8, device=dev) if labels else None
+    vp = C.c_void_p
+    with torch.cuda.device(dev):
+        check(getattr(lib(), fn_name)(ctx(dev.index), C.byref(b), vp(f.data_ptr()) if n else None, vp(r.data_ptr()) if n else None,
+                                      *scalars, vp(lab.data_ptr()) if lab is not None and n else None,
+                                      *[vp(out[k].data_ptr()) for k in ("mean_return", "count", "turnover", "spread", "summary")]))
+    if lab is not None:
+        out["labels"] = lab[:, :T]
+    return out
+
+
+SUMMARY_COLS = 5  # PQ_GROUP_SUMMARY_COLS: n_days, mean_return, std_return, sharpe, mean_turnover
+LABEL_OUT, LABEL_MID = 255, 254  # PQ_LABEL_OUT (not in the day's cross-section), PQ_LABEL_MID (in neither leg)
+
+
+def factor_quantiles(factor, fwd_return, n_quantiles: int = 5, labels: bool = False):
+    """D-15: per-day quantile sort of the factor (bucket 0 = lowest values, ties share a bucket) -> dict of device tensors:
+    mean_return / count / turnover [Q, T], spread [T] (top - bottom bucket), summary [Q + 1, 5] (last row: the spread), and with
+    labels=True labels uint8 [N, T] (LABEL_OUT outside the day's cross-section)"""
+    return _factor_groups("pq_factor_quantiles", factor, fwd_return, int(n_quantiles), [C.c_int32(int(n_quantiles))], labels)
+
+
+def factor_long_short(factor, fwd_return, top_pct: float = 0.2, bottom_pct: float = 0.2, labels: bool = False):
+    """D-15: per-day long (top top_pct) and short (bottom bottom_pct) legs -> dict of device tensors: mean_return / count / turnover
+    [2, T] (row 0 = short, row 1 = long), ls_return [T] = long - short, summary [3, 5], and with labels=True labels uint8 [N, T]
+    (1 long, 0 short, LABEL_MID in neither leg, LABEL_OUT outside the day's cross-section)"""
+    out = _factor_groups("pq_factor_long_short", factor, fwd_return, 2, [C.c_double(float(top_pct)), C.c_double(float(bottom_pct))], labels)
+    out["ls_return"] = out.pop("spread")
+    return out
+
+
+def factor_coverage(factor):
+    """D-15: share of the symbols with a non-null finite factor value, per day -> device tensor [T]"""
+    (f,), b = _xsec_inputs([factor])
+    dev = f.device
+    n, T = f.shape
+    cov = torch.empty(T, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().pq_factor_coverage(ctx(dev.index), C.byref(b), C.c_void_p(f.data_ptr()) if n else None, C.c_void_p(cov.data_ptr())))
+    return cov
+
+
+def ic_stats(ic):
+    """D-15: statistics of an IC series over its non-null days -> device tensor [5]: n_days, mean, std, ir (mean / std), win_rate"""
+    t = _to_device(ic)[0].contiguous().reshape(-1)
+    dev = t.device
+    out = torch.empty(5, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().pq_ic_stats(ctx(dev.index), C.c_void_p(t.data_ptr()) if t.numel() else None, C.c_int64(t.numel()),
+                                C.c_void_p(out.data_ptr())))
+    return out
+
+
 def _signal_call(fn_name, cols, *scalars):
     ts = [_to_device(c)[0].contiguous() for c in cols]
     dev = ts[0].device

@@ -1,0 +1,522 @@
+// xsec/sorts.hip -- cross-sectional quantile sorts, long-short legs, turnover, coverage and IC statistics
+// (Factor.quantile / portfolio_sorts / long_short / factor_mimicking_portfolio / turnover / coverage / ir / ic_win_rate;
+// README.md:1479-1487, :1535-1545, :1589-1599; README-only => decision D-15).
+//
+// Columns are symbol-major [n_series][stride]; a day's cross-section is a strided column.
+//  1. prep:      a tiled transpose turns the factor column into day-major key rows (+inf where the (factor, return) pair is not in
+//                the cross-section) and counts each day's cross-section n.
+//  2. label:     up to XS_LDS_MAX symbols one workgroup per day sorts its key row in LDS (bitonic, keys only); wider cross-sections
+//                use rocPRIM's segmented radix sort (keys only) in global memory.  Each symbol then finds its tie run [a, b) by two
+//                binary searches of its own key in the sorted row -- m = a + b, so ties share a label and nothing depends on sort
+//                stability -- and writes one uint8 label per cell, day-major.
+//  3. transpose: labels day-major -> symbol-major, 64 x 64 byte tiles.
+//  4. aggregate: one thread per (day, block of 256 symbols), consecutive threads on consecutive days (coalesced); the per-group sums
+//                are D-12's order (ascending symbols inside a block, from 0.0), counts and "new member" counts are integers.  A per-day
+//                combine adds the block sums in ascending block order and writes mean / count / turnover / spread.
+//  5. summary:   one 64-lane workgroup per output row; chunks of the series are staged in LDS and summed by one lane in ascending day
+//                order (the stated sequential order), two-pass sample std.
+#include "../pq_dev.h"
+#include <rocprim/rocprim.hpp>
+
+namespace {
+
+constexpr int XS_BLOCK = 256;      // D-12 / D-15 summation block (symbols)
+constexpr int XS_LDS_MAX = 16384;  // widest cross-section sorted in LDS: 16 384 f64 keys = 128 KiB of the CU's 160 KiB
+constexpr int XS_CHUNK = 2048;     // days staged in LDS per step of the sequential summaries
+
+__device__ __forceinline__ double xs_inf() { return __longlong_as_double(0x7FF0000000000000LL); }
+__device__ __forceinline__ bool xs_valid(double v) { return !pq_isnull(v) && isfinite(v); }
+
+struct XsRule {
+    int32_t mode;    // 0: quantiles, 1: long / short
+    int32_t q;       // number of quantiles (mode 0)
+    int32_t min_n;   // a day with a smaller cross-section is labelled PQ_LABEL_OUT everywhere
+    double top, bottom;
+};
+
+// [n][stride] factor + return -> day-major [len][n] keys (the factor where the pair is valid, else +inf) and n per day
+__global__ __launch_bounds__(256) void xs_prep_kernel(const double *f, const double *r, Dims d, double *key, int32_t *n_valid) {
+    __shared__ double tile[32][33];
+    __shared__ int cnt[32];
+    const int64_t t0 = (int64_t)blockIdx.x * 32, s0 = (int64_t)blockIdx.y * 32;
+    const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5; // 32 x 8
+    if (threadIdx.x < 32) cnt[threadIdx.x] = 0;
+    for (int i = ly; i < 32; i += 8) { // rows = symbols, lanes along days (coalesced reads)
+        const int64_t s = s0 + i, t = t0 + lx;
+        double k = xs_inf();
+        if (s < d.n && t < d.len) {
+            const double a = f[s * d.stride + t], b = r[s * d.stride + t];
+            if (xs_valid(a) && xs_valid(b)) k = a;
+        }
+        tile[i][lx] = k;
+    }
+    __syncthreads();
+    for (int i = ly; i < 32; i += 8) { // rows = days, lanes along symbols (coalesced writes)
+        const int64_t t = t0 + i, s = s0 + lx;
+        const double k = tile[lx][i];
+        if (t < d.len && s < d.n) {
+            key[t * d.n + s] = k;
+            if (k != xs_inf()) atomicAdd(&cnt[i], 1);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 32 && t0 + threadIdx.x < d.len && cnt[threadIdx.x]) atomicAdd(&n_valid[t0 + threadIdx.x], cnt[threadIdx.x]);
+}
+
+// LDS rows carry one pad slot per 16 keys, so that the 16-key chunks of consecutive lanes start on different banks
+__device__ __forceinline__ int xs_phys(int i) { return i + (i >> 4); }
+
+// m = a + b for the tie run [a, b) of `key` in the ascending row S[0 .. nv) (key is one of its entries; PAD: S is an LDS row indexed
+// through xs_phys): binary searches only, so a discrete factor's runs of thousands of equal keys cost O(log nv) per symbol, not O(run)
+template <bool PAD>
+__device__ __forceinline__ int64_t xs_pos2(const double *S, int nv, double key) {
+    auto at = [&](int i) { return S[PAD ? xs_phys(i) : i]; };
+    int lo = 0, hi = nv;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (at(mid) < key) lo = mid + 1; else hi = mid; }
+    const int a = lo;
+    int b = a + 1;
+    if (b < nv && at(b) == key) {
+        lo = b + 1; hi = nv;
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (at(mid) <= key) lo = mid + 1; else hi = mid; }
+        b = lo;
+    }
+    return (int64_t)a + (int64_t)b;
+}
+
+__device__ __forceinline__ uint8_t xs_label(int64_t m, int64_t nv, const XsRule &rule) {
+    if (rule.mode == 0) return (uint8_t)((m * rule.q) / (2 * nv)); // floor(m Q / 2n) in integers: m < 2n => [0, Q)
+    const double p = (double)m / (double)(2 * nv);
+    if (p > 1.0 - rule.top) return 1;
+    if (p < rule.bottom) return 0;
+    return PQ_LABEL_MID;
+}
+
+// All-ascending bitonic network over S[0 .. P) (P = 2^p >= 16): the first stage of the merge of size k pairs i with its mirror
+// i ^ (k-1), the later stages are half-cleaners i, i + j.  S[n .. P) holds +inf and keeps it (the larger key always goes to the
+// larger index), so a pair or a 16-key chunk that only touches indices >= n changes nothing and is skipped.  Every stage whose pairs
+// lie inside one aligned 16-key chunk runs in registers -- merges of 2 .. 16 keys entirely, and the last four stages (j = 8 .. 1) of
+// every larger merge -- so a workgroup barrier is paid for each stage with j >= 16 and once per merge for the register pass: 65
+// barriers instead of 105 at P = 16 384.
+__device__ __forceinline__ void xs_cx(double &a, double &b) { // a <= b afterwards (keys are never NaN)
+    const bool sw = b < a;
+    const double lo = sw ? b : a, hi = sw ? a : b;
+    a = lo; b = hi;
+}
+template <bool FULL> __device__ __forceinline__ void xs_chunk(double *S, int c) {
+    double r[16];
+#pragma unroll
+    for (int m = 0; m < 16; m++) r[m] = S[xs_phys(c * 16 + m)];
+    if (FULL) {
+#pragma unroll
+        for (int k = 2; k <= 16; k <<= 1) {
+#pragma unroll
+            for (int m = 0; m < 16; m++)
+                if (!(m & (k >> 1))) xs_cx(r[m], r[m ^ (k - 1)]);
+#pragma unroll
+            for (int j = k >> 2; j > 0; j >>= 1)
+#pragma unroll
+                for (int m = 0; m < 16; m++)
+                    if (!(m & j)) xs_cx(r[m], r[m | j]);
+        }
+    } else {
+#pragma unroll
+        for (int j = 8; j > 0; j >>= 1)
+#pragma unroll
+            for (int m = 0; m < 16; m++)
+                if (!(m & j)) xs_cx(r[m], r[m | j]);
+    }
+#pragma unroll
+    for (int m = 0; m < 16; m++) S[xs_phys(c * 16 + m)] = r[m];
+}
+__device__ __forceinline__ void xs_sort_lds(double *S, int P, int n, int tid, int nthr) {
+    const int nchunk = P >> 4;
+    for (int c = tid; c < nchunk && c * 16 < n; c += nthr) xs_chunk<true>(S, c);
+    __syncthreads();
+    for (int k = 32; k <= P; k <<= 1) {
+        for (int j = k >> 1; j >= 16; j >>= 1) {
+            const bool mirror = j == (k >> 1);
+            for (int q = tid; q < (P >> 1); q += nthr) {
+                const int i = ((q & ~(j - 1)) << 1) | (q & (j - 1)); // grows with q
+                if (i >= n) break;
+                const int p = mirror ? (i ^ (k - 1)) : (i + j);
+                if (p < n) {
+                    const int pi = xs_phys(i), pp = xs_phys(p);
+                    const double a = S[pi], b = S[pp];
+                    if (b < a) { S[pi] = b; S[pp] = a; }
+                }
+            }
+            __syncthreads();
+        }
+        for (int c = tid; c < nchunk && c * 16 < n; c += nthr) xs_chunk<false>(S, c);
+        __syncthreads();
+    }
+}
+
+// one workgroup per day, n <= XS_LDS_MAX: sort the day's keys in LDS, label every symbol (day-major)
+__global__ __launch_bounds__(1024) void xs_label_lds_kernel(const double *key, const int32_t *n_valid, int64_t n, int P, XsRule rule,
+                                                            uint8_t *lab) {
+    extern __shared__ __align__(16) unsigned char xs_lds[];
+    double *S = (double *)xs_lds;
+    const int64_t t = blockIdx.x;
+    const double *row = key + t * n;
+    uint8_t *out = lab + t * n;
+    const int tid = threadIdx.x, nthr = blockDim.x, nv = n_valid[t];
+    if (nv < rule.min_n) { // uniform across the workgroup
+        for (int s = tid; s < n; s += nthr) out[s] = PQ_LABEL_OUT;
+        return;
+    }
+    for (int i = tid; i < P; i += nthr) S[xs_phys(i)] = i < n ? row[i] : xs_inf();
+    __syncthreads();
+    xs_sort_lds(S, P, (int)n, tid, nthr);
+    for (int s = tid; s < n; s += nthr) {
+        const double k = row[s];
+        out[s] = k == xs_inf() ? (uint8_t)PQ_LABEL_OUT : xs_label(xs_pos2<true>(S, nv, k), nv, rule);
+    }
+}
+
+// n > XS_LDS_MAX: the day's row was sorted by rocPRIM (sorted); label from the original row
+__global__ __launch_bounds__(256) void xs_label_sorted_kernel(const double *key, const double *sorted, const int32_t *n_valid, int64_t n,
+                                                              XsRule rule, uint8_t *lab) {
+    const int64_t t = blockIdx.x;
+    const double *row = key + t * n, *S = sorted + t * n;
+    uint8_t *out = lab + t * n;
+    const int nv = n_valid[t];
+    for (int64_t s = threadIdx.x; s < n; s += 256) {
+        const double k = row[s];
+        out[s] = (nv < rule.min_n || k == xs_inf()) ? (uint8_t)PQ_LABEL_OUT : xs_label(xs_pos2<false>(S, nv, k), nv, rule);
+    }
+}
+
+__global__ __launch_bounds__(256) void xs_offsets_kernel(unsigned *off, int64_t segs, int64_t n) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i <= segs) off[i] = (unsigned)(i * n);
+}
+
+// day-major [len][n] labels -> symbol-major [n][ostride]
+__global__ __launch_bounds__(256) void xs_label_transpose_kernel(const uint8_t *dm, int64_t n, int64_t len, uint8_t *sm, int64_t ostride) {
+    __shared__ uint8_t tile[64][65];
+    const int64_t t0 = (int64_t)blockIdx.x * 64, s0 = (int64_t)blockIdx.y * 64;
+    const int lx = threadIdx.x & 63, ly = threadIdx.x >> 6; // 64 x 4
+    for (int i = ly; i < 64; i += 4) {
+        const int64_t t = t0 + i, s = s0 + lx;
+        tile[i][lx] = (t < len && s < n) ? dm[t * n + s] : (uint8_t)PQ_LABEL_OUT;
+    }
+    __syncthreads();
+    for (int i = ly; i < 64; i += 4) {
+        const int64_t s = s0 + i, t = t0 + lx;
+        if (s < n && t < len) sm[s * ostride + t] = tile[lx][i];
+    }
+}
+
+// one thread per (day, block of 256 symbols): per group the sum of the members' returns (ascending symbols, from 0.0), the member count
+// and the count of members that were not in the group the day before.  G >= ng groups live in registers (static indices).
+template <int G>
+__global__ __launch_bounds__(64) void xs_group_partial_kernel(const uint8_t *lab, int64_t lstride, const double *ret, Dims d, int ng,
+                                                              double *psum, int32_t *pcnt, int32_t *pnew) {
+    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (t >= d.len) return;
+    const int64_t s_lo = (int64_t)blockIdx.y * XS_BLOCK, s_hi = s_lo + XS_BLOCK < d.n ? s_lo + XS_BLOCK : d.n;
+    double sum[G];
+    int cnt[G], nw[G];
+#pragma unroll
+    for (int g = 0; g < G; g++) { sum[g] = 0.0; cnt[g] = 0; nw[g] = 0; }
+    constexpr int B = 8;
+    for (int64_t s0 = s_lo; s0 < s_hi; s0 += B) {
+        int l[B], lp[B];
+        double v[B];
+#pragma unroll
+        for (int k = 0; k < B; k++) {
+            const int64_t s = s0 + k < s_hi ? s0 + k : s_hi - 1;
+            l[k] = lab[s * lstride + t];
+            lp[k] = t > 0 ? lab[s * lstride + t - 1] : PQ_LABEL_OUT;
+            v[k] = ret[s * d.stride + t];
+        }
+#pragma unroll
+        for (int k = 0; k < B; k++) {
+            if (s0 + k >= s_hi) break;
+#pragma unroll
+            for (int g = 0; g < G; g++)
+                if (l[k] == g) { sum[g] += v[k]; cnt[g] += 1; nw[g] += lp[k] != g; }
+        }
+    }
+#pragma unroll
+    for (int g = 0; g < G; g++)
+        if (g < ng) {
+            const int64_t o = ((int64_t)blockIdx.y * ng + g) * d.len + t;
+            psum[o] = sum[g]; pcnt[o] = cnt[g]; pnew[o] = nw[g];
+        }
+}
+
+// one thread per day: block sums in ascending block order (from 0.0); mean, count, turnover per group; top - bottom spread
+__global__ __launch_bounds__(64) void xs_group_combine_kernel(const double *psum, const int32_t *pcnt, const int32_t *pnew, int64_t nblk,
+                                                              int64_t len, int ng, double *mean, int32_t *count, double *tov,
+                                                              double *spread) {
+    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (t >= len) return;
+    double lo = pq_null(), hi = pq_null();
+    for (int g = 0; g < ng; g++) {
+        double s = 0.0;
+        int64_t c = 0, nw = 0, cp = 0;
+        for (int64_t k = 0; k < nblk; k++) {
+            const int64_t o = (k * ng + g) * len + t;
+            s += psum[o]; c += pcnt[o]; nw += pnew[o];
+            if (t > 0) cp += pcnt[o - 1];
+        }
+        const double m = c > 0 ? s / (double)c : pq_null();
+        mean[g * len + t] = m;
+        count[g * len + t] = (int32_t)c;
+        tov[g * len + t] = (t > 0 && c > 0 && cp > 0) ? (double)nw / (double)c : pq_null();
+        if (g == 0) lo = m;
+        if (g == ng - 1) hi = m;
+    }
+    spread[t] = (pq_isnull(lo) || pq_isnull(hi)) ? pq_null() : hi - lo;
+}
+
+// Sequential statistics of a series x[0 .. len) over its non-NaN entries, in ascending order from 0.0.  SQ = false: count, sum and
+// count of entries > 0; SQ = true: sum of (x - center)^2.  The 64 lanes stage XS_CHUNK terms at a time in LDS -- the entry (or its
+// square deviation), +0.0 for a NaN entry -- and count in parallel (integers: any order); lane 0 adds the staged terms in order.
+// A +0.0 term leaves the sum unchanged: it starts at +0.0, and a round-to-nearest sum that starts there is never -0.0.  Sum and
+// counts are returned in every lane.
+template <bool SQ>
+__device__ void xs_seq(const double *x, int64_t len, double center, double *buf, double &acc, int64_t &n, int64_t &pos) {
+    acc = 0.0;
+    long long cn = 0, cp = 0;
+    for (int64_t c0 = 0; c0 < len; c0 += XS_CHUNK) {
+        const int64_t m = len - c0 < XS_CHUNK ? len - c0 : XS_CHUNK, m8 = (m + 7) & ~7LL;
+        for (int64_t i0 = threadIdx.x; i0 < m8; i0 += 64 * 8) { // eight global loads in flight per lane
+            double v[8];
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                const int64_t i = i0 + k * 64;
+                v[k] = i < m ? x[c0 + i] : __longlong_as_double(0x7FF8000000000000LL);
+            }
+#pragma unroll
+            for (int k = 0; k < 8; k++) {
+                const bool ok = v[k] == v[k];
+                cn += ok;
+                if (!SQ) cp += v[k] > 0.0;
+                const double dv = v[k] - center;
+                if (i0 + k * 64 < m8) buf[i0 + k * 64] = ok ? (SQ ? dv * dv : v[k]) : 0.0;
+            }
+        }
+        __syncthreads();
+        if (threadIdx.x == 0)
+            for (int64_t i = 0; i < m8; i += 8) {
+                double v[8];
+#pragma unroll
+                for (int k = 0; k < 8; k++) v[k] = buf[i + k];
+#pragma unroll
+                for (int k = 0; k < 8; k++) acc += v[k];
+            }
+        __syncthreads();
+    }
+    for (int o = 32; o > 0; o >>= 1) { cn += __shfl_xor(cn, o, 64); cp += __shfl_xor(cp, o, 64); }
+    n = cn; pos = cp;
+    acc = __shfl(acc, 0, 64); // the next pass centres on the mean in every lane
+}
+
+// one 64-lane workgroup per row: rows 0 .. ng-1 = the groups (mean_return[g], turnover[g]), row ng = the spread / long-short series
+__global__ __launch_bounds__(64) void xs_summary_kernel(const double *mean, const double *tov, const double *spread, int64_t len, int ng,
+                                                        double *summary) {
+    __shared__ double buf[XS_CHUNK];
+    const int g = blockIdx.x;
+    const double *x = g < ng ? mean + g * len : spread;
+    double s, ss, ts;
+    int64_t n, nt, pos;
+    xs_seq<false>(x, len, 0.0, buf, s, n, pos);
+    const double m = n > 0 ? s / (double)n : pq_null();
+    xs_seq<true>(x, len, n > 0 ? m : 0.0, buf, ss, n, pos);
+    if (g < ng) xs_seq<false>(tov + g * len, len, 0.0, buf, ts, nt, pos);
+    if (threadIdx.x == 0) {
+        const double sd = n >= 2 ? sqrt(ss / (double)(n - 1)) : pq_null();
+        double *o = summary + (int64_t)g * PQ_GROUP_SUMMARY_COLS;
+        o[0] = (double)n;
+        o[1] = m;
+        o[2] = sd;
+        o[3] = (n >= 2 && sd > 0.0) ? m / sd * sqrt(252.0) : pq_null();
+        o[4] = (g < ng && nt > 0) ? ts / (double)nt : pq_null();
+    }
+}
+
+// n_days, mean, std, ir = mean / std (not annualised), win_rate = #(ic > 0) / n_days
+__global__ __launch_bounds__(64) void xs_ic_stats_kernel(const double *ic, int64_t len, double *out) {
+    __shared__ double buf[XS_CHUNK];
+    double s, ss;
+    int64_t n, pos, pos2;
+    xs_seq<false>(ic, len, 0.0, buf, s, n, pos);
+    const double m = n > 0 ? s / (double)n : 0.0;
+    xs_seq<true>(ic, len, m, buf, ss, n, pos2);
+    if (threadIdx.x == 0) {
+        const bool ok = n >= 2;
+        const double sd = ok ? sqrt(ss / (double)(n - 1)) : pq_null();
+        out[0] = (double)n;
+        out[1] = ok ? m : pq_null();
+        out[2] = sd;
+        out[3] = (ok && sd > 0.0) ? m / sd : pq_null();
+        out[4] = ok ? (double)pos / (double)n : pq_null();
+    }
+}
+
+// coverage: one thread per (day, block of 256 symbols) counts the valid factor values (integers: any order is exact)
+__global__ __launch_bounds__(64) void xs_coverage_partial_kernel(const double *f, Dims d, int32_t *cnt) {
+    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (t >= d.len) return;
+    const int64_t s_lo = (int64_t)blockIdx.y * XS_BLOCK, s_hi = s_lo + XS_BLOCK < d.n ? s_lo + XS_BLOCK : d.n;
+    int c = 0;
+    constexpr int B = 16;
+    for (int64_t s0 = s_lo; s0 < s_hi; s0 += B) {
+        double v[B];
+#pragma unroll
+        for (int k = 0; k < B; k++) {
+            const int64_t s = s0 + k < s_hi ? s0 + k : s_hi - 1;
+            v[k] = f[s * d.stride + t];
+        }
+#pragma unroll
+        for (int k = 0; k < B; k++) c += (s0 + k < s_hi && xs_valid(v[k])) ? 1 : 0;
+    }
+    if (c) atomicAdd(&cnt[t], c);
+}
+__global__ __launch_bounds__(256) void xs_coverage_final_kernel(const int32_t *cnt, int64_t len, int64_t n, double *coverage) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (t < len) coverage[t] = n > 0 ? (double)cnt[t] / (double)n : pq_null();
+}
+
+inline size_t xs_al(size_t x) { return (x + 255) / 256 * 256; }
+
+// labels -> group statistics -> summary: the body shared by pq_factor_quantiles (ng = Q) and pq_factor_long_short (ng = 2)
+pq_status xs_groups(pq_ctx *ctx, const pq_batch *b, const double *factor, const double *fwd_return, const XsRule &rule, int ng,
+                    uint8_t *labels, double *mean, int32_t *count, double *tov, double *spread, double *summary) {
+    if (b->len == 0) return PQ_OK;
+    const Dims d = dims_of(b);
+    const size_t cells = (size_t)d.len * (size_t)d.n, len = (size_t)d.len;
+    const int64_t nblk = (d.n + XS_BLOCK - 1) / XS_BLOCK > 0 ? (d.n + XS_BLOCK - 1) / XS_BLOCK : 1;
+    const bool wide = d.n > XS_LDS_MAX;
+    if (wide) {
+        PQ_REQUIRE(d.n <= 100000, "factor sorts support at most 100000 series");
+        PQ_REQUIRE(cells < (1ull << 32), "factor sorts need n_series * len < 2^32 above 16384 series");
+    }
+    size_t tmp_bytes = 0;
+    if (wide)
+        PQ_HIP_TRY(rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes, (double *)nullptr, (double *)nullptr, (unsigned)cells,
+                                                      (unsigned)d.len, (unsigned *)nullptr, (unsigned *)nullptr, 0, 64, ctx->stream));
+    // workspace: keys (f64, day-major) | n per day (i32) | labels day-major (u8) | labels symbol-major (u8, when the caller passes
+    // none) | block partials: sums (f64), counts, new members (i32) | wide: sorted keys (f64), offsets (u32), rocPRIM temp
+    const size_t part = (size_t)nblk * (size_t)ng * len;
+    const size_t o_cnt = xs_al(cells * 8), o_ldm = o_cnt + xs_al(len * 4), o_lsm = o_ldm + xs_al(cells),
+                 o_ps = o_lsm + (labels ? 0 : xs_al(cells)), o_pc = o_ps + xs_al(part * 8), o_pn = o_pc + xs_al(part * 4),
+                 o_srt = o_pn + xs_al(part * 4), o_off = o_srt + (wide ? xs_al(cells * 8) : 0),
+                 o_tmp = o_off + (wide ? xs_al((len + 1) * 4) : 0), total = o_tmp + (wide ? xs_al(tmp_bytes) : 0);
+    PQ_TRY(pq_ws_reserve(ctx, total));
+    unsigned char *w = (unsigned char *)ctx->ws;
+    double *key = (double *)w;
+    int32_t *nv = (int32_t *)(w + o_cnt);
+    uint8_t *ldm = w + o_ldm;
+    uint8_t *lsm = labels ? labels : w + o_lsm;
+    const int64_t lstride = labels ? d.stride : d.len;
+    double *psum = (double *)(w + o_ps);
+    int32_t *pcnt = (int32_t *)(w + o_pc), *pnew = (int32_t *)(w + o_pn);
+    if (d.n > 0) {
+        PQ_HIP_TRY(hipMemsetAsync(nv, 0, len * 4, ctx->stream));
+        hipLaunchKernelGGL(xs_prep_kernel, dim3((unsigned)((d.len + 31) / 32), (unsigned)((d.n + 31) / 32)), dim3(256), 0, ctx->stream,
+                           factor, fwd_return, d, key, nv);
+        if (!wide) {
+            int P = 16;
+            while (P < d.n) P <<= 1;
+            const int nthr = P / 16 < 64 ? 64 : (P / 16 > 1024 ? 1024 : P / 16);
+            const size_t lds = (size_t)(P + P / 16) * 8;
+            PQ_HIP_TRY(hipFuncSetAttribute((const void *)xs_label_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+            hipLaunchKernelGGL(xs_label_lds_kernel, dim3((unsigned)d.len), dim3(nthr), lds, ctx->stream, (const double *)key,
+                               (const int32_t *)nv, d.n, P, rule, ldm);
+        } else {
+            double *srt = (double *)(w + o_srt);
+            unsigned *off = (unsigned *)(w + o_off);
+            hipLaunchKernelGGL(xs_offsets_kernel, dim3((unsigned)((d.len + 256) / 256)), dim3(256), 0, ctx->stream, off, d.len, d.n);
+            PQ_HIP_TRY(rocprim::segmented_radix_sort_keys(w + o_tmp, tmp_bytes, key, srt, (unsigned)cells, (unsigned)d.len, off, off + 1, 0,
+                                                          64, ctx->stream));
+            hipLaunchKernelGGL(xs_label_sorted_kernel, dim3((unsigned)d.len), dim3(256), 0, ctx->stream, (const double *)key,
+                               (const double *)srt, (const int32_t *)nv, d.n, rule, ldm);
+        }
+        hipLaunchKernelGGL(xs_label_transpose_kernel, dim3((unsigned)((d.len + 63) / 64), (unsigned)((d.n + 63) / 64)), dim3(256), 0,
+                           ctx->stream, (const uint8_t *)ldm, d.n, d.len, lsm, lstride);
+    }
+    const dim3 gp((unsigned)((d.len + 63) / 64), (unsigned)nblk), gc((unsigned)((d.len + 63) / 64));
+    if (ng <= 2)
+        hipLaunchKernelGGL(xs_group_partial_kernel<2>, gp, dim3(64), 0, ctx->stream, (const uint8_t *)lsm, lstride, fwd_return, d, ng, psum,
+                           pcnt, pnew);
+    else if (ng <= 5)
+        hipLaunchKernelGGL(xs_group_partial_kernel<5>, gp, dim3(64), 0, ctx->stream, (const uint8_t *)lsm, lstride, fwd_return, d, ng, psum,
+                           pcnt, pnew);
+    else if (ng <= 10)
+        hipLaunchKernelGGL(xs_group_partial_kernel<10>, gp, dim3(64), 0, ctx->stream, (const uint8_t *)lsm, lstride, fwd_return, d, ng,
+                           psum, pcnt, pnew);
+    else
+        hipLaunchKernelGGL(xs_group_partial_kernel<20>, gp, dim3(64), 0, ctx->stream, (const uint8_t *)lsm, lstride, fwd_return, d, ng,
+                           psum, pcnt, pnew);
+    hipLaunchKernelGGL(xs_group_combine_kernel, gc, dim3(64), 0, ctx->stream, (const double *)psum, (const int32_t *)pcnt,
+                       (const int32_t *)pnew, nblk, d.len, ng, mean, count, tov, spread);
+    hipLaunchKernelGGL(xs_summary_kernel, dim3((unsigned)(ng + 1)), dim3(64), 0, ctx->stream, (const double *)mean, (const double *)tov,
+                       (const double *)spread, d.len, ng, summary);
+    PQ_HIP_TRY(hipGetLastError());
+    return PQ_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+pq_status pq_factor_quantiles(pq_ctx *ctx, const pq_batch *b, const double *factor, const double *fwd_return, int32_t n_quantiles,
+                              uint8_t *labels, double *mean_return, int32_t *count, double *turnover, double *spread, double *summary) {
+    PQ_TRY(pq_check(ctx, b));
+    PQ_REQUIRE(n_quantiles >= 2 && n_quantiles <= 20, "pq_factor_quantiles: n_quantiles must be in [2, 20]");
+    PQ_REQUIRE((b->n_series == 0 || (factor && fwd_return)) && mean_return && count && turnover && spread && summary,
+               "pq_factor_quantiles: null pointer");
+    if (ctx->rec) { pq_set_error("pq_factor_quantiles cannot be recorded into a suite"); return PQ_ERR_UNSUPPORTED; }
+    PQ_NO_RAGGED(b, "pq_factor_quantiles (a cross-section needs every symbol on every day)");
+    const XsRule rule{0, n_quantiles, n_quantiles, 0.0, 0.0};
+    return xs_groups(ctx, b, factor, fwd_return, rule, n_quantiles, labels, mean_return, count, turnover, spread, summary);
+}
+
+pq_status pq_factor_long_short(pq_ctx *ctx, const pq_batch *b, const double *factor, const double *fwd_return, double top_pct,
+                               double bottom_pct, uint8_t *labels, double *mean_return, int32_t *count, double *turnover, double *ls_return,
+                               double *summary) {
+    PQ_TRY(pq_check(ctx, b));
+    PQ_REQUIRE(top_pct > 0.0 && bottom_pct > 0.0 && top_pct + bottom_pct <= 1.0,
+               "pq_factor_long_short: need 0 < top_pct, 0 < bottom_pct and top_pct + bottom_pct <= 1");
+    PQ_REQUIRE((b->n_series == 0 || (factor && fwd_return)) && mean_return && count && turnover && ls_return && summary,
+               "pq_factor_long_short: null pointer");
+    if (ctx->rec) { pq_set_error("pq_factor_long_short cannot be recorded into a suite"); return PQ_ERR_UNSUPPORTED; }
+    PQ_NO_RAGGED(b, "pq_factor_long_short (a cross-section needs every symbol on every day)");
+    const XsRule rule{1, 0, 2, top_pct, bottom_pct};
+    return xs_groups(ctx, b, factor, fwd_return, rule, 2, labels, mean_return, count, turnover, ls_return, summary);
+}
+
+pq_status pq_factor_coverage(pq_ctx *ctx, const pq_batch *b, const double *factor, double *coverage) {
+    PQ_TRY(pq_check(ctx, b));
+    PQ_REQUIRE((b->n_series == 0 || factor) && coverage, "pq_factor_coverage: null pointer");
+    if (ctx->rec) { pq_set_error("pq_factor_coverage cannot be recorded into a suite"); return PQ_ERR_UNSUPPORTED; }
+    PQ_NO_RAGGED(b, "pq_factor_coverage (a cross-section needs every symbol on every day)");
+    if (b->len == 0) return PQ_OK;
+    const Dims d = dims_of(b);
+    PQ_TRY(pq_ws_reserve(ctx, (size_t)d.len * 4));
+    int32_t *cnt = (int32_t *)ctx->ws;
+    PQ_HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)d.len * 4, ctx->stream));
+    if (d.n > 0)
+        hipLaunchKernelGGL(xs_coverage_partial_kernel, dim3((unsigned)((d.len + 63) / 64), (unsigned)((d.n + XS_BLOCK - 1) / XS_BLOCK)),
+                           dim3(64), 0, ctx->stream, factor, d, cnt);
+    hipLaunchKernelGGL(xs_coverage_final_kernel, dim3((unsigned)((d.len + 255) / 256)), dim3(256), 0, ctx->stream, (const int32_t *)cnt,
+                       d.len, d.n, coverage);
+    PQ_HIP_TRY(hipGetLastError());
+    return PQ_OK;
+}
+
+pq_status pq_ic_stats(pq_ctx *ctx, const double *ic, int64_t len, double *out) {
+    PQ_REQUIRE(ctx && out && (len == 0 || ic), "pq_ic_stats: null pointer");
+    PQ_REQUIRE(len >= 0, "pq_ic_stats: negative length");
+    if (ctx->rec) { pq_set_error("pq_ic_stats cannot be recorded into a suite"); return PQ_ERR_UNSUPPORTED; }
+    PQ_HIP_TRY(hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(xs_ic_stats_kernel, dim3(1), dim3(64), 0, ctx->stream, ic, len, out);
+    PQ_HIP_TRY(hipGetLastError());
+    return PQ_OK;
+}
+
+} // extern "C"

@@ -1,9 +1,11 @@
 """Factor -- the evaluation half of the README's `Factor` class (README.md:1429-1430, :1480-1482, :1626-1634): per-day
-cross-sectional IC, Rank-IC and their rolling mean / information ratio.  README-only in the reference; semantics =
-decision D-12 (oracle/backtest.c).  Inputs are [N, T] arrays (symbol-major, like every other column of this package): the
-factor and the forward return of every symbol on every day.
+cross-sectional IC, Rank-IC and their rolling mean / information ratio (decision D-12, oracle/backtest.c), and quantile sorts,
+long-short legs, turnover, coverage and IC statistics (decision D-15).  README-only in the reference.  Inputs are [N, T] arrays (symbol-major, like every other column of this
+package): the factor and the forward return of every symbol on every day.
 """
 from __future__ import annotations
+
+import torch
 
 from . import api as _api
 
@@ -22,3 +24,42 @@ class Factor:
         ic, _ = _api.factor_ic(factor, next_return, 1 if rank else 0)
         m, ir = _api.rolling_ic(ic, window)
         return {"rolling_ic": m, "rolling_ir": ir}
+
+    # ---- D-15: quantile sorts, long-short legs, turnover, coverage and IC statistics (README.md:1479-1487, :1535-1545, :1589-1599)
+    def quantile(self, factor, next_return, n_quantiles=5):
+        """-> {"mean_return", "count", "turnover": [Q, T], "spread": [T], "summary": [Q + 1, 5]} (bucket 0 = lowest factor values)"""
+        return _api.factor_quantiles(factor, next_return, n_quantiles)
+
+    def portfolio_sorts(self, factor, next_return, n_quantiles=5):
+        """-> {"quantile", "mean_return", "std_return", "sharpe"}: one row per bucket plus a last row (quantile -1) for the
+        top-minus-bottom spread"""
+        s = _api.factor_quantiles(factor, next_return, n_quantiles)["summary"]
+        q = torch.tensor(list(range(int(n_quantiles))) + [-1], dtype=torch.int32, device=s.device)
+        return {"quantile": q, "mean_return": s[:, 1], "std_return": s[:, 2], "sharpe": s[:, 3]}
+
+    def long_short(self, factor, next_return, top_pct=0.2, bottom_pct=0.2):
+        """-> {"mean_return", "count", "turnover": [2, T] (short, long), "ls_return": [T], "summary": [3, 5]}"""
+        return _api.factor_long_short(factor, next_return, top_pct, bottom_pct)
+
+    def factor_mimicking_portfolio(self, factor, next_return, top_pct=0.3, bottom_pct=0.3):
+        """-> {"long_return", "short_return", "ls_return"}: [T] each"""
+        r = _api.factor_long_short(factor, next_return, top_pct, bottom_pct)
+        return {"long_return": r["mean_return"][1], "short_return": r["mean_return"][0], "ls_return": r["ls_return"]}
+
+    def turnover(self, factor, next_return, n_quantiles=5):
+        """-> [Q, T]: share of each bucket's members that were not in it the day before"""
+        return _api.factor_quantiles(factor, next_return, n_quantiles)["turnover"]
+
+    def coverage(self, factor):
+        """-> [T]: share of the symbols with a non-null finite factor value"""
+        return _api.factor_coverage(factor)
+
+    def ir(self, factor, next_return, rank=False):
+        """-> mean / sample std of the (rank) IC series over its non-null days (not annualised; nan below 2 days or at std 0)"""
+        ic, _ = _api.factor_ic(factor, next_return, 1 if rank else 0)
+        return float(_api.ic_stats(ic)[3])
+
+    def ic_win_rate(self, factor, next_return, rank=False):
+        """-> share of the non-null days with a positive (rank) IC (nan below 2 days)"""
+        ic, _ = _api.factor_ic(factor, next_return, 1 if rank else 0)
+        return float(_api.ic_stats(ic)[4])
