@@ -459,6 +459,21 @@ pq_status pq_factor_coverage(pq_ctx *, const pq_batch *, const double *factor, d
  * win_rate = #(ic > 0) / n_days; all but n_days null below 2 days, ir null where std is 0 */
 pq_status pq_ic_stats(pq_ctx *, const double *ic, int64_t len, double *out);
 
+/* ---- rank 3, continued: per-day factor cleaning, clean(...) (README.md:244-345; README-only, decision D-16 in DESIGN.md section 2).
+ * factor / cap_z: f64 [n_series][stride], industry: int32 [n_series][stride], all on the batch's row pitch.  Per day, the cross-section is
+ * every symbol with a non-null finite factor, a non-null finite cap_z (size neutralization on) and an industry code in [0, n_industries)
+ * (industry neutralization on).  In the README's order: winsorize (clip to bounds from the day's cross-section), the OLS residual on cap_z
+ * with an intercept, minus the mean of the symbol's industry, standardize (mean 0, sample std 1).  The log of the cap is the caller's:
+ * cap_z is regressed on as given.  NULL outside the cross-section, on days with fewer than 2 members, and (standardize) on days whose std
+ * is 0.  out may be factor itself (in place); cap_z and industry must not overlap out.  mad / percentile: n_series <= 100000, and above
+ * 16384, n_series * len < 2^32.  Uses the context workspace (~8 bytes per cell for mad / percentile, ~16 above 16384 series, plus
+ * ~10 * n_industries bytes per (day, block of 256 symbols)). */
+/* D-16. winsorize: 0 none, 1 mad (winsorize_n MADs x 1.4826), 2 sigma (winsorize_n stds), 3 percentile (winsorize_n %, 0 <= p < 50);
+ * cap_z / industry NULL = that neutralization off; industry codes outside [0, n_industries) are unclassified; n_industries in [1, 256];
+ * standardize 0 / 1; out [n_series][stride], NULL outside the cross-section */
+pq_status pq_factor_clean(pq_ctx *, const pq_batch *, const double *factor, int32_t winsorize, double winsorize_n,
+                          const double *cap_z, const int32_t *industry, int32_t n_industries, int32_t standardize, double *out);
+
 /* ---- suites: record many calls, replay them as a few chip-filling grids ----
  * One indicator over N symbols is only N/64 wavefronts -- far too few for 256 CUs -- but a DataFrame query asks
  * for many indicators at once (df.with_columns([...]) in the reference; Polars then calls the plugin once per

@@ -508,6 +508,75 @@ def ic_stats(ic):
     return out
 
 
+CLEAN_WINSORIZE = {None: 0, "mad": 1, "sigma": 2, "percentile": 3}     # pq_factor_clean's winsorize codes
+CLEAN_WINSORIZE_N = {"mad": 3.0, "sigma": 3.0, "percentile": 1.0}    # the README's defaults
+MAX_INDUSTRIES = 256
+
+
+def _clean_args(winsorize, winsorize_n, industry):
+    """argument checks of factor_clean that need no device: -> (mode, winsorize_n, industry as an integer tensor or None, n_industries)"""
+    if winsorize not in CLEAN_WINSORIZE:
+        raise ValueError(f"winsorize must be one of None, 'mad', 'sigma', 'percentile', not {winsorize!r}")
+    mode = CLEAN_WINSORIZE[winsorize]
+    wn = 0.0 if winsorize is None else float(CLEAN_WINSORIZE_N[winsorize] if winsorize_n is None else winsorize_n)
+    if winsorize in ("mad", "sigma") and not (0.0 <= wn < float("inf")):
+        raise ValueError(f"winsorize_n must be finite and >= 0 for {winsorize!r}, not {wn}")
+    if winsorize == "percentile" and not (0.0 <= wn / 100.0 < 0.5):
+        raise ValueError(f"percentile winsorize needs 0 <= winsorize_n < 50 (percent), not {wn}")
+    ind, G = None, 0
+    if industry is not None:
+        ind = industry if isinstance(industry, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(industry)))
+        if ind.dtype.is_floating_point or ind.dtype == torch.bool:
+            raise ValueError("industry must hold integer codes")
+        G = int(ind.max()) + 1 if ind.numel() else 1
+        if G > MAX_INDUSTRIES:
+            raise ValueError(f"industry codes must be < {MAX_INDUSTRIES} (negative = unclassified), got a code {G - 1}")
+        G = max(G, 1)
+    return mode, wn, ind, G
+
+
+def factor_clean(factor, winsorize=None, winsorize_n=None, cap=None, log_cap: bool = True, industry=None, standardize: bool = False):
+    """D-16: per-day cross-sectional cleaning of an [N, T] factor in the README's order -> device tensor [N, T] (f64, NULL outside the
+    day's cross-section and on days with fewer than 2 members).
+    winsorize: None, "mad" (clip to median +- winsorize_n * 1.4826 MAD, default 3), "sigma" (mean +- winsorize_n std, default 3) or
+    "percentile" (the winsorize_n % and (100 - winsorize_n) % quantiles, default 1); cap [N, T]: OLS residual on log(cap) (log_cap) or
+    on cap; industry int codes [N] or [N, T] (negative = unclassified, at most 256 industries): minus the day's industry mean;
+    standardize: (x - mean) / sample std (NULL on days whose std is 0)."""
+    mode, wn, ind, G = _clean_args(winsorize, winsorize_n, industry)
+    f = _to_device(factor)[0]
+    n, T = f.shape
+    ts = [f]
+    if cap is not None:
+        z = _to_device(cap)[0]
+        if z.shape != f.shape:
+            raise ValueError(f"cap must have the factor's shape {tuple(f.shape)}, not {tuple(z.shape)}")
+        if log_cap:      # into a column on the factor's row pitch, so that both keep it
+            zl = torch.empty_strided(f.shape, f.stride(), dtype=torch.float64, device=f.device)
+            torch.log(z, out=zl)
+            z = zl
+        ts.append(z)
+    ts = _same_layout(ts)
+    f, z = ts[0], ts[1] if cap is not None else None
+    b = _batch_of(f)
+    dev = f.device
+    ib = None
+    if ind is not None:
+        ind = ind.to(device=dev, dtype=torch.int32)
+        if ind.dim() == 1:
+            ind = ind[:, None]
+        if ind.dim() != 2 or ind.shape[0] != n or ind.shape[1] not in (1, T):
+            raise ValueError(f"industry must be [N] or [N, T] with N = {n}, T = {T}, not {tuple(ind.shape)}")
+        ib = torch.empty((n, b.stride), dtype=torch.int32, device=dev)     # on the factor's row pitch
+        ib[:, :T] = ind
+    out = torch.empty((n, b.stride), dtype=torch.float64, device=dev)
+    vp = C.c_void_p
+    with torch.cuda.device(dev):
+        check(lib().pq_factor_clean(ctx(dev.index), C.byref(b), vp(f.data_ptr()) if n else None, C.c_int32(mode), C.c_double(wn),
+                                    vp(z.data_ptr()) if z is not None and n else None, vp(ib.data_ptr()) if ib is not None and n else None,
+                                    C.c_int32(G), C.c_int32(1 if standardize else 0), vp(out.data_ptr()) if n else None))
+    return out[:, :T]
+
+
 def _signal_call(fn_name, cols, *scalars):
     ts = [_to_device(c)[0].contiguous() for c in cols]
     dev = ts[0].device

@@ -15,17 +15,12 @@
 //                combine adds the block sums in ascending block order and writes mean / count / turnover / spread.
 //  5. summary:   one 64-lane workgroup per output row; chunks of the series are staged in LDS and summed by one lane in ascending day
 //                order (the stated sequential order), two-pass sample std.
-#include "../pq_dev.h"
+#include "xsec_dev.h"
 #include <rocprim/rocprim.hpp>
 
 namespace {
 
-constexpr int XS_BLOCK = 256;      // D-12 / D-15 summation block (symbols)
-constexpr int XS_LDS_MAX = 16384;  // widest cross-section sorted in LDS: 16 384 f64 keys = 128 KiB of the CU's 160 KiB
 constexpr int XS_CHUNK = 2048;     // days staged in LDS per step of the sequential summaries
-
-__device__ __forceinline__ double xs_inf() { return __longlong_as_double(0x7FF0000000000000LL); }
-__device__ __forceinline__ bool xs_valid(double v) { return !pq_isnull(v) && isfinite(v); }
 
 struct XsRule {
     int32_t mode;    // 0: quantiles, 1: long / short
@@ -63,9 +58,6 @@ __global__ __launch_bounds__(256) void xs_prep_kernel(const double *f, const dou
     if (threadIdx.x < 32 && t0 + threadIdx.x < d.len && cnt[threadIdx.x]) atomicAdd(&n_valid[t0 + threadIdx.x], cnt[threadIdx.x]);
 }
 
-// LDS rows carry one pad slot per 16 keys, so that the 16-key chunks of consecutive lanes start on different banks
-__device__ __forceinline__ int xs_phys(int i) { return i + (i >> 4); }
-
 // m = a + b for the tie run [a, b) of `key` in the ascending row S[0 .. nv) (key is one of its entries; PAD: S is an LDS row indexed
 // through xs_phys): binary searches only, so a discrete factor's runs of thousands of equal keys cost O(log nv) per symbol, not O(run)
 template <bool PAD>
@@ -89,67 +81,6 @@ __device__ __forceinline__ uint8_t xs_label(int64_t m, int64_t nv, const XsRule 
     if (p > 1.0 - rule.top) return 1;
     if (p < rule.bottom) return 0;
     return PQ_LABEL_MID;
-}
-
-// All-ascending bitonic network over S[0 .. P) (P = 2^p >= 16): the first stage of the merge of size k pairs i with its mirror
-// i ^ (k-1), the later stages are half-cleaners i, i + j.  S[n .. P) holds +inf and keeps it (the larger key always goes to the
-// larger index), so a pair or a 16-key chunk that only touches indices >= n changes nothing and is skipped.  Every stage whose pairs
-// lie inside one aligned 16-key chunk runs in registers -- merges of 2 .. 16 keys entirely, and the last four stages (j = 8 .. 1) of
-// every larger merge -- so a workgroup barrier is paid for each stage with j >= 16 and once per merge for the register pass: 65
-// barriers instead of 105 at P = 16 384.
-__device__ __forceinline__ void xs_cx(double &a, double &b) { // a <= b afterwards (keys are never NaN)
-    const bool sw = b < a;
-    const double lo = sw ? b : a, hi = sw ? a : b;
-    a = lo; b = hi;
-}
-template <bool FULL> __device__ __forceinline__ void xs_chunk(double *S, int c) {
-    double r[16];
-#pragma unroll
-    for (int m = 0; m < 16; m++) r[m] = S[xs_phys(c * 16 + m)];
-    if (FULL) {
-#pragma unroll
-        for (int k = 2; k <= 16; k <<= 1) {
-#pragma unroll
-            for (int m = 0; m < 16; m++)
-                if (!(m & (k >> 1))) xs_cx(r[m], r[m ^ (k - 1)]);
-#pragma unroll
-            for (int j = k >> 2; j > 0; j >>= 1)
-#pragma unroll
-                for (int m = 0; m < 16; m++)
-                    if (!(m & j)) xs_cx(r[m], r[m | j]);
-        }
-    } else {
-#pragma unroll
-        for (int j = 8; j > 0; j >>= 1)
-#pragma unroll
-            for (int m = 0; m < 16; m++)
-                if (!(m & j)) xs_cx(r[m], r[m | j]);
-    }
-#pragma unroll
-    for (int m = 0; m < 16; m++) S[xs_phys(c * 16 + m)] = r[m];
-}
-__device__ __forceinline__ void xs_sort_lds(double *S, int P, int n, int tid, int nthr) {
-    const int nchunk = P >> 4;
-    for (int c = tid; c < nchunk && c * 16 < n; c += nthr) xs_chunk<true>(S, c);
-    __syncthreads();
-    for (int k = 32; k <= P; k <<= 1) {
-        for (int j = k >> 1; j >= 16; j >>= 1) {
-            const bool mirror = j == (k >> 1);
-            for (int q = tid; q < (P >> 1); q += nthr) {
-                const int i = ((q & ~(j - 1)) << 1) | (q & (j - 1)); // grows with q
-                if (i >= n) break;
-                const int p = mirror ? (i ^ (k - 1)) : (i + j);
-                if (p < n) {
-                    const int pi = xs_phys(i), pp = xs_phys(p);
-                    const double a = S[pi], b = S[pp];
-                    if (b < a) { S[pi] = b; S[pp] = a; }
-                }
-            }
-            __syncthreads();
-        }
-        for (int c = tid; c < nchunk && c * 16 < n; c += nthr) xs_chunk<false>(S, c);
-        __syncthreads();
-    }
 }
 
 // one workgroup per day, n <= XS_LDS_MAX: sort the day's keys in LDS, label every symbol (day-major)
@@ -185,11 +116,6 @@ __global__ __launch_bounds__(256) void xs_label_sorted_kernel(const double *key,
         const double k = row[s];
         out[s] = (nv < rule.min_n || k == xs_inf()) ? (uint8_t)PQ_LABEL_OUT : xs_label(xs_pos2<false>(S, nv, k), nv, rule);
     }
-}
-
-__global__ __launch_bounds__(256) void xs_offsets_kernel(unsigned *off, int64_t segs, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i <= segs) off[i] = (unsigned)(i * n);
 }
 
 // day-major [len][n] labels -> symbol-major [n][ostride]
@@ -380,8 +306,6 @@ __global__ __launch_bounds__(256) void xs_coverage_final_kernel(const int32_t *c
     const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (t < len) coverage[t] = n > 0 ? (double)cnt[t] / (double)n : pq_null();
 }
-
-inline size_t xs_al(size_t x) { return (x + 255) / 256 * 256; }
 
 // labels -> group statistics -> summary: the body shared by pq_factor_quantiles (ng = Q) and pq_factor_long_short (ng = 2)
 pq_status xs_groups(pq_ctx *ctx, const pq_batch *b, const double *factor, const double *fwd_return, const XsRule &rule, int ng,

@@ -1,7 +1,8 @@
 """Factor -- the evaluation half of the README's `Factor` class (README.md:1429-1430, :1480-1482, :1626-1634): per-day
 cross-sectional IC, Rank-IC and their rolling mean / information ratio (decision D-12, oracle/backtest.c), and quantile sorts,
 long-short legs, turnover, coverage and IC statistics (decision D-15).  README-only in the reference.  Inputs are [N, T] arrays (symbol-major, like every other column of this
-package): the factor and the forward return of every symbol on every day.
+package): the factor and the forward return of every symbol on every day.  `clean` is the README's factor cleaning step that comes
+before the evaluation (decision D-16).
 """
 from __future__ import annotations
 
@@ -63,3 +64,18 @@ class Factor:
         """-> share of the non-null days with a positive (rank) IC (nan below 2 days)"""
         ic, _ = _api.factor_ic(factor, next_return, 1 if rank else 0)
         return float(_api.ic_stats(ic)[4])
+
+
+def clean(factor, winsorize=None, winsorize_n=None, neutralize_market_cap=False, cap=None, neutralize_industry=False, industry=None,
+          standardize=False, log_cap=True):
+    """README `clean(df, col, winsorize, winsorize_n, neutralize_market_cap, cap_col, neutralize_industry, industry_col, standardize)`
+    (README.md:244-345) on arrays instead of columns: factor and cap [N, T], industry integer codes [N] or [N, T] (negative =
+    unclassified).  Per day and in the README's order: winsorize ("mad" / "sigma" / "percentile"; winsorize_n=None picks 3.0 / 3.0 /
+    1.0), size neutralization (OLS residual on log(cap), or on cap with log_cap=False), industry neutralization (minus the industry mean,
+    after the size step), standardize.  -> device tensor [N, T]; NULL outside the day's cross-section.  Decision D-16, DESIGN.md section 2."""
+    if neutralize_market_cap and cap is None:
+        raise ValueError("neutralize_market_cap=True needs cap")
+    if neutralize_industry and industry is None:
+        raise ValueError("neutralize_industry=True needs industry")
+    return _api.factor_clean(factor, winsorize, winsorize_n, cap if neutralize_market_cap else None, log_cap,
+                             industry if neutralize_industry else None, standardize)
