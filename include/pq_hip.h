@@ -474,6 +474,26 @@ pq_status pq_ic_stats(pq_ctx *, const double *ic, int64_t len, double *out);
 pq_status pq_factor_clean(pq_ctx *, const pq_batch *, const double *factor, int32_t winsorize, double winsorize_n,
                           const double *cap_z, const int32_t *industry, int32_t n_industries, int32_t standardize, double *out);
 
+/* ---- rank 3, continued: OLS with t-tests, ic_test / factor_return / fama_macbeth / time_series_regression (README.md:1521-1600;
+ * README-only, decision D-17 in DESIGN.md section 2).  Model r = a + sum_j b_j f_j, 1 <= k <= PQ_REGRESS_MAX_K.  factors is a HOST array
+ * of k device pointers, each on the batch's row pitch ([n_series][stride]).  A sample is every index where the return and all k factors
+ * are non-null and finite; sums over blocks of 256 indices as in D-12, centred normal equations solved by C = L D L^T in D-17's order,
+ * so coef / t / R^2 / n are bit-exact; p-values (two-sided Student t) are accurate to ~1e-13 relative.  NULL (coef, t, p, R^2) where
+ * n < k + 2 or a pivot D_j <= 1e-12 C[j][j]; t and p NULL where se == 0; R^2 NULL where the centred sum of squares of r is 0.  Ragged
+ * batches and suite recording are refused.  Uses the context workspace (~8 (k + 1)(k + 2) / 2 bytes per (unit, block of 256)). */
+#define PQ_REGRESS_MAX_K 8
+#define PQ_REGRESS_SUMMARY_COLS 5 /* n_days, mean_coef, std_coef (ddof 1), t = mean / (std / sqrt(n_days)), p on n_days - 1 */
+/* per-day cross-sectional regression over the symbols.  coef / t_stat / p_value: [k + 1][len] (row k = the intercept); r2 / n_obs:
+ * [len]; summary (Fama-MacBeth, NULL: not written): [k + 1][PQ_REGRESS_SUMMARY_COLS] over the days with a solution */
+pq_status pq_xsec_regress(pq_ctx *, const pq_batch *, const double *const *factors, int32_t k, const double *fwd_return, double *coef,
+                          double *t_stat, double *p_value, double *r2, int32_t *n_obs, double *summary);
+/* per-symbol time-series regression over the days.  Bit j of series_mask: factors[j] is one [len] series shared by every symbol (e.g. a
+ * market return).  coef / t_stat / p_value: [n_series][k + 1] (column k = the intercept); r2 / n_obs: [n_series] */
+pq_status pq_ts_regress(pq_ctx *, const pq_batch *, const double *const *factors, int32_t k, uint32_t series_mask, const double *ret,
+                        double *coef, double *t_stat, double *p_value, double *r2, int32_t *n_obs);
+/* correlation t-test: t = corr sqrt((n - 2) / (1 - corr corr)), p on n - 2; NULL where corr is NaN, n < 3 or 1 - corr^2 == 0 */
+pq_status pq_corr_t_test(pq_ctx *, const double *corr, const int32_t *n_valid, int64_t len, double *t_stat, double *p_value);
+
 /* ---- suites: record many calls, replay them as a few chip-filling grids ----
  * One indicator over N symbols is only N/64 wavefronts -- far too few for 256 CUs -- but a DataFrame query asks
  * for many indicators at once (df.with_columns([...]) in the reference; Polars then calls the plugin once per

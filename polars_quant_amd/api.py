@@ -577,6 +577,112 @@ def factor_clean(factor, winsorize=None, winsorize_n=None, cap=None, log_cap: bo
     return out[:, :T]
 
 
+
+REGRESS_MAX_K = 8             # PQ_REGRESS_MAX_K
+REGRESS_SUMMARY_COLS = 5      # PQ_REGRESS_SUMMARY_COLS: n_days, mean_coef, std_coef, t_stat, p_value
+
+
+def _shape(x):
+    return tuple(x.shape) if hasattr(x, "shape") else np.shape(x)
+
+
+def _regress_args(factors, ret, series_ok):
+    """argument checks of xsec_regress / ts_regress that need no device: factors a list / tuple of [N, T] (or, series_ok, [T]) arrays
+    or one [K, N, T] array -> (list of factor columns, [N, T] of the return)"""
+    rs = _shape(ret)
+    if len(rs) != 2:
+        raise ValueError(f"the return must be [N, T], not {rs}")
+    if isinstance(factors, (list, tuple)):
+        cols = list(factors)
+    else:
+        fs = _shape(factors)
+        if len(fs) != 3:
+            raise ValueError(f"factors must be a list of [N, T] arrays or one [K, N, T] array, not {fs}")
+        cols = [factors[j] for j in range(fs[0])]
+    if not 1 <= len(cols) <= REGRESS_MAX_K:
+        raise ValueError(f"the number of factors must be in 1..{REGRESS_MAX_K}, not {len(cols)}")
+    for j, c in enumerate(cols):
+        cs = _shape(c)
+        if cs != rs and not (series_ok and cs == rs[1:]):
+            want = f"{rs} or {rs[1:]}" if series_ok else f"{rs}"
+            raise ValueError(f"factor {j} must have shape {want}, not {cs}")
+    return cols, rs
+
+
+def _regress_call(fn_name, cols, ret, series_ok, make_outs, extra):
+    """uploads the factor columns and the return onto one row pitch, allocates the outputs on their device (make_outs(device) -> list of
+    output tensors, None: not written) and calls fn_name"""
+    ser = [series_ok and len(_shape(c)) == 1 for c in cols]
+    mats = _same_layout([_to_device(c)[0] for c, s in zip(cols, ser) if not s] + [_to_device(ret)[0]])
+    r = mats[-1]
+    dev = r.device
+    n, T = r.shape
+    b = _batch_of(r)
+    it = iter(mats[:-1])
+    fs = [_to_device(c)[0].reshape(-1).contiguous() if s else next(it) for c, s in zip(cols, ser)]
+    mask = sum(1 << j for j, s in enumerate(ser) if s)
+    vp = C.c_void_p
+    ptrs = (vp * len(fs))(*[f.data_ptr() for f in fs])
+    outs = make_outs(dev)
+    with torch.cuda.device(dev):
+        check(getattr(lib(), fn_name)(ctx(dev.index), C.byref(b), ptrs if n and T else None, C.c_int32(len(fs)), *extra(mask),
+                                      vp(r.data_ptr()) if n and T else None, *[vp(o.data_ptr()) if o is not None and o.numel() else None
+                                                                              for o in outs]))
+    return outs
+
+
+def xsec_regress(factors, fwd_return, summary: bool = True):
+    """D-17: per-day cross-sectional OLS of the forward return on K factors (each [N, T]; a list or a [K, N, T] array) with an intercept
+    -> dict of device tensors: coef / t_stat / p_value [K + 1, T] (row K = the intercept), r_squared [T], n [T] (int32), and with
+    summary=True the Fama-MacBeth summary [K + 1, 5]: n_days, mean_coef, std_coef, t_stat, p_value over the days with a solution"""
+    cols, (n, T) = _regress_args(factors, fwd_return, False)
+    K = len(cols)
+
+    def make(dev):
+        f64 = dict(dtype=torch.float64, device=dev)
+        return [torch.empty((K + 1, T), **f64), torch.empty((K + 1, T), **f64), torch.empty((K + 1, T), **f64), torch.empty(T, **f64),
+                torch.empty(T, dtype=torch.int32, device=dev), torch.empty((K + 1, REGRESS_SUMMARY_COLS), **f64) if summary else None]
+    coef, t, p, r2, nobs, summ = _regress_call("pq_xsec_regress", cols, fwd_return, False, make, lambda mask: ())
+    out = {"coef": coef, "t_stat": t, "p_value": p, "r_squared": r2, "n": nobs}
+    if summ is not None:
+        if T == 0:      # no day: nothing was launched
+            summ.copy_(torch.tensor([[0.0] + [float("nan")] * 4] * (K + 1), dtype=torch.float64))
+        out["summary"] = summ
+    return out
+
+
+def ts_regress(factors, returns):
+    """D-17: per-symbol time-series OLS of returns [N, T] on K factors, each [N, T] or a [T] series shared by every symbol (a list, or a
+    [K, N, T] array), with an intercept -> dict of device tensors: coef / t_stat / p_value [N, K + 1] (column K = the intercept),
+    r_squared [N], n_obs [N] (int32)"""
+    cols, (n, T) = _regress_args(factors, returns, True)
+    K = len(cols)
+
+    def make(dev):
+        f64 = dict(dtype=torch.float64, device=dev)
+        return [torch.empty((n, K + 1), **f64), torch.empty((n, K + 1), **f64), torch.empty((n, K + 1), **f64), torch.empty(n, **f64),
+                torch.empty(n, dtype=torch.int32, device=dev)]
+    coef, t, p, r2, nobs = _regress_call("pq_ts_regress", cols, returns, True, make, lambda mask: (C.c_uint32(mask),))
+    return {"coef": coef, "t_stat": t, "p_value": p, "r_squared": r2, "n_obs": nobs}
+
+
+def corr_t_test(corr, n_valid):
+    """D-17: t-test of per-day correlations (IC or Rank-IC) -> (t_stat [T], p_value [T]) device tensors: t = corr sqrt((n - 2) /
+    (1 - corr^2)), two-sided p on n - 2 degrees of freedom; NULL where corr is NaN, n < 3 or corr^2 == 1"""
+    c = _to_device(corr)[0].contiguous().reshape(-1)
+    nv = n_valid.to(device=c.device, dtype=torch.int32) if isinstance(n_valid, torch.Tensor) else \
+        torch.from_numpy(np.ascontiguousarray(np.asarray(n_valid), dtype=np.int32)).to(c.device)
+    nv = nv.contiguous().reshape(-1)
+    if nv.numel() != c.numel():
+        raise ValueError(f"n_valid must have one count per correlation: {nv.numel()} vs {c.numel()}")
+    dev = c.device
+    t, p = torch.empty_like(c), torch.empty_like(c)
+    vp = C.c_void_p
+    with torch.cuda.device(dev):
+        check(lib().pq_corr_t_test(ctx(dev.index), vp(c.data_ptr()) if c.numel() else None, vp(nv.data_ptr()) if c.numel() else None,
+                                   C.c_int64(c.numel()), vp(t.data_ptr()) if c.numel() else None, vp(p.data_ptr()) if c.numel() else None))
+    return t, p
+
 def _signal_call(fn_name, cols, *scalars):
     ts = [_to_device(c)[0].contiguous() for c in cols]
     dev = ts[0].device

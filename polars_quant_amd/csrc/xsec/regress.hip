@@ -1,0 +1,483 @@
+// xsec/regress.hip -- OLS with t-tests: the per-day cross-sectional regression (Factor.factor_return / fama_macbeth), the per-symbol
+// time-series regression (Factor.time_series_regression) and the correlation t-test (Factor.ic_test); README.md:1521-1600,
+// README-only => decision D-17, DESIGN.md section 2.
+//
+// Columns are symbol-major [n_series][stride].  A "unit" is what one regression is fitted for: a day (cross-sectional form: the sums run
+// over the symbols of a strided column) or a symbol (time-series form: the sums run over the days of a row).  Model r = a + sum_j b_j f_j.
+//  1. passes:  one thread per (unit, block of 256 summation indices) sums its block in ascending index order from 0.0, members only:
+//              pass 1 n, sum r, sum f_j; pass 2 the centred cross-products C[j][k] (k <= j), c[j] and Srr; pass 3 the squared
+//              residuals.  Cross-sectional: consecutive threads on consecutive days (coalesced).  Time-series: consecutive threads on
+//              consecutive symbols, each walking its own row; a factor flagged in series_mask is one [len] series read by every symbol.
+//  2. combine: one thread per unit adds the block sums in ascending block order from 0.0.  After pass 2 it factorises C = L D L^T,
+//              solves for b and the intercept, and keeps diag(C^-1) and fbar^T C^-1 fbar for the standard errors; after pass 3 it
+//              writes coef / t / p / R^2 / n.  The operation order is D-17's, restated in tests/xsec_regress_ref.py.
+//  3. summary: (cross-sectional) one 64-lane workgroup per regressor: the Fama-MacBeth mean / std / t / p over the days with a solution.
+// p-values: two-sided Student t, p = I_{df / (df + t^2)}(df / 2, 1/2), by the Lentz continued fraction in double-double arithmetic
+// (near x = 1 the fraction loses ~log10(1 / (1 - x)) digits in plain f64), with log Gamma(a + 1/2) / Gamma(a) from its asymptotic
+// series (lgamma(a) - lgamma(a + 1/2) cancels at large df).  Accurate to a few 1e-13 relative on df in [1, 1e5], |t| <= 50.
+#include "xsec_dev.h"
+
+namespace {
+
+constexpr int RG_MAX_K = 8;             // PQ_REGRESS_MAX_K
+constexpr int RG_SUMMARY_COLS = 5;      // PQ_REGRESS_SUMMARY_COLS
+constexpr double RG_SINGULAR = 1e-12;   // pivot D_j <= 1e-12 * C[j][j]: singular
+
+// ---------------------------------------------------------------- Student-t p-value
+struct Dd { double hi, lo; };
+__device__ __forceinline__ Dd dd_two_sum(double a, double b) {
+    const double s = a + b, bb = s - a;
+    return Dd{s, (a - (s - bb)) + (b - bb)};
+}
+__device__ __forceinline__ Dd dd_quick(double a, double b) {
+    const double s = a + b;
+    return Dd{s, b - (s - a)};
+}
+__device__ __forceinline__ Dd dd_add(Dd x, Dd y) {
+    const Dd s = dd_two_sum(x.hi, y.hi);
+    return dd_quick(s.hi, s.lo + (x.lo + y.lo));
+}
+__device__ __forceinline__ Dd dd_mul(Dd x, Dd y) {
+    const double p = x.hi * y.hi, e = fma(x.hi, y.hi, -p);
+    return dd_quick(p, e + (x.hi * y.lo + x.lo * y.hi));
+}
+__device__ __forceinline__ Dd dd_div(Dd x, Dd y) {
+    const double q1 = x.hi / y.hi;
+    const Dd p = dd_mul(y, Dd{q1, 0.0});
+    const Dd r = dd_add(x, Dd{-p.hi, -p.lo});
+    return dd_quick(q1, r.hi / y.hi);
+}
+__device__ __forceinline__ Dd dd_floor(Dd x) { return fabs(x.hi) < 1e-300 ? Dd{1e-300, 0.0} : x; }
+
+// continued fraction of I_x(a, b) (Numerical Recipes' betacf, modified Lentz), x in double-double; a, b are multiples of 1/2 small
+// enough that every numerator and denominator below is exact in f64
+__device__ double rg_betacf(Dd x, double a, double b) {
+    const double qab = a + b, qap = a + 1.0, qam = a - 1.0;
+    const Dd one{1.0, 0.0};
+    Dd c = one, d = dd_floor(dd_add(one, dd_div(dd_mul(x, Dd{-qab, 0.0}), Dd{qap, 0.0})));
+    d = dd_div(one, d);
+    Dd h = d;
+    for (int m = 1; m <= 100000; m++) {
+        const double m2 = 2.0 * m, dm = (double)m;
+        Dd del{1.0, 0.0};
+#pragma unroll
+        for (int half = 0; half < 2; half++) {
+            const double num = half == 0 ? dm * (b - dm) : -(a + dm) * (qab + dm);
+            const double den = half == 0 ? (qam + m2) * (a + m2) : (a + m2) * (qap + m2);
+            const Dd aa = dd_div(dd_mul(x, Dd{num, 0.0}), Dd{den, 0.0});
+            d = dd_floor(dd_add(dd_mul(d, aa), one));
+            c = dd_floor(dd_add(dd_div(aa, c), one));
+            d = dd_div(one, d);
+            del = dd_mul(d, c);
+            h = dd_mul(h, del);
+        }
+        if (fabs((del.hi - 1.0) + del.lo) < 1e-17) break;
+    }
+    return h.hi;
+}
+
+// log(Gamma(a + 1/2) / Gamma(a)), a >= 1/2: shift a up to >= 16, then 1/2 log a - 1/(8a) + 1/(192a^3) - 1/(640a^5) + 17/(14336a^7)
+// - 31/(18432a^9) (error < 1e-17 there)
+__device__ double rg_lgamma_half_ratio(double a) {
+    double prod = 1.0;
+    while (a < 16.0) {
+        prod *= (a + 0.5) / a;
+        a += 1.0;
+    }
+    const double ia = 1.0 / a, ia2 = ia * ia;
+    const double s = ia * (-1.0 / 8 + ia2 * (1.0 / 192 + ia2 * (-1.0 / 640 + ia2 * (17.0 / 14336 + ia2 * (-31.0 / 18432)))));
+    return 0.5 * log(a) + s - log(prod);
+}
+
+// two-sided Student-t p-value of t on df > 0 degrees of freedom: I_x(df/2, 1/2), x = df / (df + t^2), 1 - x = t^2 / (df + t^2)
+// taken directly; 1 at t == 0 (or t^2 below the f64 range), 0 at |t| == inf
+__device__ double rg_t_pvalue(double t, double df) {
+    if (!isfinite(t)) return t == t ? 0.0 : pq_null();
+    const double t2h = t * t;
+    if (t2h == 0.0) return 1.0;
+    if (!(t2h < HUGE_VAL)) return 0.0;
+    const Dd t2{t2h, fma(t, t, -t2h)}, den = dd_add(Dd{df, 0.0}, t2);
+    const Dd x = dd_div(Dd{df, 0.0}, den), y = dd_div(t2, den);
+    const double a = 0.5 * df;
+    const double e = a * -log1p(t2h / df) + 0.5 * log(y.hi) + rg_lgamma_half_ratio(a);   // log(x^a (1-x)^(1/2) / B(a, 1/2)) + log sqrt(pi)
+    const double front = exp(e) / 1.7724538509055160273;                                   // / sqrt(pi)
+    if (x.hi < (a + 1.0) / (a + 2.5)) return front * rg_betacf(x, a, 0.5) / a;
+    return 1.0 - front * rg_betacf(y, 0.5, a) / 0.5;
+}
+
+// ---------------------------------------------------------------- passes
+enum RgPass { RG_P1 = 1, RG_P2 = 2, RG_P3 = 3 };
+
+template <int K> struct RgNa {   // accumulators per pass
+    static constexpr int P1 = K + 1, P2 = K * (K + 1) / 2 + K + 1, P3 = 1;
+};
+
+struct RgIn {
+    const double *f[RG_MAX_K];
+    const double *r;
+    uint32_t series;       // time-series form: bit j = f[j] is one [len] series shared by every symbol
+    Dims d;
+};
+
+// per-unit state: [rows][units] f64 rows
+struct RgUnit {
+    int32_t *n;
+    int32_t *ok;       // 1: solved
+    double *mean;      // [K + 1]: rbar, fbar_0 .. fbar_{K-1}
+    double *b;         // [K + 1]: b_0 .. b_{K-1}, intercept
+    double *v;         // [K + 1]: diag(C^-1), then 1/n + fbar^T C^-1 fbar
+    double *srr;
+};
+
+template <int K, int P, bool TS>
+__global__ __launch_bounds__(64) void rg_pass_kernel(RgIn in, RgUnit un, double *ps, int32_t *pcnt) {
+    constexpr int NA = P == RG_P1 ? RgNa<K>::P1 : (P == RG_P2 ? RgNa<K>::P2 : RgNa<K>::P3);
+    const Dims d = in.d;
+    const int64_t units = TS ? d.n : d.len, span = TS ? d.len : d.n;
+    const int64_t u = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (u >= units) return;
+    double rbar = 0.0, fbar[K], b[K];
+#pragma unroll
+    for (int j = 0; j < K; j++) { fbar[j] = 0.0; b[j] = 0.0; }
+    if (P >= RG_P2) {
+        rbar = un.mean[u];
+#pragma unroll
+        for (int j = 0; j < K; j++) fbar[j] = un.mean[(int64_t)(j + 1) * units + u];
+    }
+    if (P == RG_P3) {
+#pragma unroll
+        for (int j = 0; j < K; j++) b[j] = un.b[(int64_t)j * units + u];
+    }
+    double acc[NA];
+#pragma unroll
+    for (int q = 0; q < NA; q++) acc[q] = 0.0;
+    int cnt = 0;
+    const int64_t i_lo = (int64_t)blockIdx.y * XS_BLOCK, i_hi = i_lo + XS_BLOCK < span ? i_lo + XS_BLOCK : span;
+    constexpr int B = K + 1 <= 2 ? 8 : (K + 1 <= 4 ? 4 : 2);   // indices loaded ahead: about 16 loads in flight per lane
+    for (int64_t i0 = i_lo; i0 < i_hi; i0 += B) {
+        double rv[B], fv[B][K];
+#pragma unroll
+        for (int k = 0; k < B; k++) {
+            const int64_t i = i0 + k < i_hi ? i0 + k : i_hi - 1;
+            const int64_t s = TS ? u : i, t = TS ? i : u, o = s * d.stride + t;
+            rv[k] = in.r[o];
+#pragma unroll
+            for (int j = 0; j < K; j++) fv[k][j] = (TS && ((in.series >> j) & 1u)) ? in.f[j][t] : in.f[j][o];
+        }
+#pragma unroll
+        for (int k = 0; k < B; k++) {
+            if (i0 + k >= i_hi) break;
+            bool mem = xs_valid(rv[k]);
+#pragma unroll
+            for (int j = 0; j < K; j++) mem = mem && xs_valid(fv[k][j]);
+            if (!mem) continue;
+            cnt += 1;
+            if (P == RG_P1) {
+                acc[0] += rv[k];
+#pragma unroll
+                for (int j = 0; j < K; j++) acc[1 + j] += fv[k][j];
+                continue;
+            }
+            const double dr = rv[k] - rbar;
+            double df[K];
+#pragma unroll
+            for (int j = 0; j < K; j++) df[j] = fv[k][j] - fbar[j];
+            if (P == RG_P2) {
+#pragma unroll
+                for (int j = 0; j < K; j++)
+#pragma unroll
+                    for (int l = 0; l <= j; l++) acc[j * (j + 1) / 2 + l] += df[j] * df[l];
+#pragma unroll
+                for (int j = 0; j < K; j++) acc[K * (K + 1) / 2 + j] += df[j] * dr;
+                acc[NA - 1] += dr * dr;
+                continue;
+            }
+            double fit = 0.0;
+#pragma unroll
+            for (int j = 0; j < K; j++) fit += b[j] * df[j];
+            const double e = dr - fit;
+            acc[0] += e * e;
+        }
+    }
+#pragma unroll
+    for (int q = 0; q < NA; q++) ps[((int64_t)blockIdx.y * NA + q) * units + u] = acc[q];
+    if (P == RG_P1) pcnt[(int64_t)blockIdx.y * units + u] = cnt;
+}
+
+template <int NA>
+__device__ __forceinline__ void rg_combine(const double *ps, int64_t nblk, int64_t units, int64_t u, double (&s)[NA]) {
+#pragma unroll
+    for (int q = 0; q < NA; q++) s[q] = 0.0;
+    for (int64_t k = 0; k < nblk; k++)
+#pragma unroll
+        for (int q = 0; q < NA; q++) s[q] += ps[(k * NA + q) * units + u];
+}
+
+// after pass 1: n and the means
+template <int K>
+__global__ __launch_bounds__(64) void rg_means_kernel(const double *ps, const int32_t *pcnt, int64_t nblk, int64_t units, RgUnit un) {
+    const int64_t u = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (u >= units) return;
+    double s[K + 1];
+    rg_combine<K + 1>(ps, nblk, units, u, s);
+    int32_t n = 0;
+    for (int64_t k = 0; k < nblk; k++) n += pcnt[k * units + u];
+    un.n[u] = n;
+    const double dn = (double)n;
+#pragma unroll
+    for (int q = 0; q <= K; q++) un.mean[(int64_t)q * units + u] = s[q] / dn;
+}
+
+// forward substitution with the unit lower-triangular L: z_m = v_m - sum_{i < m} L[m][i] z_i (sum ascending from 0.0)
+template <int K> __device__ __forceinline__ void rg_forward(const double (&L)[K][K], const double (&v)[K], double (&z)[K]) {
+#pragma unroll
+    for (int m = 0; m < K; m++) {
+        double s = 0.0;
+#pragma unroll
+        for (int i = 0; i < m; i++) s += L[m][i] * z[i];
+        z[m] = v[m] - s;
+    }
+}
+
+// after pass 2: C = L D L^T by rows, the solution b, the intercept, diag(C^-1) and 1/n + fbar^T C^-1 fbar
+template <int K>
+__global__ __launch_bounds__(64) void rg_solve_kernel(const double *ps, int64_t nblk, int64_t units, RgUnit un) {
+    const int64_t u = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (u >= units) return;
+    constexpr int NA = RgNa<K>::P2;
+    double s[NA];
+    rg_combine<NA>(ps, nblk, units, u, s);
+    un.srr[u] = s[NA - 1];
+    const int32_t n = un.n[u];
+    bool ok = n >= K + 2;
+    double L[K][K], D[K], W[K][K];
+#pragma unroll
+    for (int j = 0; j < K; j++)
+#pragma unroll
+        for (int k = 0; k < K; k++) { L[j][k] = j == k ? 1.0 : 0.0; W[j][k] = 0.0; }
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+#pragma unroll
+        for (int k = 0; k < j; k++) {
+            double w = s[j * (j + 1) / 2 + k];
+#pragma unroll
+            for (int m = 0; m < k; m++) w -= W[j][m] * L[k][m];
+            W[j][k] = w;
+            L[j][k] = w / D[k];
+        }
+        const double cjj = s[j * (j + 1) / 2 + j];
+        double dj = cjj;
+#pragma unroll
+        for (int m = 0; m < j; m++) dj -= W[j][m] * L[j][m];
+        D[j] = dj;
+        ok = ok && dj > RG_SINGULAR * cjj;   // singular: D_j <= 1e-12 C[j][j] (NaN from an overflow counts as singular)
+    }
+    un.ok[u] = ok ? 1 : 0;
+    if (!ok) return;
+    double c[K], z[K], b[K], fbar[K];
+#pragma unroll
+    for (int j = 0; j < K; j++) { c[j] = s[K * (K + 1) / 2 + j]; fbar[j] = un.mean[(int64_t)(j + 1) * units + u]; }
+    rg_forward<K>(L, c, z);
+#pragma unroll
+    for (int j = K - 1; j >= 0; j--) {   // y_j = z_j / D_j; b_j = y_j - sum_{m > j} L[m][j] b_m (m ascending, from 0.0)
+        double t = 0.0;
+#pragma unroll
+        for (int m = j + 1; m < K; m++) t += L[m][j] * b[m];
+        b[j] = z[j] / D[j] - t;
+    }
+    double sa = 0.0;
+#pragma unroll
+    for (int j = 0; j < K; j++) sa += b[j] * fbar[j];
+#pragma unroll
+    for (int j = 0; j < K; j++) un.b[(int64_t)j * units + u] = b[j];
+    un.b[(int64_t)K * units + u] = un.mean[u] - sa;
+    // (C^-1)_jj = sum_m (L^-1 e_j)_m^2 / D_m, m ascending from 0.0
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        double e[K], w[K];
+#pragma unroll
+        for (int m = 0; m < K; m++) e[m] = m == j ? 1.0 : 0.0;
+        rg_forward<K>(L, e, w);
+        double vj = 0.0;
+#pragma unroll
+        for (int m = 0; m < K; m++) vj += w[m] * w[m] / D[m];
+        un.v[(int64_t)j * units + u] = vj;
+    }
+    double w[K], q = 0.0;
+    rg_forward<K>(L, fbar, w);
+#pragma unroll
+    for (int m = 0; m < K; m++) q += w[m] * w[m] / D[m];
+    un.v[(int64_t)K * units + u] = 1.0 / (double)n + q;
+}
+
+// after pass 3: s^2 = SSE / (n - K - 1), se_j = sqrt(s^2 V_jj), t_j = b_j / se_j, p on n - K - 1, R^2 = 1 - SSE / Srr.
+// Outputs [K + 1][units] (cross-sectional) or [units][K + 1] (time-series, TS).
+template <int K, bool TS>
+__global__ __launch_bounds__(64) void rg_final_kernel(const double *ps, int64_t nblk, int64_t units, RgUnit un, double *coef,
+                                                      double *tst, double *pv, double *r2, int32_t *n_obs) {
+    const int64_t u = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (u >= units) return;
+    double sse[1];
+    rg_combine<1>(ps, nblk, units, u, sse);
+    const int32_t n = un.n[u];
+    n_obs[u] = n;
+    const bool ok = un.ok[u] != 0;
+    const double df = (double)(n - K - 1), s2 = sse[0] / df, srr = ok ? un.srr[u] : 0.0;
+    r2[u] = ok && srr != 0.0 ? 1.0 - sse[0] / srr : pq_null();
+#pragma unroll
+    for (int j = 0; j <= K; j++) {
+        const int64_t o = TS ? u * (K + 1) + j : (int64_t)j * units + u;
+        if (!ok) { coef[o] = pq_null(); tst[o] = pq_null(); pv[o] = pq_null(); continue; }
+        const double bj = un.b[(int64_t)j * units + u], se = sqrt(s2 * un.v[(int64_t)j * units + u]);
+        coef[o] = bj;
+        const double t = se == 0.0 ? pq_null() : bj / se;
+        tst[o] = t;
+        pv[o] = se == 0.0 ? pq_null() : rg_t_pvalue(t, df);
+    }
+}
+
+// Fama-MacBeth summary, one 64-lane workgroup per coefficient row: n_days, mean, std (ddof 1), t = mean / (std / sqrt(n_days)), p on
+// n_days - 1, over the non-NaN days of the row (the days with a solution), ascending sequential sums from 0.0
+__global__ __launch_bounds__(64) void rg_summary_kernel(const double *coef, int64_t len, double *summary) {
+    __shared__ double buf[XS_CHUNK];
+    const double *x = coef + (int64_t)blockIdx.x * len;
+    double s, ss;
+    int64_t n, pos;
+    xs_seq<false>(x, len, 0.0, buf, s, n, pos);
+    const double m = n > 0 ? s / (double)n : 0.0;
+    xs_seq<true>(x, len, m, buf, ss, n, pos);
+    if (threadIdx.x == 0) {
+        const double sd = n >= 2 ? sqrt(ss / (double)(n - 1)) : 0.0;
+        const bool ok = n >= 2 && sd != 0.0;
+        double *o = summary + (int64_t)blockIdx.x * RG_SUMMARY_COLS;
+        o[0] = (double)n;
+        o[1] = n > 0 ? m : pq_null();
+        o[2] = ok ? sd : pq_null();
+        const double t = ok ? m / (sd / sqrt((double)n)) : pq_null();
+        o[3] = t;
+        o[4] = ok ? rg_t_pvalue(t, (double)(n - 1)) : pq_null();
+    }
+}
+
+// t = r sqrt((n - 2) / (1 - r r)), p on n - 2; NULL where r is NaN, n < 3 or 1 - r r == 0
+__global__ __launch_bounds__(256) void rg_corr_t_kernel(const double *corr, const int32_t *n_valid, int64_t len, double *tst, double *pv) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= len) return;
+    const double r = corr[i];
+    const int32_t n = n_valid[i];
+    const double den = 1.0 - r * r;
+    if (r != r || n < 3 || den == 0.0) { tst[i] = pq_null(); pv[i] = pq_null(); return; }
+    const double df = (double)(n - 2), t = r * sqrt(df / den);
+    tst[i] = t;
+    pv[i] = rg_t_pvalue(t, df);
+}
+
+struct RgOut {
+    double *coef, *tst, *pv, *r2;
+    int32_t *n_obs;
+    double *summary;
+};
+
+template <int K, bool TS>
+pq_status rg_run(pq_ctx *ctx, const RgIn &in, const RgOut &out) {
+    const Dims d = in.d;
+    const int64_t units = TS ? d.n : d.len, span = TS ? d.len : d.n;
+    const int64_t nblk = (span + XS_BLOCK - 1) / XS_BLOCK > 0 ? (span + XS_BLOCK - 1) / XS_BLOCK : 1;
+    const size_t U = (size_t)units, part = (size_t)nblk * U;
+    // workspace: n, ok (i32) | mean, b, v [K + 1] and srr (f64 rows) | block partials [nblk][NA][units] (f64) | block counts (i32)
+    const size_t o_ok = xs_al(U * 4), o_rows = o_ok + xs_al(U * 4), row = xs_al(U * 8), o_ps = o_rows + (3 * (K + 1) + 1) * row,
+                 o_pc = o_ps + xs_al(part * RgNa<K>::P2 * 8), total = o_pc + xs_al(part * 4);
+    PQ_TRY(pq_ws_reserve(ctx, total));
+    unsigned char *ws = (unsigned char *)ctx->ws;
+    RgUnit un;
+    un.n = (int32_t *)ws;
+    un.ok = (int32_t *)(ws + o_ok);
+    un.mean = (double *)(ws + o_rows);
+    un.b = (double *)(ws + o_rows + (K + 1) * row);
+    un.v = (double *)(ws + o_rows + 2 * (K + 1) * row);
+    un.srr = (double *)(ws + o_rows + 3 * (K + 1) * row);
+    double *ps = (double *)(ws + o_ps);
+    int32_t *pc = (int32_t *)(ws + o_pc);
+    const dim3 gp((unsigned)((units + 63) / 64), (unsigned)nblk), gu((unsigned)((units + 63) / 64));
+    hipStream_t st = ctx->stream;
+    hipLaunchKernelGGL((rg_pass_kernel<K, RG_P1, TS>), gp, dim3(64), 0, st, in, un, ps, pc);
+    hipLaunchKernelGGL(rg_means_kernel<K>, gu, dim3(64), 0, st, (const double *)ps, (const int32_t *)pc, nblk, units, un);
+    hipLaunchKernelGGL((rg_pass_kernel<K, RG_P2, TS>), gp, dim3(64), 0, st, in, un, ps, pc);
+    hipLaunchKernelGGL(rg_solve_kernel<K>, gu, dim3(64), 0, st, (const double *)ps, nblk, units, un);
+    hipLaunchKernelGGL((rg_pass_kernel<K, RG_P3, TS>), gp, dim3(64), 0, st, in, un, ps, pc);
+    hipLaunchKernelGGL((rg_final_kernel<K, TS>), gu, dim3(64), 0, st, (const double *)ps, nblk, units, un, out.coef, out.tst, out.pv,
+                       out.r2, out.n_obs);
+    if (!TS && out.summary)
+        hipLaunchKernelGGL(rg_summary_kernel, dim3(K + 1), dim3(64), 0, st, (const double *)out.coef, units, out.summary);
+    PQ_HIP_TRY(hipGetLastError());
+    return PQ_OK;
+}
+
+template <bool TS>
+pq_status rg_dispatch(pq_ctx *ctx, int k, const RgIn &in, const RgOut &out) {
+    switch (k) {
+    case 1: return rg_run<1, TS>(ctx, in, out);
+    case 2: return rg_run<2, TS>(ctx, in, out);
+    case 3: return rg_run<3, TS>(ctx, in, out);
+    case 4: return rg_run<4, TS>(ctx, in, out);
+    case 5: return rg_run<5, TS>(ctx, in, out);
+    case 6: return rg_run<6, TS>(ctx, in, out);
+    case 7: return rg_run<7, TS>(ctx, in, out);
+    default: return rg_run<8, TS>(ctx, in, out);
+    }
+}
+
+pq_status rg_args(pq_ctx *ctx, const pq_batch *b, const char *what, const double *const *factors, int32_t k, const double *ret, RgIn &in) {
+    PQ_TRY(pq_check(ctx, b));
+    if (k < 1 || k > RG_MAX_K) { pq_set_error("%s: k must be in [1, 8]", what); return PQ_ERR_ARG; }
+    if (ctx->rec) { pq_set_error("%s cannot be recorded into a suite", what); return PQ_ERR_UNSUPPORTED; }
+    if (b->offsets) { pq_set_error("%s: ragged batches are not supported", what); return PQ_ERR_UNSUPPORTED; }
+    const bool empty = b->n_series == 0 || b->len == 0;
+    if (!empty && (!factors || !ret)) { pq_set_error("%s: null pointer", what); return PQ_ERR_ARG; }
+    in = RgIn{};
+    in.r = ret;
+    in.d = dims_of(b);
+    for (int j = 0; j < k && !empty; j++) {
+        if (!factors[j]) { pq_set_error("%s: null factor pointer", what); return PQ_ERR_ARG; }
+        in.f[j] = factors[j];
+    }
+    return PQ_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+pq_status pq_xsec_regress(pq_ctx *ctx, const pq_batch *b, const double *const *factors, int32_t k, const double *fwd_return, double *coef,
+                          double *t_stat, double *p_value, double *r2, int32_t *n_obs, double *summary) {
+    RgIn in;
+    PQ_TRY(rg_args(ctx, b, "pq_xsec_regress", factors, k, fwd_return, in));
+    PQ_REQUIRE(b->len == 0 || (coef && t_stat && p_value && r2 && n_obs), "pq_xsec_regress: null output pointer");
+    if (b->len == 0) return PQ_OK;
+    return rg_dispatch<false>(ctx, k, in, RgOut{coef, t_stat, p_value, r2, n_obs, summary});
+}
+
+pq_status pq_ts_regress(pq_ctx *ctx, const pq_batch *b, const double *const *factors, int32_t k, uint32_t series_mask, const double *ret,
+                        double *coef, double *t_stat, double *p_value, double *r2, int32_t *n_obs) {
+    RgIn in;
+    PQ_TRY(rg_args(ctx, b, "pq_ts_regress", factors, k, ret, in));
+    PQ_REQUIRE((series_mask >> k) == 0, "pq_ts_regress: series_mask names a factor beyond k");
+    PQ_REQUIRE(b->n_series == 0 || (coef && t_stat && p_value && r2 && n_obs), "pq_ts_regress: null output pointer");
+    if (b->n_series == 0) return PQ_OK;
+    in.series = series_mask;
+    return rg_dispatch<true>(ctx, k, in, RgOut{coef, t_stat, p_value, r2, n_obs, nullptr});
+}
+
+pq_status pq_corr_t_test(pq_ctx *ctx, const double *corr, const int32_t *n_valid, int64_t len, double *t_stat, double *p_value) {
+    PQ_REQUIRE(ctx, "pq_corr_t_test: null context");
+    PQ_REQUIRE(len >= 0, "pq_corr_t_test: negative length");
+    PQ_REQUIRE(len == 0 || (corr && n_valid && t_stat && p_value), "pq_corr_t_test: null pointer");
+    if (ctx->rec) { pq_set_error("pq_corr_t_test cannot be recorded into a suite"); return PQ_ERR_UNSUPPORTED; }
+    if (len == 0) return PQ_OK;
+    PQ_HIP_TRY(hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(rg_corr_t_kernel, dim3((unsigned)((len + 255) / 256)), dim3(256), 0, ctx->stream, corr, n_valid, len, t_stat, p_value);
+    PQ_HIP_TRY(hipGetLastError());
+    return PQ_OK;
+}
+
+} // extern "C"

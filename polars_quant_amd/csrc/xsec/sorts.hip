@@ -20,8 +20,6 @@
 
 namespace {
 
-constexpr int XS_CHUNK = 2048;     // days staged in LDS per step of the sequential summaries
-
 struct XsRule {
     int32_t mode;    // 0: quantiles, 1: long / short
     int32_t q;       // number of quantiles (mode 0)
@@ -196,49 +194,6 @@ __global__ __launch_bounds__(64) void xs_group_combine_kernel(const double *psum
         if (g == ng - 1) hi = m;
     }
     spread[t] = (pq_isnull(lo) || pq_isnull(hi)) ? pq_null() : hi - lo;
-}
-
-// Sequential statistics of a series x[0 .. len) over its non-NaN entries, in ascending order from 0.0.  SQ = false: count, sum and
-// count of entries > 0; SQ = true: sum of (x - center)^2.  The 64 lanes stage XS_CHUNK terms at a time in LDS -- the entry (or its
-// square deviation), +0.0 for a NaN entry -- and count in parallel (integers: any order); lane 0 adds the staged terms in order.
-// A +0.0 term leaves the sum unchanged: it starts at +0.0, and a round-to-nearest sum that starts there is never -0.0.  Sum and
-// counts are returned in every lane.
-template <bool SQ>
-__device__ void xs_seq(const double *x, int64_t len, double center, double *buf, double &acc, int64_t &n, int64_t &pos) {
-    acc = 0.0;
-    long long cn = 0, cp = 0;
-    for (int64_t c0 = 0; c0 < len; c0 += XS_CHUNK) {
-        const int64_t m = len - c0 < XS_CHUNK ? len - c0 : XS_CHUNK, m8 = (m + 7) & ~7LL;
-        for (int64_t i0 = threadIdx.x; i0 < m8; i0 += 64 * 8) { // eight global loads in flight per lane
-            double v[8];
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const int64_t i = i0 + k * 64;
-                v[k] = i < m ? x[c0 + i] : __longlong_as_double(0x7FF8000000000000LL);
-            }
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const bool ok = v[k] == v[k];
-                cn += ok;
-                if (!SQ) cp += v[k] > 0.0;
-                const double dv = v[k] - center;
-                if (i0 + k * 64 < m8) buf[i0 + k * 64] = ok ? (SQ ? dv * dv : v[k]) : 0.0;
-            }
-        }
-        __syncthreads();
-        if (threadIdx.x == 0)
-            for (int64_t i = 0; i < m8; i += 8) {
-                double v[8];
-#pragma unroll
-                for (int k = 0; k < 8; k++) v[k] = buf[i + k];
-#pragma unroll
-                for (int k = 0; k < 8; k++) acc += v[k];
-            }
-        __syncthreads();
-    }
-    for (int o = 32; o > 0; o >>= 1) { cn += __shfl_xor(cn, o, 64); cp += __shfl_xor(cp, o, 64); }
-    n = cn; pos = cp;
-    acc = __shfl(acc, 0, 64); // the next pass centres on the mean in every lane
 }
 
 // one 64-lane workgroup per row: rows 0 .. ng-1 = the groups (mean_return[g], turnover[g]), row ng = the spread / long-short series

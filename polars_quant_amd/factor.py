@@ -1,14 +1,17 @@
 """Factor -- the evaluation half of the README's `Factor` class (README.md:1429-1430, :1480-1482, :1626-1634): per-day
 cross-sectional IC, Rank-IC and their rolling mean / information ratio (decision D-12, oracle/backtest.c), and quantile sorts,
-long-short legs, turnover, coverage and IC statistics (decision D-15).  README-only in the reference.  Inputs are [N, T] arrays (symbol-major, like every other column of this
-package): the factor and the forward return of every symbol on every day.  `clean` is the README's factor cleaning step that comes
-before the evaluation (decision D-16).
+long-short legs, turnover, coverage and IC statistics (decision D-15), and the regressions and significance tests
+ic_test / factor_return / fama_macbeth / time_series_regression (decision D-17).  README-only in the reference.  Inputs are [N, T]
+arrays (symbol-major, like every other column of this package): the factor and the forward return of every symbol on every day.
+`clean` is the README's factor cleaning step that comes before the evaluation (decision D-16).
 """
 from __future__ import annotations
 
 import torch
 
 from . import api as _api
+
+IC_METHODS = {"pearson": 0, "spearman": 1}
 
 
 class Factor:
@@ -64,6 +67,39 @@ class Factor:
         """-> share of the non-null days with a positive (rank) IC (nan below 2 days)"""
         ic, _ = _api.factor_ic(factor, next_return, 1 if rank else 0)
         return float(_api.ic_stats(ic)[4])
+
+    # ---- D-17: regressions and significance tests (README.md:1521-1600)
+    def ic_test(self, factor, next_return, method="pearson"):
+        """-> {"ic", "n_valid", "t_stat", "p_value"}: [T] each; t = ic sqrt((n - 2) / (1 - ic^2)), two-sided p on n - 2 degrees of
+        freedom (method "pearson": IC, "spearman": Rank-IC)"""
+        if method not in IC_METHODS:
+            raise ValueError(f"method must be 'pearson' or 'spearman', not {method!r}")
+        ic, nv = _api.factor_ic(factor, next_return, IC_METHODS[method])
+        t, p = _api.corr_t_test(ic, nv)
+        return {"ic": ic, "n_valid": nv, "t_stat": t, "p_value": p}
+
+    def factor_return(self, factor, next_return):
+        """-> {"factor_return", "intercept", "t_stat", "p_value", "r_squared", "n"}: [T] each, the per-day cross-sectional OLS of the
+        next return on the factor with an intercept (t and p of the slope)"""
+        r = _api.xsec_regress([factor], next_return, summary=False)
+        return {"factor_return": r["coef"][0], "intercept": r["coef"][1], "t_stat": r["t_stat"][0], "p_value": r["p_value"][0],
+                "r_squared": r["r_squared"], "n": r["n"]}
+
+    def fama_macbeth(self, factors, next_return):
+        """factors: a list of [N, T] arrays or one [K, N, T] array -> {"mean_coef", "std_coef", "t_stat", "p_value", "n_days"}: [K + 1]
+        each (the intercept last), over the days with a solution, and "daily": {"coef", "t_stat", "p_value": [K + 1, T], "r_squared",
+        "n": [T]}, the per-day cross-sectional regressions"""
+        r = _api.xsec_regress(factors, next_return, summary=True)
+        s = r.pop("summary")
+        return {"mean_coef": s[:, 1], "std_coef": s[:, 2], "t_stat": s[:, 3], "p_value": s[:, 4], "n_days": s[:, 0], "daily": r}
+
+    def time_series_regression(self, factors, returns):
+        """factors: a list of [N, T] or [T] arrays (a [T] series, e.g. a market return, is shared by every symbol) or one [K, N, T]
+        array -> {"coefficient", "t_stat", "p_value": [N, K + 1] (the intercept last), "r_squared", "n_obs": [N]}, one OLS per symbol
+        over its days"""
+        r = _api.ts_regress(factors, returns)
+        return {"coefficient": r["coef"], "t_stat": r["t_stat"], "p_value": r["p_value"], "r_squared": r["r_squared"],
+                "n_obs": r["n_obs"]}
 
 
 def clean(factor, winsorize=None, winsorize_n=None, neutralize_market_cap=False, cap=None, neutralize_industry=False, industry=None,
