@@ -76,7 +76,7 @@ def check(pq, f, cap, ind, mode, use_cap, use_ind, stdz, pitch=None, wn=None):
     got = api.factor_clean(fd, mode, wn, cd, True, ind if use_ind else None, stdz)
     z = torch.log(cd).cpu().numpy() if use_cap else None
     exp = R.clean(f, mode, wn, z, ind if use_ind else None, None, stdz)
-    same(f"clean {mode} cap={use_cap} ind={use_ind} std={stdz} {f.shape} wn={wn}", got.cpu().numpy(), exp)
+    same(f"clean {mode} cap={use_cap} ind={use_ind} std={stdz} {f.shape} wn={wn} pitch={pitch}", got.cpu().numpy(), exp)
     return got
 
 

@@ -97,6 +97,21 @@ def check_xsec(pq, F, r, pitch=None, summary=True):
     return got, exp
 
 
+def check_ts(pq, cols, r, pitch=None):
+    """ts_regress on factor columns cols ([N, T] or a [T] series each) and returns r [N, T] against the restatement"""
+    from polars_quant_amd import api
+    got = api.ts_regress([to_dev(c, pitch) for c in cols], to_dev(r, pitch))
+    exp = R.ts_regress(cols, r)
+    ser = "".join("s" if np.ndim(c) == 1 else "m" for c in cols)
+    tag = f"ts K={len(cols)} {r.shape} factors={ser} pitch={pitch}"
+    same(f"coef {tag}", got["coef"].cpu().numpy(), exp["coef"])
+    same(f"t {tag}", got["t_stat"].cpu().numpy(), exp["t"])
+    same(f"r2 {tag}", got["r_squared"].cpu().numpy(), exp["r2"])
+    same(f"n {tag}", got["n_obs"].cpu().numpy(), exp["n"])
+    close_p(f"p {tag}", got["p_value"].cpu().numpy(), exp["p"])
+    return got, exp
+
+
 @pytest.mark.parametrize("K", KS)
 @pytest.mark.parametrize("shape", SHAPES, ids=[f"{n}x{t}" for n, t in SHAPES])
 def test_xsec_regress_bitwise(pq, shape, K):
@@ -119,7 +134,6 @@ def test_xsec_regress_odd_pitch_and_clean_data(pq, K):
 @pytest.mark.parametrize("K", KS)
 @pytest.mark.parametrize("shape", [(37, 50), (20, 600), (300, 131), (2, 3), (1, 5)], ids=lambda s: f"{s[0]}x{s[1]}")
 def test_ts_regress_bitwise(pq, shape, K):
-    from polars_quant_amd import api
     n, T = shape
     F, r = make(K, n, T, 7 * K + n + T)
     rng = np.random.default_rng(K + T)
@@ -132,14 +146,7 @@ def test_ts_regress_bitwise(pq, shape, K):
     if n >= 2 and T >= 3:
         r[1, 2:] = R.NULL                                  # a symbol with too few days
     for pitch in (None, T + 5):
-        got = api.ts_regress([to_dev(c, pitch) for c in cols], to_dev(r, pitch))
-        exp = R.ts_regress(cols, r)
-        tag = f"ts K={K} {shape} pitch={pitch}"
-        same(f"coef {tag}", got["coef"].cpu().numpy(), exp["coef"])
-        same(f"t {tag}", got["t_stat"].cpu().numpy(), exp["t"])
-        same(f"r2 {tag}", got["r_squared"].cpu().numpy(), exp["r2"])
-        same(f"n {tag}", got["n_obs"].cpu().numpy(), exp["n"])
-        close_p(f"p {tag}", got["p_value"].cpu().numpy(), exp["p"])
+        check_ts(pq, cols, r, pitch)
 
 
 def test_factor_methods(pq):

@@ -120,7 +120,7 @@ def test_k1_against_linregress():
         np.testing.assert_allclose(out["p"][0, t], lr.pvalue, rtol=1e-12)
 
 
-@pytest.mark.parametrize("K", [2, 3, 8])
+@pytest.mark.parametrize("K", range(1, 9))
 def test_against_lstsq_and_inverse_normal_equations(K):
     rng = np.random.default_rng(10 + K)
     n, T = 300, 4
@@ -137,6 +137,71 @@ def test_against_lstsq_and_inverse_normal_equations(K):
         np.testing.assert_allclose(out["p"][:, t], 2 * stats.t.sf(np.abs(beta / se), n - K - 1), rtol=1e-9)
         rc = r[:, t] - r[:, t].mean()
         np.testing.assert_allclose(out["r2"][t], 1.0 - res[0] / (rc @ rc), rtol=1e-10)
+
+
+@pytest.mark.parametrize("K", [4, 5, 6, 7])
+def test_time_series_form_against_lstsq(K):
+    """per-symbol OLS on the symbol's sample, with [T] series at j = 0 and j = K - 1 (one with NULL days) among [N, T] factors"""
+    rng = np.random.default_rng(40 + K)
+    N, T = 5, 700
+    cols = [rng.standard_normal((N, T)) for _ in range(K)]
+    cols[0] = rng.standard_normal(T)
+    cols[K - 1] = rng.standard_normal(T) + 0.5 * cols[0]
+    r = sum(0.1 * (j + 1) * np.broadcast_to(c, (N, T)) for j, c in enumerate(cols)) + rng.standard_normal((N, T))
+    cols[0][::13] = NULL
+    cols[2][3, ::7] = np.nan
+    r[1, ::5] = NULL
+    r[4, 3] = np.inf
+    out = R.ts_regress(cols, r)
+    for s in range(N):
+        Xs = np.column_stack([np.broadcast_to(c, (N, T))[s] for c in cols] + [np.ones(T)])
+        ok = np.isfinite(Xs).all(axis=1) & np.isfinite(r[s])
+        X, y = Xs[ok], r[s][ok]
+        n = len(y)
+        beta, res, _, _ = np.linalg.lstsq(X, y, rcond=None)
+        s2 = res[0] / (n - K - 1)
+        se = np.sqrt(np.diag(np.linalg.inv(X.T @ X)) * s2)
+        assert out["n"][s] == n, s
+        np.testing.assert_allclose(out["coef"][s], beta, rtol=1e-10, atol=1e-12)
+        np.testing.assert_allclose(out["coef"][s] / out["t"][s], se, rtol=1e-10)
+        np.testing.assert_allclose(out["p"][s], 2 * stats.t.sf(np.abs(beta / se), n - K - 1), rtol=1e-9)
+        yc = y - y.mean()
+        np.testing.assert_allclose(out["r2"][s], 1.0 - res[0] / (yc @ yc), rtol=1e-10)
+
+
+def test_ill_conditioned_day_against_mpmath():
+    """K = 5 with two factors correlated at rho ~ 0.999 and one of mean 1e6, sd 1: the slopes against the exact least-squares solution of
+    the same f64 data (mpmath, 50 digits) within 1e-14 * kappa_2(C) * |b|_inf, C the centred cross-product matrix"""
+    import mpmath
+    rng = np.random.default_rng(21)
+    n, K = 400, 5
+    F = rng.standard_normal((K, n))
+    F[1] = 0.999 * F[0] + np.sqrt(1.0 - 0.999 ** 2) * F[1]
+    F[2] = 1e6 + F[2]
+    r = 0.3 * F[0] - 0.2 * F[1] + 0.05 * (F[2] - 1e6) + 0.1 * F[3] - 0.4 * F[4] + 0.5 * rng.standard_normal(n)
+    out = R.xsec_regress([f[:, None] for f in F], r[:, None])
+    with mpmath.workdps(50):
+        cols = [[mpmath.mpf(float(v)) for v in f] for f in F]
+        ys = [mpmath.mpf(float(v)) for v in r]
+        means = [mpmath.fsum(c) / n for c in cols]
+        ybar = mpmath.fsum(ys) / n
+        dc = [[v - m for v in c] for c, m in zip(cols, means)]
+        dy = [v - ybar for v in ys]
+        C = mpmath.matrix(K, K)
+        c = mpmath.matrix(K, 1)
+        for j in range(K):
+            c[j] = mpmath.fsum(a * b for a, b in zip(dc[j], dy))
+            for k in range(K):
+                C[j, k] = mpmath.fsum(a * b for a, b in zip(dc[j], dc[k]))
+        b = mpmath.lu_solve(C, c)
+        exact = np.array([float(b[j]) for j in range(K)])
+        sv = mpmath.svd_r(C, compute_uv=False)
+        kappa = float(max(sv) / min(sv))
+    got = out["coef"][:K, 0]
+    err = float(np.abs(got - exact).max())
+    ratio = err / (kappa * float(np.abs(exact).max()))
+    assert kappa > 1e3, kappa
+    assert ratio <= 1e-14, f"|db|_inf / (kappa_2(C) |b|_inf) = {ratio:.3e} (kappa {kappa:.3e}, |db|_inf {err:.3e})"
 
 
 def test_time_series_form_transposes_the_units():

@@ -81,7 +81,7 @@ def check_groups(pq, f, r, mode, q=0, top=0.0, bottom=0.0, pitch=None):
         key = "ls_return"
     torch.cuda.synchronize()
     exp = X.groups(f, r, mode, q, top, bottom)
-    tag = f"mode{mode} q{q} top{top} bottom{bottom} {f.shape}"
+    tag = f"mode{mode} q{q} top{top} bottom{bottom} {f.shape} pitch={pitch}"
     same("labels " + tag, got["labels"].cpu().numpy(), exp["labels"])
     same("count " + tag, got["count"].cpu().numpy(), exp["count"])
     same("mean_return " + tag, got["mean_return"].cpu().numpy(), exp["mean_return"])

@@ -2,9 +2,12 @@
 quantile-sort / long-short / coverage / IC-statistics feature (C ABI declarations, Factor methods)."""
 import math
 import re
+from fractions import Fraction
 from pathlib import Path
 
 import numpy as np
+import pytest
+from scipy.stats import rankdata
 
 import xsec_ref as X
 
@@ -146,3 +149,32 @@ def test_factor_class_has_the_evaluation_methods():
     from polars_quant_amd import api
     for f in ("factor_quantiles", "factor_long_short", "factor_coverage", "ic_stats"):
         assert callable(getattr(api, f, None)), f
+
+
+@pytest.mark.parametrize("q", [3, 7, 13])
+def test_label_day_against_rankdata(q):
+    """label_day's quantile buckets = floor((2 rank - 1) Q / (2 n_valid)) with scipy's average ranks over the valid pairs, in exact
+    rationals, on tied and NULL-bearing days; every label is LABEL_OUT on a day with n_valid < Q"""
+    rng = np.random.default_rng(q)
+    for n, levels in ((40, 0), (40, 4), (257, 9), (600, 3), (q + 1, 2), (q, 0), (q - 1, 0)):
+        f = rng.integers(-levels, levels + 1, n).astype(np.float64) if levels else rng.standard_normal(n)
+        f[(f == 0.0) & (rng.random(n) < 0.5)] = -0.0
+        r = rng.standard_normal(n)
+        if n > 2 * q:
+            f[rng.random(n) < 0.1] = X.NULL
+            f[rng.random(n) < 0.05] = np.nan
+            f[rng.random(n) < 0.03] = np.inf
+            r[rng.random(n) < 0.05] = X.NULL
+            r[rng.random(n) < 0.03] = -np.inf
+        ok = np.isfinite(f) & np.isfinite(r)
+        nv = int(ok.sum())
+        lab = X.label_day(f, r, 0, q)
+        assert (lab[~ok] == OUT).all()
+        if nv < q:
+            assert (lab == OUT).all()
+            continue
+        rank = rankdata(f[ok], method="average")
+        exp = [math.floor(Fraction(int(2 * R - 1)) * q / (2 * nv)) for R in rank]
+        assert lab[ok].tolist() == exp, (n, levels)
+        if not levels:      # distinct values: every bucket is used
+            assert set(exp) == set(range(q)), n
