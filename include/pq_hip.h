@@ -494,6 +494,29 @@ pq_status pq_ts_regress(pq_ctx *, const pq_batch *, const double *const *factors
 /* correlation t-test: t = corr sqrt((n - 2) / (1 - corr corr)), p on n - 2; NULL where corr is NaN, n < 3 or 1 - corr^2 == 0 */
 pq_status pq_corr_t_test(pq_ctx *, const double *corr, const int32_t *n_valid, int64_t len, double *t_stat, double *p_value);
 
+/* ---- rank 3, continued: IC decay, sub-period and sub-group robustness tests, ic_decay / subsample_test / subgroup_test
+ * (README.md:1556-1565, :1607-1624; README-only, decision D-18 in DESIGN.md section 2).  factor / fwd_return: [n_series][stride]; the
+ * cross-section, the blocked sums (Pearson) and the average ranks (Rank-IC) are D-12's, so every daily IC is bit-identical to
+ * pq_factor_ic on the shifted or masked inputs.  method 0 Pearson IC, 1 Spearman Rank-IC (n_series <= 100000).  summary rows
+ * [PQ_IC_SUMMARY_COLS] = n_days, mean, std (ddof 1), t = mean / (std / sqrt(n_days)), p on n_days - 1 over the non-null days, as
+ * pq_xsec_regress's Fama-MacBeth summary.  Ragged batches and suite recording are refused.  Use the context workspace (Pearson ~24 bytes
+ * per (row, day, block of 256 symbols); Rank-IC ~8 bytes per cell, ~12 for sub-groups). */
+#define PQ_IC_DECAY_MAX_LAG 256
+#define PQ_IC_MAX_GROUPS 256
+#define PQ_IC_SUMMARY_COLS 5
+/* IC decay: row l - 1 (l = 1 .. max_lag) is the IC of the factor of day t against the return of day t + l - 1, NULL with n_valid 0 for
+ * t > len - l.  ic / n_valid: [max_lag][len]; summary: [max_lag][PQ_IC_SUMMARY_COLS] */
+pq_status pq_ic_decay(pq_ctx *, const pq_batch *, const double *factor, const double *fwd_return, int32_t method, int32_t max_lag,
+                      double *ic, int32_t *n_valid, double *summary);
+/* sub-group IC: row g is the IC over the day's cross-section restricted to the symbols whose code is g.  group: int32 codes, [n_series]
+ * (group_stride 0) or [n_series][group_stride] (group_stride >= len); codes outside [0, n_groups) are unclassified; n_groups in [1, 256].
+ * ic / n_valid: [n_groups][len]; summary: [n_groups][PQ_IC_SUMMARY_COLS] */
+pq_status pq_ic_subgroup(pq_ctx *, const pq_batch *, const double *factor, const double *fwd_return, const int32_t *group,
+                         int64_t group_stride, int32_t n_groups, int32_t method, double *ic, int32_t *n_valid, double *summary);
+/* sub-period summaries of a series x [len]: the periods are numpy.array_split(range(len), n_splits) (contiguous, the first len % n_splits
+ * one day longer), 1 <= n_splits <= len; summary: [n_splits][PQ_IC_SUMMARY_COLS] */
+pq_status pq_series_split_summary(pq_ctx *, const double *x, int64_t len, int32_t n_splits, double *summary);
+
 /* ---- suites: record many calls, replay them as a few chip-filling grids ----
  * One indicator over N symbols is only N/64 wavefronts -- far too few for 256 CUs -- but a DataFrame query asks
  * for many indicators at once (df.with_columns([...]) in the reference; Polars then calls the plugin once per

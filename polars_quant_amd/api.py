@@ -683,6 +683,105 @@ def corr_t_test(corr, n_valid):
                                    C.c_int64(c.numel()), vp(t.data_ptr()) if c.numel() else None, vp(p.data_ptr()) if c.numel() else None))
     return t, p
 
+
+IC_DECAY_MAX_LAG = 256    # PQ_IC_DECAY_MAX_LAG
+IC_MAX_GROUPS = 256       # PQ_IC_MAX_GROUPS
+IC_SUMMARY_COLS = 5       # PQ_IC_SUMMARY_COLS: n_days, mean, std, t_stat, p_value
+
+
+def _ic_pair_args(factor, fwd_return, method):
+    """argument checks of the D-18 calls that need no device -> (n, T)"""
+    if method not in (0, 1):
+        raise ValueError(f"method must be 0 (Pearson IC) or 1 (Spearman Rank-IC), not {method!r}")
+    fs, rs = _shape(factor), _shape(fwd_return)
+    if len(rs) != 2 or fs != rs:
+        raise ValueError(f"factor and fwd_return must both be [N, T] of one shape, not {fs} and {rs}")
+    return rs
+
+
+def _ic_rows(fn_name, factor, fwd_return, V, args):
+    """uploads factor / fwd_return onto one row pitch and runs a D-18 call that writes ic / n_valid [V, T] and summary [V, 5]"""
+    (f, r), b = _xsec_inputs([factor, fwd_return])
+    dev = f.device
+    n, T = f.shape
+    ic = torch.empty((V, T), dtype=torch.float64, device=dev)
+    nv = torch.empty((V, T), dtype=torch.int32, device=dev)
+    summ = torch.empty((V, IC_SUMMARY_COLS), dtype=torch.float64, device=dev)
+    vp = C.c_void_p
+    with torch.cuda.device(dev):
+        check(getattr(lib(), fn_name)(ctx(dev.index), C.byref(b), vp(f.data_ptr()) if n and T else None, vp(r.data_ptr()) if n and T else None,
+                                      *args(b, dev), vp(ic.data_ptr()) if T else None, vp(nv.data_ptr()) if T else None, vp(summ.data_ptr())))
+    return {"ic": ic, "n_valid": nv, "summary": summ}
+
+
+def ic_decay(factor, fwd_return, max_lag: int = 10, method: int = 0):
+    """D-18: IC of the factor of day t against the return of day t + l - 1, l = 1 .. max_lag (1 <= max_lag <= 256) -> dict of device
+    tensors: ic / n_valid [max_lag, T] (NULL / 0 for t > T - l) and summary [max_lag, 5] (n_days, mean, std, t_stat, p_value over the
+    non-null days, D-17's Fama-MacBeth rules).  method 0 Pearson IC, 1 Spearman Rank-IC"""
+    _ic_pair_args(factor, fwd_return, method)
+    if isinstance(max_lag, bool) or not isinstance(max_lag, (int, np.integer)) or not 1 <= max_lag <= IC_DECAY_MAX_LAG:
+        raise ValueError(f"max_lag must be an integer in 1..{IC_DECAY_MAX_LAG}, not {max_lag!r}")
+    L = int(max_lag)
+    return _ic_rows("pq_ic_decay", factor, fwd_return, L, lambda b, dev: (C.c_int32(method), C.c_int32(L)))
+
+
+def _group_codes(group, n, T):
+    """argument checks of ic_subgroup that need no device: integer codes [N] or [N, T] (negative = unclassified) -> (codes, G)"""
+    g = group if isinstance(group, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(group)))
+    if g.dtype.is_floating_point or g.dtype.is_complex or g.dtype == torch.bool:
+        raise ValueError("group must hold integer codes")
+    if tuple(g.shape) not in ((n,), (n, T)):
+        raise ValueError(f"group must be [N] or [N, T] with N = {n}, T = {T}, not {tuple(g.shape)}")
+    G = int(g.max()) + 1 if g.numel() else 1
+    if G > IC_MAX_GROUPS:
+        raise ValueError(f"group codes must be < {IC_MAX_GROUPS} (negative = unclassified), got a code {G - 1}")
+    return g, max(G, 1)
+
+
+def ic_subgroup(factor, fwd_return, group, method: int = 0):
+    """D-18: per-day IC within each group: group integer codes [N] or [N, T] (negative = unclassified, G = max code + 1 <= 256) -> dict
+    of device tensors: ic / n_valid [G, T] (row g = the day's cross-section restricted to code g) and summary [G, 5] (n_days, mean,
+    std, t_stat, p_value).  method 0 Pearson IC, 1 Spearman Rank-IC"""
+    n, T = _ic_pair_args(factor, fwd_return, method)
+    g, G = _group_codes(group, n, T)
+
+    def args(b, dev):
+        gd = g.to(device=dev, dtype=torch.int32)
+        if gd.dim() == 2:       # onto the factor's row pitch
+            gp = torch.empty((n, b.stride), dtype=torch.int32, device=dev)
+            gp[:, :T] = gd
+            gd, gs = gp, b.stride
+        else:
+            gd, gs = gd.contiguous(), 0
+        args.keep = gd          # kept alive until the call has returned
+        return (C.c_void_p(gd.data_ptr()) if gd.numel() else None, C.c_int64(gs), C.c_int32(G), C.c_int32(method))
+    return _ic_rows("pq_ic_subgroup", factor, fwd_return, G, args)
+
+
+def split_periods(T: int, n_splits: int):
+    """numpy.array_split(range(T), n_splits) as inclusive (start, end) day indices -> two int64 numpy arrays; 1 <= n_splits <= T"""
+    if isinstance(n_splits, bool) or not isinstance(n_splits, (int, np.integer)) or not 1 <= n_splits <= T:
+        raise ValueError(f"n_splits must be an integer in 1..T (T = {T}), not {n_splits!r}")
+    P = int(n_splits)
+    q, r = divmod(int(T), P)
+    p = np.arange(P, dtype=np.int64)
+    start = p * q + np.minimum(p, r)
+    return start, start + q + (p < r) - 1
+
+
+def series_split_summary(x, n_splits: int):
+    """D-18: summary rows of a series x [T] over numpy.array_split(range(T), n_splits) -> device tensor [n_splits, 5] (n_days, mean, std,
+    t_stat, p_value over each period's non-null days)"""
+    T = int(np.prod(_shape(x))) if len(_shape(x)) else 1
+    split_periods(T, n_splits)
+    t = _to_device(x)[0].contiguous().reshape(-1)
+    out = torch.empty((int(n_splits), IC_SUMMARY_COLS), dtype=torch.float64, device=t.device)
+    with torch.cuda.device(t.device):
+        check(lib().pq_series_split_summary(ctx(t.device.index), C.c_void_p(t.data_ptr()), C.c_int64(T), C.c_int32(int(n_splits)),
+                                            C.c_void_p(out.data_ptr())))
+    return out
+
+
 def _signal_call(fn_name, cols, *scalars):
     ts = [_to_device(c)[0].contiguous() for c in cols]
     dev = ts[0].device

@@ -1,7 +1,8 @@
 """Factor -- the evaluation half of the README's `Factor` class (README.md:1429-1430, :1480-1482, :1626-1634): per-day
 cross-sectional IC, Rank-IC and their rolling mean / information ratio (decision D-12, oracle/backtest.c), and quantile sorts,
 long-short legs, turnover, coverage and IC statistics (decision D-15), and the regressions and significance tests
-ic_test / factor_return / fama_macbeth / time_series_regression (decision D-17).  README-only in the reference.  Inputs are [N, T]
+ic_test / factor_return / fama_macbeth / time_series_regression (decision D-17), and the robustness tests ic_decay / subsample_test /
+subgroup_test (decision D-18).  README-only in the reference.  Inputs are [N, T]
 arrays (symbol-major, like every other column of this package): the factor and the forward return of every symbol on every day.
 `clean` is the README's factor cleaning step that comes before the evaluation (decision D-16).
 """
@@ -100,6 +101,51 @@ class Factor:
         r = _api.ts_regress(factors, returns)
         return {"coefficient": r["coef"], "t_stat": r["t_stat"], "p_value": r["p_value"], "r_squared": r["r_squared"],
                 "n_obs": r["n_obs"]}
+
+    # ---- D-18: IC decay, sub-period and sub-group robustness tests (README.md:1556-1565, :1607-1624)
+    def ic_decay(self, factor, next_return, max_lag=10, method="pearson"):
+        """-> {"lag", "ic", "std_ic", "t_stat", "p_value", "n_days"}: [max_lag] each, over the non-null days of the IC of the factor of
+        day t against the return of day t + lag - 1 (lag 1 = the ordinary IC), and "daily": {"ic", "n_valid": [max_lag, T]}"""
+        r = _api.ic_decay(factor, next_return, max_lag, _method(method))
+        s = r.pop("summary")
+        lag = torch.arange(1, s.shape[0] + 1, dtype=torch.int32, device=s.device)
+        return {"lag": lag, "ic": s[:, 1], "std_ic": s[:, 2], "t_stat": s[:, 3], "p_value": s[:, 4], "n_days": s[:, 0], "daily": r}
+
+    def subsample_test(self, factor, next_return, n_splits=3, method="pearson", dates=None):
+        """-> {"period", "start", "end", "mean_ic", "std_ic", "t_stat", "p_value", "n_days"}: [n_splits] each, the daily IC summarised
+        over numpy.array_split(range(T), n_splits) (start / end: inclusive day indices); with dates (length T), also "start_date" /
+        "end_date" lists"""
+        m = _method(method)
+        T = _api._ic_pair_args(factor, next_return, m)[1]
+        start, end = _api.split_periods(T, n_splits)
+        if dates is not None and len(dates) != T:
+            raise ValueError(f"dates must have one entry per day ({T}), not {len(dates)}")
+        ic, _ = _api.factor_ic(factor, next_return, m)
+        s = _api.series_split_summary(ic, n_splits)
+        p = torch.arange(len(start), dtype=torch.int64, device=s.device)   # the bounds of split_periods, built on the device (no copy)
+        q, rem = divmod(T, len(start))
+        first = p * q + p.clamp(max=rem)
+        out = {"period": p.to(torch.int32), "start": first, "end": first + (q - 1) + (p < rem), "mean_ic": s[:, 1], "std_ic": s[:, 2],
+               "t_stat": s[:, 3], "p_value": s[:, 4], "n_days": s[:, 0]}
+        if dates is not None:
+            out["start_date"] = [dates[int(i)] for i in start]
+            out["end_date"] = [dates[int(i)] for i in end]
+        return out
+
+    def subgroup_test(self, factor, next_return, group, method="pearson"):
+        """group: integer codes [N] or [N, T] (e.g. industries; negative = unclassified, at most 256 groups) -> {"group", "mean_ic",
+        "std_ic", "t_stat", "p_value", "n_days"}: [G] each (G = max code + 1), and "daily": {"ic", "n_valid": [G, T]}, the per-day IC
+        within each group"""
+        r = _api.ic_subgroup(factor, next_return, group, _method(method))
+        s = r.pop("summary")
+        g = torch.arange(s.shape[0], dtype=torch.int32, device=s.device)
+        return {"group": g, "mean_ic": s[:, 1], "std_ic": s[:, 2], "t_stat": s[:, 3], "p_value": s[:, 4], "n_days": s[:, 0], "daily": r}
+
+
+def _method(method):
+    if method not in IC_METHODS:
+        raise ValueError(f"method must be 'pearson' or 'spearman', not {method!r}")
+    return IC_METHODS[method]
 
 
 def clean(factor, winsorize=None, winsorize_n=None, neutralize_market_cap=False, cap=None, neutralize_industry=False, industry=None,
