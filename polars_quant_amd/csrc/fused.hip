@@ -100,7 +100,9 @@ static pq_status ht_all_time_split(pq_ctx *ctx, const pq_batch *b, const HtAll6O
     w.op = op6; w.real = real; w.b = *b; w.tile_rows = K; w.lds = (unsigned)seq_lds_bytes(op6);
     for (int k = 0; k < 3; k++) {
         w.out[k] = o3[k];
-        w.chk[k] = pq_ws_col(ctx, b, k); // (recording: a fresh column owned by the suite; only the check tiles of it are ever touched)
+        // (a fresh column owned by the suite, zeroed: only its check tiles are written, and the check kernel must never read memory
+        //  that nothing wrote)
+        w.chk[k] = reinterpret_cast<double *>(rec_alloc_zero(ctx, batch_rows(b) * sizeof(double)));
         if (!w.chk[k]) { pq_set_error("out of device memory for a check column"); return PQ_ERR_NOMEM; }
     }
     const size_t tiles = (size_t)((b->n_series + SEQ_BLOCK - 1) / SEQ_BLOCK);

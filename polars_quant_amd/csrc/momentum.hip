@@ -142,6 +142,7 @@ pq_status pq_adxr_chain(pq_ctx *ctx, const pq_batch *b, const double *h, const d
     return launch_row(ctx, b, op, InCols<1>{{adx}}, OutColsT<AdxrOp, double>{{out}});
 }
 pq_status pq_adxr_from_adx(pq_ctx *ctx, const pq_batch *b, const double *adx, int64_t p, double *out) { // the second half of pq_adxr_chain
+    CHK("pq_adxr_from_adx", adx && out);
     AdxrOp op{}; op.p = p;
     return launch_row(ctx, b, op, InCols<1>{{adx}}, OutColsT<AdxrOp, double>{{out}});
 }

@@ -474,7 +474,8 @@ static inline bool wt_try(pq_ctx *ctx, const pq_batch *b, const WtOp &wop, const
         if (hipStreamSynchronize(ctx->stream) != hipSuccess) { pq_set_error("hipStreamSynchronize failed"); *st = PQ_ERR_HIP; return true; }
         if (ctx->wt_gate) (void)hipFree(ctx->wt_gate);
         ctx->wt_gate = nullptr; ctx->wt_gate_tiles = 0;
-        if (hipMalloc((void **)&ctx->wt_gate, tiles * sizeof(unsigned)) != hipSuccess || hipMemset(ctx->wt_gate, 0, tiles * sizeof(unsigned)) != hipSuccess) {
+        if (hipMalloc((void **)&ctx->wt_gate, tiles * sizeof(unsigned)) != hipSuccess ||
+            hipMemsetAsync(ctx->wt_gate, 0, tiles * sizeof(unsigned), ctx->stream) != hipSuccess) { // (the stream the gated kernels run on)
             pq_set_error("out of device memory for a gate"); *st = PQ_ERR_NOMEM; return true;
         }
         ctx->wt_gate_tiles = tiles;

@@ -119,7 +119,9 @@ pq_status ctx_gate(pq_ctx *ctx, size_t tiles, unsigned **gate) {
         PQ_HIP_TRY(hipStreamSynchronize(ctx->stream));
         if (ctx->wt_gate) (void)hipFree(ctx->wt_gate);
         ctx->wt_gate = nullptr; ctx->wt_gate_tiles = 0;
-        if (hipMalloc((void **)&ctx->wt_gate, tiles * sizeof(unsigned)) != hipSuccess || hipMemset(ctx->wt_gate, 0, tiles * sizeof(unsigned)) != hipSuccess) {
+        // (zeroed on the context's stream, where the gated kernels run: a NULL-stream memset is not ordered against a non-blocking one)
+        if (hipMalloc((void **)&ctx->wt_gate, tiles * sizeof(unsigned)) != hipSuccess ||
+            hipMemsetAsync(ctx->wt_gate, 0, tiles * sizeof(unsigned), ctx->stream) != hipSuccess) {
             pq_set_error("out of device memory for a gate");
             return PQ_ERR_NOMEM;
         }

@@ -94,13 +94,15 @@ struct pq_suite {
     Recorder rec;
 };
 
-// the tiled body of one job of the light kernel; an op that may be split in time (pq_dev.h TsOk) walks the row range of its job
-template <class OP, bool TS = TsOk<OP>::value>
+// the tiled body of one job of a tiled kernel (UNAL: its 8-byte form); an op that may be split in time (pq_dev.h TsOk) walks the row
+// range of its job -- in every tiled kernel: one 8-byte job in the class moves the whole grid, time-split jobs included, to the 8-byte
+// form (ts_row0 is a multiple of 16 rows, so a chunk's columns keep the alignment of the series)
+template <class OP, bool UNAL = false, bool TS = TsOk<OP>::value>
 struct TiledJob {
-    __device__ static __forceinline__ void run(OP &op, const SeqJob &job, const Dims &d, int64_t s0, unsigned char *lds) { run_seq_lds<OP, false>(op, job.in, job.out, d, s0, lds); }
+    __device__ static __forceinline__ void run(OP &op, const SeqJob &job, const Dims &d, int64_t s0, unsigned char *lds) { run_seq_lds<OP, UNAL>(op, job.in, job.out, d, s0, lds); }
 };
-template <class OP>
-struct TiledJob<OP, true> {
+template <class OP, bool UNAL>
+struct TiledJob<OP, UNAL, true> {
     __device__ static __forceinline__ void run(OP &op, const SeqJob &job, const Dims &d, int64_t s0, unsigned char *lds) {
         Dims dj = d;
         if (job.ts_len) dj.len = job.ts_len;
@@ -111,7 +113,7 @@ struct TiledJob<OP, true> {
 #pragma unroll
         for (int k = 0; k < OP::NOUT; k++) outj[k] = job.out[k] + job.ts_row0;
         op.ts_shift(job.ts_row0);
-        run_seq_lds<OP, false>(op, inj, outj, dj, s0, lds, job.ts_skip);
+        run_seq_lds<OP, UNAL>(op, inj, outj, dj, s0, lds, job.ts_skip);
     }
 };
 template <int V>
@@ -137,8 +139,7 @@ __device__ __forceinline__ void seq_jobs_body(const SeqJob *jobs, Dims d, unsign
         __builtin_memcpy(&op, job.op, sizeof(OP));                                                                   \
         if constexpr (V == 2) run_seq(op, job.in, job.out, d, s);                                                    \
         else if constexpr (V == 0) TiledJob<OP>::run(op, job, d, s0, jobs_lds);                                      \
-        else                                                                                                         \
-            run_seq_lds<OP, V == 3>(op, job.in, job.out, d, s0, jobs_lds); \
+        else TiledJob<OP, V == 3>::run(op, job, d, s0, jobs_lds);                                                    \
     } break;
     // the two lists must agree with the ops' HEAVY trait (which is what the class assignment in suite_finalize looks at)
 #define XL(OP) static_assert(!IsHeavy<OP>::value, "light list holds an op marked HEAVY"); X(OP)
@@ -1005,7 +1006,9 @@ static void suite_free(pq_ctx *ctx, Recorder &r) {
 void *rec_alloc_zero(pq_ctx *ctx, size_t bytes) {
     void *p = nullptr;
     if (hipMalloc(&p, bytes ? bytes : 4) != hipSuccess) return nullptr;
-    if (hipMemset(p, 0, bytes ? bytes : 4) != hipSuccess) { (void)hipFree(p); return nullptr; }
+    // (on the context's stream: the kernels that set and consume these flags run there, and it may be a non-blocking stream that
+    //  a memset on the NULL stream does not order against)
+    if (hipMemsetAsync(p, 0, bytes ? bytes : 4, ctx->stream) != hipSuccess) { (void)hipFree(p); return nullptr; }
     ctx->rec->scratch.push_back(p);
     return p;
 }

@@ -197,9 +197,29 @@ class Suite:
     house = _house
 
     def refresh_inputs(self, ohlcv: dict) -> None:
-        """after the caller changed input columns that record() had to re-house: copy them again (same buffers, no re-recording).
-        run(ohlcv) does this itself; run() without tensors replays on the copies as they are."""
-        self._house({k: t for k, t in ohlcv.items() if k in self._housed})
+        """bind the caller's current data to the recording for the next replays (no re-recording): a column that record() re-housed
+        is copied into the suite's buffer (current stream) whatever the layout of the tensor passed; a column that the recording reads
+        in place accepts only the recorded tensor itself (same data_ptr, shape and strides) -- its data are read where they are.  Any
+        other tensor for such a column, or a key the recording does not read, raises ValueError: re-record, or write into the recorded
+        buffer.  run(ohlcv) does this itself."""
+        rec = getattr(self, "_ohlcv", None) or {}
+        unknown = sorted(set(ohlcv) - set(rec))
+        if unknown:
+            raise ValueError(f"input columns {unknown} are not read by the recorded step (it reads {sorted(rec)})")
+        copies = []   # (every column is checked before any is copied: a refused call changes nothing)
+        for k, t in ohlcv.items():
+            r, buf = rec[k], self._housed.get(k)
+            if buf is not None and buf.data_ptr() == r.data_ptr():      # the recording reads the suite's copy of this column
+                if not isinstance(t, torch.Tensor) or tuple(t.shape) != (self.n, self.T):
+                    raise ValueError(f"input column `{k}`: expected a [{self.n}, {self.T}] tensor, got {getattr(t, 'shape', type(t))}")
+                copies.append((r, t))
+            elif not (isinstance(t, torch.Tensor) and t.data_ptr() == r.data_ptr() and t.shape == r.shape and t.stride() == r.stride()
+                      and t.dtype == r.dtype and t.device == r.device):
+                raise ValueError(f"input column `{k}` is read in place by the recorded step, and this is not the recorded tensor: "
+                                 f"re-record (Suite.record) with the new tensor, or write the new data into the recorded buffer")
+        for r, t in copies:
+            r.copy_(t)
+        self._stale_warned = False
 
     def record(self, ohlcv: dict, tasks=None, summaries=None) -> None:
         """record the step once (pq_suite_begin/end): the sequential jobs of all functions become one grid per phase.
@@ -207,6 +227,7 @@ class Suite:
         summaries[k] (every other output column is shared) -- run(slot=k) then replays recording k, so that a multi-GPU caller can
         keep the exchange of one table in flight while the next step fills the other (distributed.OverlappedGather)."""
         self.close()
+        self._housed, self._stale_warned = {}, False   # copies of an earlier recording are not this one's
         L, h = lib(), ctx(self.dev.index)
         ohlcv = self._house(ohlcv)
         self._ohlcv = ohlcv  # keep the inputs alive: the suite holds raw device pointers
@@ -263,6 +284,7 @@ class Suite:
         if slow:
             raise ValueError(f"record_staged: columns {slow} are not on the suite's row pitch ({self.stride} elements): pass suite.house(columns)")
         self.close()
+        self._housed, self._stale_warned = {}, False   # every column is read in place: no copies of an earlier recording stay
         L, h = lib(), ctx(self.dev.index)
         self._ohlcv = ohlcv
         stages, have, left = [], set(), list(self.tasks(fused=True))
@@ -332,20 +354,21 @@ class Suite:
 
     def run(self, ohlcv: dict | None = None, slot: int = 0) -> None:
         """one step: every indicator + all 61 patterns + the MACD-cross backtest, enqueued on the current stream
-        (slot: which of the recordings of record(summaries=[...]) to replay)"""
+        (slot: which of the recordings of record(summaries=[...]) to replay).  ohlcv: the data of this step, bound as refresh_inputs()
+        binds them -- copied into the suite's buffer for a re-housed column, the recorded tensor itself for a column read in place
+        (any other tensor raises ValueError); without it the step replays on the recorded buffers as they are."""
         if getattr(self, "_suite", None) is None:
             self.record(ohlcv)
-        elif self._housed:
-            # the recording reads suite-owned copies of the columns that were handed over at a slow row pitch: tensors passed here are
-            # copied into them again (current stream); without tensors the step replays on the copies as they are -- said once
-            if ohlcv is not None:
-                self.refresh_inputs(ohlcv)
-            elif not getattr(self, "_stale_warned", True):
-                import warnings
-                from .api import PqLayoutWarning
-                self._stale_warned = True
-                warnings.warn(f"Suite.run(): columns {sorted(self._housed)} were re-housed at record time; this replay reads those copies, not the "
-                              f"caller's tensors -- pass the tensors to run() or call refresh_inputs() after changing them", PqLayoutWarning, stacklevel=2)
+        elif ohlcv is not None:
+            self.refresh_inputs(ohlcv)
+        elif self._housed and not getattr(self, "_stale_warned", True):
+            # the recording reads suite-owned copies of the columns that were handed over at a slow row pitch: a replay without tensors
+            # reads those copies as they are -- said once per recording
+            import warnings
+            from .api import PqLayoutWarning
+            self._stale_warned = True
+            warnings.warn(f"Suite.run(): columns {sorted(self._housed)} were re-housed at record time; this replay reads those copies, not the "
+                          f"caller's tensors -- pass the tensors to run() or call refresh_inputs() after changing them", PqLayoutWarning, stacklevel=2)
         if not Suite._stream_warned and torch.cuda.current_stream(self.dev).cuda_stream != 0:
             # (a replay needs four hardware queues on four compute pipes: the NULL stream + the three side streams of the context are a
             #  process's first four; a created stream shifts them and two chains share a pipe -- DESIGN.md section 6, INTEGRATION.md)
