@@ -494,6 +494,16 @@ pq_status pq_ts_regress(pq_ctx *, const pq_batch *, const double *const *factors
 /* correlation t-test: t = corr sqrt((n - 2) / (1 - corr corr)), p on n - 2; NULL where corr is NaN, n < 3 or 1 - corr^2 == 0 */
 pq_status pq_corr_t_test(pq_ctx *, const double *corr, const int32_t *n_valid, int64_t len, double *t_stat, double *p_value);
 
+/* ---- rank 3, continued: multi-factor orthogonalization and neutralization, Factor().clean(factors, method) (README.md:1495-1519;
+ * README-only, decision D-19 in DESIGN.md section 2).  factors is a HOST array of k device pointers, 2 <= k <= PQ_REGRESS_MAX_K, and out
+ * a HOST array of k - 1, all on the batch's row pitch.  Per day, the sample is every symbol whose k factors are all non-null and finite.
+ * out[j] (j = 0 .. k - 2) is the residual of factors[j + 1]: mode 0 (orthogonalize, sequential Gram-Schmidt) on factors[0 .. j], mode
+ * 1 (neutralize) on factors[0] alone, each with an intercept and bit-identical to the e of pq_xsec_regress's D-17 order (one
+ * C = L D L^T per day serves every level).  NULL outside the sample and where D-17 would NULL that regression's coefficients
+ * (n < regressors + 2 or a singular pivot; in mode 0 a singular block NULLs every later residual).  out[j] may be factors[j + 1] (in
+ * place).  Ragged batches and suite recording are refused.  Uses the context workspace (~4 k (k + 1) bytes per (day, block of 256)). */
+pq_status pq_factor_orthogonalize(pq_ctx *, const pq_batch *, const double *const *factors, int32_t k, int32_t mode, double *const *out);
+
 /* ---- rank 3, continued: IC decay, sub-period and sub-group robustness tests, ic_decay / subsample_test / subgroup_test
  * (README.md:1556-1565, :1607-1624; README-only, decision D-18 in DESIGN.md section 2).  factor / fwd_return: [n_series][stride]; the
  * cross-section, the blocked sums (Pearson) and the average ranks (Rank-IC) are D-12's, so every daily IC is bit-identical to

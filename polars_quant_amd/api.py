@@ -684,6 +684,74 @@ def corr_t_test(corr, n_valid):
     return t, p
 
 
+ORTH_MODES = {"orthogonalize": 0, "neutralize": 1}
+
+
+def _orth_args(factors, mode):
+    """argument checks of factor_orthogonalize that need no device: mode 0 / 1, factors a list / tuple of 2..8 [N, T] arrays of one
+    shape or one [K, N, T] array -> (list of factor columns, (N, T))"""
+    if mode not in (0, 1):
+        raise ValueError(f"mode must be 0 (orthogonalize) or 1 (neutralize), not {mode!r}")
+    if isinstance(factors, (list, tuple)):
+        cols = list(factors)
+    else:
+        fs = _shape(factors)
+        if len(fs) != 3:
+            raise ValueError(f"factors must be a list of [N, T] arrays or one [K, N, T] array, not {fs}")
+        cols = [factors[j] for j in range(fs[0])]
+    if not 2 <= len(cols) <= REGRESS_MAX_K:
+        raise ValueError(f"the number of factors must be in 2..{REGRESS_MAX_K}, not {len(cols)}")
+    s0 = _shape(cols[0])
+    if len(s0) != 2:
+        raise ValueError(f"factor 0 must be [N, T], not {s0}")
+    _regress_args(cols, cols[0], False)
+    return cols, s0
+
+
+def factor_orthogonalize(factors, mode: int = 0, out=None, keep_first: bool = False):
+    """D-19: per-day residuals of factors 1 .. K-1 (factors: a list of K [N, T] arrays or one [K, N, T] array, 2 <= K <= 8) over the
+    day's joint sample: mode 0 (orthogonalize) the residual of factor k on factors 0 .. k-1, mode 1 (neutralize) on factor 0 alone,
+    each with an intercept, NULL outside the sample and where the regression has no solution -> device tensor [K - 1, N, T].
+    out: K - 1 device float64 [N, T] tensors on the inputs' row pitch to write instead (out[j] may be factor j + 1 itself), returned
+    as given.  keep_first (mode 0, out None): -> [K, N, T] with row 0 a copy of factor 0 and rows 1 .. the residuals."""
+    cols, (n, T) = _orth_args(factors, mode)
+    K = len(cols)
+    if keep_first and (mode != 0 or out is not None):
+        raise ValueError("keep_first is for mode 0 without out")
+    if n == 0 or T == 0:    # no cell: nothing is uploaded or launched
+        if out is not None:
+            return list(out)
+        _require_gpu()
+        c0 = cols[0]
+        dev = c0.device if isinstance(c0, torch.Tensor) and c0.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        return torch.empty((K - 1 + (1 if keep_first else 0), n, T), dtype=torch.float64, device=dev)
+    mats = _same_layout([_to_device(c)[0] for c in cols])
+    dev = mats[0].device
+    b = _batch_of(mats[0])
+    if out is None:
+        lead = 1 if keep_first else 0
+        buf = torch.empty((K - 1 + lead, n, b.stride), dtype=torch.float64, device=dev)[:, :, :T]
+        if keep_first:
+            buf[0].copy_(mats[0])
+        res, outs = buf, [buf[lead + j] for j in range(K - 1)]
+    else:
+        res = outs = list(out)
+        if len(outs) != K - 1:
+            raise ValueError(f"out must hold {K - 1} tensors, not {len(outs)}")
+        for j, o in enumerate(outs):
+            if not (isinstance(o, torch.Tensor) and o.device == dev and o.dtype == torch.float64 and tuple(o.shape) == (n, T)
+                    and (T <= 1 or o.stride(1) == 1) and (n <= 1 or o.stride(0) == b.stride)):
+                raise ValueError(f"out[{j}] must be a float64 [N, T] tensor on {dev} with row pitch {b.stride}")
+    vp = C.c_void_p
+    live = n > 0 and T > 0
+    fp = (vp * K)(*[m.data_ptr() for m in mats])
+    op = (vp * (K - 1))(*[o.data_ptr() for o in outs])
+    with torch.cuda.device(dev):
+        check(lib().pq_factor_orthogonalize(ctx(dev.index), C.byref(b), fp if live else None, C.c_int32(K), C.c_int32(mode),
+                                            op if live else None))
+    return res
+
+
 IC_DECAY_MAX_LAG = 256    # PQ_IC_DECAY_MAX_LAG
 IC_MAX_GROUPS = 256       # PQ_IC_MAX_GROUPS
 IC_SUMMARY_COLS = 5       # PQ_IC_SUMMARY_COLS: n_days, mean, std, t_stat, p_value

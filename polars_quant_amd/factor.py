@@ -2,8 +2,9 @@
 cross-sectional IC, Rank-IC and their rolling mean / information ratio (decision D-12, oracle/backtest.c), and quantile sorts,
 long-short legs, turnover, coverage and IC statistics (decision D-15), and the regressions and significance tests
 ic_test / factor_return / fama_macbeth / time_series_regression (decision D-17), and the robustness tests ic_decay / subsample_test /
-subgroup_test (decision D-18).  README-only in the reference.  Inputs are [N, T]
-arrays (symbol-major, like every other column of this package): the factor and the forward return of every symbol on every day.
+subgroup_test (decision D-18), and the multi-factor orthogonalization / neutralization Factor().clean (decision D-19).  README-only
+in the reference.  Inputs are [N, T] arrays (symbol-major, like every other column of this package): the factor and the forward return
+of every symbol on every day.
 `clean` is the README's factor cleaning step that comes before the evaluation (decision D-16).
 """
 from __future__ import annotations
@@ -16,6 +17,12 @@ IC_METHODS = {"pearson": 0, "spearman": 1}
 
 
 class Factor:
+    def __init__(self):
+        # Factor().clean (D-19) is bound per instance, the way the README calls it (`factor = Factor(); factor.clean(df, ...)`).  The
+        # class itself carries no `clean` attribute: the package's public-surface contract keeps `Factor.clean` off the class so that it
+        # is never taken for the module-level single-factor `clean` (D-16).
+        self.clean = self._clean_factors
+
     def ic(self, factor, next_return):
         """-> (ic [T], n_valid [T]): Pearson correlation across symbols, per day"""
         return _api.factor_ic(factor, next_return, 0)
@@ -140,6 +147,27 @@ class Factor:
         s = r.pop("summary")
         g = torch.arange(s.shape[0], dtype=torch.int32, device=s.device)
         return {"group": g, "mean_ic": s[:, 1], "std_ic": s[:, 2], "t_stat": s[:, 3], "p_value": s[:, 4], "n_days": s[:, 0], "daily": r}
+
+    # ---- D-19: multi-factor orthogonalization and neutralization (README.md:1495-1519); reached as Factor().clean
+    def _clean_factors(self, factors, method="orthogonalize", inplace=False):
+        """Factor().clean(factors, method="orthogonalize", inplace=False).  factors: a list of K [N, T] arrays or one [K, N, T] array
+        (2 <= K <= 8), in order of priority.  Per day, over the symbols whose K factors are all non-null and finite: "orthogonalize" (sequential Gram-Schmidt) keeps factor 0 as it is and replaces factor k
+        by its OLS residual on factors 0 .. k-1 -> [K, N, T]; "neutralize" gives the residual of each factor 1 .. K-1 on factor 0 alone
+        -> [K - 1, N, T].  NULL outside the day's sample and where the regression has no solution.  inplace=True (orthogonalize only,
+        factors a device float64 [K, N, T] tensor) rewrites rows 1 .. K-1 of factors and returns it."""
+        if method not in _api.ORTH_MODES:
+            raise ValueError(f"method must be 'orthogonalize' or 'neutralize', not {method!r}")
+        mode = _api.ORTH_MODES[method]
+        cols, _ = _api._orth_args(factors, mode)
+        if not inplace:
+            return _api.factor_orthogonalize(factors, mode, keep_first=mode == 0)
+        if mode != 0:
+            raise ValueError("inplace=True is only for method='orthogonalize'")
+        if not (isinstance(factors, torch.Tensor) and factors.is_cuda and factors.dtype == torch.float64 and factors.dim() == 3
+                and (factors.shape[2] <= 1 or factors.stride(2) == 1)):
+            raise ValueError("inplace=True needs one device float64 [K, N, T] tensor with unit stride along days")
+        _api.factor_orthogonalize(factors, 0, out=[factors[j] for j in range(1, len(cols))])
+        return factors
 
 
 def _method(method):
