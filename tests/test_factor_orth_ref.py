@@ -34,7 +34,7 @@ def test_exact_residuals_and_singular_block():
     assert not O.isnull(n[1, :, 1]).any()              # neutralize never regresses on f_1
 
 
-@pytest.mark.parametrize("K", [2, 3, 5])
+@pytest.mark.parametrize("K", range(2, 9))
 def test_sample_size_thresholds(K):
     """level k needs n >= k + 2: at n = K + 1 every level is solved, at n = K the last one is NULL, at n = K + 2 all again"""
     rng = np.random.default_rng(K)
@@ -65,7 +65,7 @@ def random_factors(K, N, T, seed, holes=True):
     return F
 
 
-@pytest.mark.parametrize("K", [2, 3, 5, 8])
+@pytest.mark.parametrize("K", range(2, 9))
 def test_against_lstsq_and_orthogonal(K):
     F = random_factors(K, 300, 6, 11 * K)
     e = O.orthogonalize(F)
@@ -86,6 +86,64 @@ def test_against_lstsq_and_orthogonal(K):
         nrm = np.sqrt(np.diag(G))
         off = np.abs(G - np.diag(np.diag(G))) / np.outer(nrm, nrm)
         assert off.max() <= 1e-12
+
+
+def level_table(K, n, seed):
+    """[K, n, 2K] factors on which the number of solved levels takes every value: day m - 1 (m = 1 .. K-1) has
+    f_m = 2 f_{m-1} + 3, so the pivot of level m + 1 is rounding noise: levels 1 .. m are solved (level m with a residual of rounding
+    noise) and the rest are NULL; day K + m - 2 (m = 1 .. K-1) has exactly m + 2 members, so level k <= m has its k + 2 members;
+    on day 2K - 2 every value is scaled by 1e160, C[0][0] overflows and pivot 0 already fails (inf > 1e-12 inf is false); on day
+    2K - 1 only f_1 is scaled by 1e160: D_0 is healthy and D_1 = inf - inf is NaN, which counts as singular, so level 1 alone is solved"""
+    rng = np.random.default_rng(seed)
+    F = rng.standard_normal((K, n, 2 * K))
+    for k in range(1, K):
+        F[k] += 0.5 * F[k - 1]
+    for m in range(1, K):
+        F[m, :, m - 1] = 2.0 * F[m - 1, :, m - 1] + 3.0
+        F[0, m + 2:, K + m - 2] = O.NULL
+    F[:, :, 2 * K - 2] *= 1e160
+    F[1, :, 2 * K - 1] *= 1e160
+    return F
+
+
+def solved_levels(e):
+    """residuals [K - 1, n, T] -> per day the number of levels with a residual, after asserting that they are levels 1 .. that number"""
+    has = ~O.isnull(e).all(axis=1)                     # [K - 1, T]
+    cnt = has.sum(axis=0)
+    assert (has == (np.arange(1, e.shape[0] + 1)[:, None] <= cnt[None, :])).all(), "the solved levels are not a prefix"
+    return cnt
+
+
+def level_table_counts(K):
+    return list(range(1, K)) + list(range(1, K)) + [0, 1]
+
+
+@pytest.mark.parametrize("n", [40, 300])
+@pytest.mark.parametrize("K", range(2, 9))
+def test_every_solved_level_count(K, n):
+    """level_table: the restatement solves exactly 1 .. K-1 levels on the collinear days, 1 .. K-1 on the size days, none on the
+    overflow day and one on the NaN-pivot day, always a prefix; the solved residuals agree with lstsq on the size days, and the
+    level-m residual of a collinear day is rounding noise"""
+    F = level_table(K, n, 17 * K + n)
+    e = O.orthogonalize(F)
+    assert solved_levels(e).tolist() == level_table_counts(K)
+    mem = O.joint(F)
+    assert mem[:, :K - 1].all() and mem[:, 2 * K - 2:].all() and mem[:, K - 1:2 * K - 2].sum(axis=0).tolist() == list(range(3, K + 2))
+    for m in range(1, K):
+        assert np.abs(e[m - 1, :, m - 1]).max() <= 1e-12 * np.abs(F[m, :, m - 1]).max()
+        t = K + m - 2
+        sel = mem[:, t]
+        for k in range(1, m + 1):
+            X = np.column_stack([np.ones(m + 2)] + [F[j, sel, t] for j in range(k)])
+            y = F[k, sel, t]
+            exp = y - X @ np.linalg.lstsq(X, y, rcond=None)[0]
+            assert np.abs(e[k - 1, sel, t] - exp).max() <= 1e-9 * (np.abs(y).max() + 1.0), (K, m, k)
+    with np.errstate(all="ignore"):                       # the last day: pivot 0 is healthy, pivot 1 is inf - inf
+        d0, d1 = (F[j, :, 2 * K - 1] - F[j, :, 2 * K - 1].mean() for j in (0, 1))
+        c00, c10, c11 = (d0 * d0).sum(), (d1 * d0).sum(), (d1 * d1).sum()
+        assert 0.0 < c00 < np.inf and np.isfinite(c10) and c11 == np.inf and np.isnan(c11 - c10 * (c10 / c00))
+    nz = O.orthogonalize(F, "neutralize")                 # one regressor: solved on every day but the overflow day
+    assert solved_levels(nz).tolist() == [K - 1] * (2 * K - 2) + [0, K - 1]
 
 
 @pytest.mark.parametrize("K", [2, 4])
