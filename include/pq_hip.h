@@ -527,6 +527,29 @@ pq_status pq_ic_subgroup(pq_ctx *, const pq_batch *, const double *factor, const
  * one day longer), 1 <= n_splits <= len; summary: [n_splits][PQ_IC_SUMMARY_COLS] */
 pq_status pq_series_split_summary(pq_ctx *, const double *x, int64_t len, int32_t n_splits, double *summary);
 
+/* ---- rank 3, continued: the general factor calculations, Factor.rank / normalize / weighted / ratio / diff (README.md:1416-1421,
+ * :1438-1470; README-only, decision D-20 in DESIGN.md section 2).  Every column is f64 [n_series][stride] on the batch's row pitch, and
+ * so is out, which may be one of the inputs (in place).  "Valid" is non-null and finite.  Ragged batches and suite recording are refused;
+ * n_series = 0 or len = 0 launches nothing.  Normalize's zscore is pq_factor_clean(winsorize 0, standardize 1). */
+/* Factor.rank and normalize("quantile") (README.md:1420-1421, :1456-1460).  Per day over the n valid symbols: a symbol whose key (-0 ties
+ * with +0) occupies the tie run [a, b) of the ascending sort has rank = ((a + 1) + b) / 2; descending: n + 1 - rank.  mode 0: that rank,
+ * 1: rank / n (pct), 2: (rank - 0.5) / n, the mid-rank position in (0, 1) (descending must be 0).  NULL outside the sample.
+ * n_series <= 100000; above 16384, n_series * len < 2^32.  Uses the context workspace (~8 bytes per cell, ~16 above 16384 series). */
+pq_status pq_factor_rank(pq_ctx *, const pq_batch *, const double *factor, int32_t mode, int32_t descending, double *out);
+/* normalize("minmax") (README.md:1420, :1454-1456): (x - min) / (max - min) over the day's valid symbols, -0 read as +0; the whole day
+ * NULL where max == min.  Uses the context workspace (~16 bytes per (day, block of 256 symbols)). */
+pq_status pq_factor_minmax(pq_ctx *, const pq_batch *, const double *factor, double *out);
+/* Factor.weighted (README.md:1419, :1449-1451): (x w) / W per day over the symbols whose factor and weight are both valid and (group not
+ * NULL) whose code lies in [0, n_groups); W = the sum of w over the day's sample, or over the symbol's group on that day, in D-12's
+ * blocked order (blocks of 256 symbols, ascending from 0.0, block sums in ascending order).  group: int32 codes, [n_series]
+ * (group_stride 0) or [n_series][group_stride] (group_stride >= len); n_groups in [1, 256].  NULL outside the sample and where W == 0.
+ * Uses the context workspace (~8 * max(n_groups, 1) bytes per (day, block of 256 symbols)). */
+pq_status pq_factor_weighted(pq_ctx *, const pq_batch *, const double *factor, const double *weight, const int32_t *group,
+                             int64_t group_stride, int32_t n_groups, double *out);
+/* Factor.ratio / diff (README.md:1417-1418, :1441-1447): op 0: a / b, 1: a - b, 2: (a - b) / |b|.  NULL where either input is NULL,
+ * otherwise plain IEEE-754 (a zero divisor gives inf or NaN). */
+pq_status pq_factor_binary(pq_ctx *, const pq_batch *, const double *a, const double *b, int32_t op, double *out);
+
 /* ---- suites: record many calls, replay them as a few chip-filling grids ----
  * One indicator over N symbols is only N/64 wavefronts -- far too few for 256 CUs -- but a DataFrame query asks
  * for many indicators at once (df.with_columns([...]) in the reference; Polars then calls the plugin once per

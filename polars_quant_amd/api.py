@@ -826,6 +826,94 @@ def ic_subgroup(factor, fwd_return, group, method: int = 0):
     return _ic_rows("pq_ic_subgroup", factor, fwd_return, G, args)
 
 
+RANK_MODES = {"rank": 0, "pct": 1, "quantile": 2}              # pq_factor_rank's mode codes
+NORMALIZE_METHODS = ("zscore", "minmax", "quantile")
+BINARY_OPS = {"ratio": 0, "diff": 1, "reldiff": 2}             # pq_factor_binary's op codes
+
+
+def _build_shapes(names, cols):
+    """argument check of the D-20 calls that needs no device: every column is [N, T] of one shape -> (N, T)"""
+    s0 = _shape(cols[0])
+    if len(s0) != 2:
+        raise ValueError(f"{names[0]} must be [N, T], not {s0}")
+    for nm, c in zip(names[1:], cols[1:]):
+        if _shape(c) != s0:
+            raise ValueError(f"{nm} must have the shape of {names[0]} {s0}, not {_shape(c)}")
+    return s0
+
+
+def _build_call(fn_name, cols, make_args):
+    """uploads the columns onto one row pitch and runs a D-20 call fn(ctx, batch, *columns, *make_args(batch, device), out) ->
+    the device f64 [N, T] output at the inputs' pitch"""
+    ts, b = _xsec_inputs(cols)
+    dev = ts[0].device
+    n, T = ts[0].shape
+    out = torch.empty((n, b.stride), dtype=torch.float64, device=dev)
+    vp = C.c_void_p
+    live = n > 0 and T > 0
+    with torch.cuda.device(dev):
+        check(getattr(lib(), fn_name)(ctx(dev.index), C.byref(b), *[vp(t.data_ptr()) if live else None for t in ts], *make_args(b, dev),
+                                      vp(out.data_ptr()) if live else None))
+    return out[:, :T]
+
+
+def factor_rank(factor, mode: int = 0, descending: bool = False):
+    """D-20: per-day average rank of an [N, T] factor over its non-null finite symbols (-0 ties with +0; ties share the mean of their
+    positions) -> device tensor [N, T], NULL outside the day's sample.  mode 0: rank in 1 .. n, 1: rank / n, 2: (rank - 0.5) / n (the
+    mid-rank position, ascending only); descending: n + 1 - rank."""
+    if mode not in (0, 1, 2):
+        raise ValueError(f"mode must be 0 (rank), 1 (pct) or 2 (mid-rank position), not {mode!r}")
+    if mode == 2 and descending:
+        raise ValueError("mode 2 (mid-rank position) is ascending only")
+    _build_shapes(("factor",), (factor,))
+    return _build_call("pq_factor_rank", [factor], lambda b, dev: (C.c_int32(mode), C.c_int32(1 if descending else 0)))
+
+
+def factor_normalize(factor, method: str = "zscore"):
+    """D-20: per-day normalization of an [N, T] factor over its non-null finite symbols -> device tensor [N, T].  "zscore": D-16's
+    standardize (factor_clean(standardize=True) itself); "minmax": (x - min) / (max - min), the day NULL where max == min; "quantile":
+    (average rank - 0.5) / n."""
+    if method not in NORMALIZE_METHODS:
+        raise ValueError(f"method must be one of 'zscore', 'minmax', 'quantile', not {method!r}")
+    _build_shapes(("factor",), (factor,))
+    if method == "zscore":
+        return factor_clean(factor, standardize=True)
+    if method == "quantile":
+        return factor_rank(factor, RANK_MODES["quantile"])
+    return _build_call("pq_factor_minmax", [factor], lambda b, dev: ())
+
+
+def factor_weighted(factor, weight, group=None):
+    """D-20: (factor * weight) / W per day, W the sum of the weights over the day's sample (symbols whose factor and weight are both
+    non-null and finite), or with group (integer codes [N] or [N, T], negative = unclassified, at most 256 groups) over the symbol's group
+    on that day -> device tensor [N, T], NULL outside the sample and where W == 0."""
+    n, T = _build_shapes(("factor", "weight"), (factor, weight))
+    g, G = _group_codes(group, n, T) if group is not None else (None, 0)
+
+    def args(b, dev):
+        if g is None:
+            return (None, C.c_int64(0), C.c_int32(0))
+        gd = g.to(device=dev, dtype=torch.int32)
+        if gd.dim() == 2:       # onto the factor's row pitch
+            gp = torch.empty((n, b.stride), dtype=torch.int32, device=dev)
+            gp[:, :T] = gd
+            gd, gs = gp, b.stride
+        else:
+            gd, gs = gd.contiguous(), 0
+        args.keep = gd          # kept alive until the call has returned
+        return (C.c_void_p(gd.data_ptr()) if gd.numel() else None, C.c_int64(gs), C.c_int32(G))
+    return _build_call("pq_factor_weighted", [factor, weight], args)
+
+
+def factor_binary(a, b, op: int = 0):
+    """D-20: elementwise op 0: a / b, 1: a - b, 2: (a - b) / |b| on [N, T] columns -> device tensor [N, T]; NULL where either input is
+    NULL, otherwise plain IEEE-754 (a zero divisor gives inf or nan)."""
+    if op not in (0, 1, 2):
+        raise ValueError(f"op must be 0 (a / b), 1 (a - b) or 2 ((a - b) / |b|), not {op!r}")
+    _build_shapes(("a", "b"), (a, b))
+    return _build_call("pq_factor_binary", [a, b], lambda bb, dev: (C.c_int32(op),))
+
+
 def split_periods(T: int, n_splits: int):
     """numpy.array_split(range(T), n_splits) as inclusive (start, end) day indices -> two int64 numpy arrays; 1 <= n_splits <= T"""
     if isinstance(n_splits, bool) or not isinstance(n_splits, (int, np.integer)) or not 1 <= n_splits <= T:

@@ -1,0 +1,396 @@
+// xsec/build.hip -- the README's general factor calculations: per-day rank, normalize, weighted, and the elementwise ratio and diff
+// (Factor.rank / normalize / weighted / ratio / diff; README.md:1416-1421, :1438-1470; README-only => decision D-20).
+//
+// Columns are symbol-major [n_series][stride]; a day's cross-section is a strided column.  Every output is a full [n_series][stride] f64
+// column, NULL outside the day's sample.
+//  rank family: a tiled transpose writes day-major keys (the factor where it is non-null and finite, +0 for -0, else +inf) and counts n
+//               per day; each day's row is sorted (LDS bitonic up to XS_LDS_MAX symbols, rocPRIM's segmented radix sort above); every
+//               symbol finds the tie run [a, b) of its own key by two binary searches and overwrites its key by the finished value (rank,
+//               reversed rank, pct or mid-rank position), still day-major; a second tiled transpose brings the values symbol-major, so the
+//               final stores run along days, 256 contiguous bytes per half-wave.
+//  minmax:      one thread per (day, block of 256 symbols), consecutive threads on consecutive days (coalesced), takes the block's min
+//               and max; one thread per day combines them; the (day, block) pass runs once more and writes.
+//  weighted:    the same three passes with the sum of the weights (D-12: members only, ascending symbols from 0.0, block sums in ascending
+//               block order).  With groups every lane keeps G sums in LDS ([g][lane]: consecutive lanes on consecutive 8-byte words, so no
+//               bank conflict whatever the codes), as D-16's industry sums do.
+//  ratio, diff: one elementwise kernel with an op code, rows along days.
+// The zscore of Factor.normalize is pq_factor_clean(standardize = 1) itself (clean.hip), not restated here.
+#include "xsec_dev.h"
+#include <rocprim/rocprim.hpp>
+
+namespace {
+
+constexpr int BD_MAX_G = 256;
+
+enum BdRank { BD_RANK = 0, BD_PCT = 1, BD_MID = 2 };
+enum BdOp { BD_RATIO = 0, BD_DIFF = 1, BD_RELDIFF = 2 };
+
+// ---------------------------------------------------------------- rank family
+// [n][stride] factor -> day-major [len][n] keys (the factor where it is valid, +0 for -0, else +inf), n per day
+__global__ __launch_bounds__(256) void bd_prep_kernel(const double *f, Dims d, double *key, int32_t *n_valid) {
+    __shared__ double tile[32][33];
+    __shared__ int cnt[32];
+    const int64_t t0 = (int64_t)blockIdx.x * 32, s0 = (int64_t)blockIdx.y * 32;
+    const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5; // 32 x 8
+    if (threadIdx.x < 32) cnt[threadIdx.x] = 0;
+    for (int i = ly; i < 32; i += 8) { // rows = symbols, lanes along days (coalesced reads)
+        const int64_t s = s0 + i, t = t0 + lx;
+        double k = xs_inf();
+        if (s < d.n && t < d.len) {
+            const double x = f[s * d.stride + t];
+            if (xs_valid(x)) k = x == 0.0 ? 0.0 : x;
+        }
+        tile[i][lx] = k;
+    }
+    __syncthreads();
+    for (int i = ly; i < 32; i += 8) { // rows = days, lanes along symbols (coalesced writes)
+        const int64_t t = t0 + i, s = s0 + lx;
+        const double k = tile[lx][i];
+        if (t < d.len && s < d.n) {
+            key[t * d.n + s] = k;
+            if (k != xs_inf()) atomicAdd(&cnt[i], 1);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 32 && t0 + threadIdx.x < d.len && cnt[threadIdx.x]) atomicAdd(&n_valid[t0 + threadIdx.x], cnt[threadIdx.x]);
+}
+
+// a + b for the tie run [a, b) of `key` in the ascending row S[0 .. nv) (key is one of its entries; PAD: an LDS row indexed through
+// xs_phys): two binary searches, so a discrete factor's long runs of equal keys cost O(log nv) per symbol
+template <bool PAD> __device__ __forceinline__ int64_t bd_run(const double *S, int nv, double key) {
+    auto at = [&](int i) { return S[PAD ? xs_phys(i) : i]; };
+    int lo = 0, hi = nv;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (at(mid) < key) lo = mid + 1; else hi = mid; }
+    const int a = lo;
+    lo = a + 1; hi = nv;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (at(mid) <= key) lo = mid + 1; else hi = mid; }
+    return (int64_t)a + (int64_t)lo;
+}
+
+// m = a + b -> the average rank ((a + 1) + b) / 2 (a half-integer: exact), reversed as n + 1 - rank (exact), then one division
+__device__ __forceinline__ double bd_value(int64_t m, int nv, int mode, int desc) {
+    double r = (double)(m + 1) / 2.0;
+    if (desc) r = (double)(nv + 1) - r;
+    if (mode == BD_PCT) r = r / (double)nv;
+    if (mode == BD_MID) r = (r - 0.5) / (double)nv;
+    return r;
+}
+
+// one workgroup per day, n <= XS_LDS_MAX: sort the day's keys in LDS; every symbol replaces its key by its value (day-major, in place)
+__global__ __launch_bounds__(1024) void bd_rank_lds_kernel(double *key, const int32_t *n_valid, int64_t n, int P, int mode, int desc) {
+    extern __shared__ __align__(16) unsigned char bd_lds[];
+    double *S = (double *)bd_lds;
+    const int64_t t = blockIdx.x;
+    double *row = key + t * n;
+    const int tid = threadIdx.x, nthr = blockDim.x, nv = n_valid[t];
+    if (nv == 0) { // uniform across the workgroup
+        for (int s = tid; s < n; s += nthr) row[s] = pq_null();
+        return;
+    }
+    for (int i = tid; i < P; i += nthr) S[xs_phys(i)] = i < n ? row[i] : xs_inf();
+    __syncthreads();
+    xs_sort_lds(S, P, (int)n, tid, nthr);
+    for (int s = tid; s < n; s += nthr) {
+        const double k = row[s];
+        row[s] = k == xs_inf() ? pq_null() : bd_value(bd_run<true>(S, nv, k), nv, mode, desc);
+    }
+}
+
+// n > XS_LDS_MAX: the day's row was sorted by rocPRIM (sorted); values from the original row, in place
+__global__ __launch_bounds__(256) void bd_rank_sorted_kernel(double *key, const double *sorted, const int32_t *n_valid, int64_t n, int mode,
+                                                             int desc) {
+    const int64_t t = blockIdx.x;
+    double *row = key + t * n;
+    const double *S = sorted + t * n;
+    const int nv = n_valid[t];
+    for (int64_t s = threadIdx.x; s < n; s += 256) {
+        const double k = row[s];
+        row[s] = k == xs_inf() ? pq_null() : bd_value(bd_run<false>(S, nv, k), nv, mode, desc);
+    }
+}
+
+// day-major [len][n] values -> symbol-major [n][stride]: 32 x 32 tiles, reads along symbols, stores along days
+__global__ __launch_bounds__(256) void bd_transpose_kernel(const double *dm, int64_t n, int64_t len, double *out, int64_t stride) {
+    __shared__ double tile[32][33];
+    const int64_t t0 = (int64_t)blockIdx.x * 32, s0 = (int64_t)blockIdx.y * 32;
+    const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5; // 32 x 8
+    for (int i = ly; i < 32; i += 8) {
+        const int64_t t = t0 + i, s = s0 + lx;
+        tile[i][lx] = (t < len && s < n) ? dm[t * n + s] : 0.0;
+    }
+    __syncthreads();
+    for (int i = ly; i < 32; i += 8) {
+        const int64_t s = s0 + i, t = t0 + lx;
+        if (s < n && t < len) out[s * stride + t] = tile[lx][i];
+    }
+}
+
+// ---------------------------------------------------------------- minmax
+// one thread per (day, block of 256 symbols): the block's min and max over the valid values (-0 read as +0); +inf / -inf without one
+template <bool WRITE>
+__global__ __launch_bounds__(64) void bd_minmax_kernel(const double *f, Dims d, double *pmin, double *pmax, const double *dmin,
+                                                       const double *dmax, double *out) {
+    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (t >= d.len) return;
+    const int64_t s_lo = (int64_t)blockIdx.y * XS_BLOCK, s_hi = s_lo + XS_BLOCK < d.n ? s_lo + XS_BLOCK : d.n;
+    double mn = xs_inf(), mx = -xs_inf();
+    if (WRITE) { mn = dmin[t]; mx = dmax[t]; }
+    const double range = mx - mn;
+    const bool dead = WRITE && mx == mn;
+    constexpr int B = 8;
+    for (int64_t s0 = s_lo; s0 < s_hi; s0 += B) {
+        double x[B];
+#pragma unroll
+        for (int k = 0; k < B; k++) x[k] = f[(s0 + k < s_hi ? s0 + k : s_hi - 1) * d.stride + t];
+#pragma unroll
+        for (int k = 0; k < B; k++) {
+            if (s0 + k >= s_hi) break;
+            const bool mem = xs_valid(x[k]);
+            const double v = x[k] == 0.0 ? 0.0 : x[k];
+            if (WRITE) {
+                out[(s0 + k) * d.stride + t] = (mem && !dead) ? (v - mn) / range : pq_null();
+            } else if (mem) {
+                mn = v < mn ? v : mn;
+                mx = v > mx ? v : mx;
+            }
+        }
+    }
+    if (WRITE) return;
+    const int64_t o = (int64_t)blockIdx.y * d.len + t;
+    pmin[o] = mn;
+    pmax[o] = mx;
+}
+
+__global__ __launch_bounds__(64) void bd_minmax_combine_kernel(const double *pmin, const double *pmax, int64_t nblk, int64_t len, double *dmin,
+                                                               double *dmax) {
+    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (t >= len) return;
+    double mn = xs_inf(), mx = -xs_inf();
+    for (int64_t k = 0; k < nblk; k++) {
+        const double a = pmin[k * len + t], b = pmax[k * len + t];
+        mn = a < mn ? a : mn;
+        mx = b > mx ? b : mx;
+    }
+    dmin[t] = mn;
+    dmax[t] = mx;
+}
+
+// ---------------------------------------------------------------- weighted
+struct BdW {
+    const double *f, *w;
+    const int32_t *grp;   // null = one sum per day
+    int64_t gstride;      // 0: grp is [n], else [n][gstride]
+    int32_t G;            // group codes in [0, G)
+    Dims d;
+};
+
+__device__ __forceinline__ bool bd_w_member(const BdW &in, double x, double w, int32_t g) {
+    return xs_valid(x) && xs_valid(w) && (!in.grp || (g >= 0 && g < in.G));
+}
+
+enum BdWPass { BD_W_SUM, BD_W_GSUM, BD_W_WRITE };
+
+// one thread per (day, block of 256 symbols).  BD_W_SUM: the block's sum of w over the members, ascending symbols from 0.0 (D-12);
+// BD_W_GSUM: one such sum per group, [g][lane] in LDS; BD_W_WRITE: (x w) / W with the day's (or the day's group's) W, NULL where W == 0
+template <int P>
+__global__ __launch_bounds__(64) void bd_weighted_kernel(BdW in, double *ps, const double *W, double *out) {
+    extern __shared__ __align__(16) unsigned char bd_lds[];
+    const Dims d = in.d;
+    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (t >= d.len) return;
+    const int lane = threadIdx.x, G = in.G;
+    double *gs = (double *)bd_lds;
+    if (P == BD_W_GSUM)
+        for (int g = 0; g < G; g++) gs[g * 64 + lane] = 0.0;
+    const bool grouped = in.grp != nullptr;
+    const double Wday = (P == BD_W_WRITE && !grouped) ? W[t] : 0.0;
+    const int64_t s_lo = (int64_t)blockIdx.y * XS_BLOCK, s_hi = s_lo + XS_BLOCK < d.n ? s_lo + XS_BLOCK : d.n;
+    double a0 = 0.0;
+    constexpr int B = 8;
+    for (int64_t s0 = s_lo; s0 < s_hi; s0 += B) {
+        double x[B], w[B];
+        int32_t g[B];
+#pragma unroll
+        for (int k = 0; k < B; k++) {
+            const int64_t s = s0 + k < s_hi ? s0 + k : s_hi - 1, o = s * d.stride + t;
+            x[k] = in.f[o];
+            w[k] = in.w[o];
+            g[k] = grouped ? in.grp[in.gstride ? s * in.gstride + t : s] : 0;
+        }
+#pragma unroll
+        for (int k = 0; k < B; k++) {
+            if (s0 + k >= s_hi) break;
+            const bool mem = bd_w_member(in, x[k], w[k], g[k]);
+            if (P == BD_W_SUM) { if (mem) a0 += w[k]; continue; }
+            if (P == BD_W_GSUM) { if (mem) gs[g[k] * 64 + lane] += w[k]; continue; }
+            double v = pq_null();
+            if (mem) {
+                const double Ws = grouped ? W[(int64_t)g[k] * d.len + t] : Wday;
+                if (Ws != 0.0) v = (x[k] * w[k]) / Ws;
+            }
+            out[(s0 + k) * d.stride + t] = v;
+        }
+    }
+    if (P == BD_W_SUM) ps[(int64_t)blockIdx.y * d.len + t] = a0;
+    if (P == BD_W_GSUM)
+        for (int g = 0; g < G; g++) ps[((int64_t)blockIdx.y * G + g) * d.len + t] = gs[g * 64 + lane];
+}
+
+// one thread per (day, group): the block sums in ascending block order from 0.0 -> W [G][len] (G = 1 without groups)
+__global__ __launch_bounds__(64) void bd_weighted_combine_kernel(const double *ps, int64_t nblk, int64_t len, int G, double *W) {
+    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    const int g = blockIdx.y;
+    if (t >= len) return;
+    double s = 0.0;
+    for (int64_t k = 0; k < nblk; k++) s += ps[(k * G + g) * len + t];
+    W[(int64_t)g * len + t] = s;
+}
+
+// ---------------------------------------------------------------- ratio / diff
+// one workgroup per (series, 256 days), walked with a grid stride; NULL where either input is NULL, else plain IEEE-754
+__global__ __launch_bounds__(256) void bd_binary_kernel(const double *a, const double *b, Dims d, int op, int64_t chunks, int64_t total,
+                                                        double *out) {
+    for (int64_t w = blockIdx.x; w < total; w += gridDim.x) {
+        const int64_t s = w / chunks, t = (w - s * chunks) * 256 + threadIdx.x;
+        if (t >= d.len) continue;
+        const int64_t o = s * d.stride + t;
+        const double x = a[o], y = b[o];
+        double v;
+        if (pq_isnull(x) || pq_isnull(y)) v = pq_null();
+        else if (op == BD_RATIO) v = x / y;
+        else if (op == BD_DIFF) v = x - y;
+        else v = (x - y) / fabs(y);
+        out[o] = v;
+    }
+}
+
+} // namespace
+
+extern "C" {
+
+pq_status pq_factor_rank(pq_ctx *ctx, const pq_batch *b, const double *factor, int32_t mode, int32_t descending, double *out) {
+    PQ_TRY(pq_check(ctx, b));
+    PQ_REQUIRE(mode >= BD_RANK && mode <= BD_MID, "pq_factor_rank: mode must be 0 (rank), 1 (pct) or 2 (mid-rank position)");
+    PQ_REQUIRE(descending == 0 || descending == 1, "pq_factor_rank: descending must be 0 or 1");
+    PQ_REQUIRE(b->n_series == 0 || b->len == 0 || (factor && out), "pq_factor_rank: null pointer");
+    if (ctx->rec) { pq_set_error("pq_factor_rank cannot be recorded into a suite"); return PQ_ERR_UNSUPPORTED; }
+    PQ_NO_RAGGED(b, "pq_factor_rank (a cross-section needs every symbol on every day)");
+    if (b->len == 0 || b->n_series == 0) return PQ_OK;
+    const Dims d = dims_of(b);
+    const size_t cells = (size_t)d.len * (size_t)d.n, len = (size_t)d.len;
+    const bool wide = d.n > XS_LDS_MAX;
+    if (wide) {
+        PQ_REQUIRE(d.n <= 100000, "pq_factor_rank supports at most 100000 series");
+        PQ_REQUIRE(cells < (1ull << 32), "pq_factor_rank needs n_series * len < 2^32 above 16384 series");
+    }
+    size_t tmp_bytes = 0;
+    if (wide)
+        PQ_HIP_TRY(rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes, (double *)nullptr, (double *)nullptr, (unsigned)cells,
+                                                      (unsigned)d.len, (unsigned *)nullptr, (unsigned *)nullptr, 0, 64, ctx->stream));
+    // workspace: keys, then values (f64, day-major) | n per day (i32) | wide: sorted keys (f64), offsets (u32), rocPRIM temp
+    const size_t o_cnt = xs_al(cells * 8), o_srt = o_cnt + xs_al(len * 4), o_off = o_srt + (wide ? xs_al(cells * 8) : 0),
+                 o_tmp = o_off + (wide ? xs_al((len + 1) * 4) : 0), total = o_tmp + (wide ? xs_al(tmp_bytes) : 0);
+    PQ_TRY(pq_ws_reserve(ctx, total));
+    unsigned char *ws = (unsigned char *)ctx->ws;
+    double *key = (double *)ws;
+    int32_t *nv = (int32_t *)(ws + o_cnt);
+    hipStream_t st = ctx->stream;
+    const dim3 gt((unsigned)((d.len + 31) / 32), (unsigned)((d.n + 31) / 32));
+    PQ_HIP_TRY(hipMemsetAsync(nv, 0, len * 4, st));
+    hipLaunchKernelGGL(bd_prep_kernel, gt, dim3(256), 0, st, factor, d, key, nv);
+    if (!wide) {
+        int P = 16;
+        while (P < d.n) P <<= 1;
+        const int nthr = P / 16 < 64 ? 64 : (P / 16 > 1024 ? 1024 : P / 16);
+        const size_t lds = (size_t)(P + P / 16) * 8;
+        PQ_HIP_TRY(hipFuncSetAttribute((const void *)bd_rank_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(bd_rank_lds_kernel, dim3((unsigned)d.len), dim3(nthr), lds, st, key, (const int32_t *)nv, d.n, P, mode, descending);
+    } else {
+        double *srt = (double *)(ws + o_srt);
+        unsigned *off = (unsigned *)(ws + o_off);
+        hipLaunchKernelGGL(xs_offsets_kernel, dim3((unsigned)((d.len + 256) / 256)), dim3(256), 0, st, off, d.len, d.n);
+        PQ_HIP_TRY(rocprim::segmented_radix_sort_keys(ws + o_tmp, tmp_bytes, key, srt, (unsigned)cells, (unsigned)d.len, off, off + 1, 0, 64,
+                                                      st));
+        hipLaunchKernelGGL(bd_rank_sorted_kernel, dim3((unsigned)d.len), dim3(256), 0, st, key, (const double *)srt, (const int32_t *)nv, d.n,
+                           mode, descending);
+    }
+    hipLaunchKernelGGL(bd_transpose_kernel, gt, dim3(256), 0, st, (const double *)key, d.n, d.len, out, d.stride);
+    PQ_HIP_TRY(hipGetLastError());
+    return PQ_OK;
+}
+
+pq_status pq_factor_minmax(pq_ctx *ctx, const pq_batch *b, const double *factor, double *out) {
+    PQ_TRY(pq_check(ctx, b));
+    PQ_REQUIRE(b->n_series == 0 || b->len == 0 || (factor && out), "pq_factor_minmax: null pointer");
+    if (ctx->rec) { pq_set_error("pq_factor_minmax cannot be recorded into a suite"); return PQ_ERR_UNSUPPORTED; }
+    PQ_NO_RAGGED(b, "pq_factor_minmax (a cross-section needs every symbol on every day)");
+    if (b->len == 0 || b->n_series == 0) return PQ_OK;
+    const Dims d = dims_of(b);
+    const size_t len = (size_t)d.len;
+    const int64_t nblk = (d.n + XS_BLOCK - 1) / XS_BLOCK;
+    // workspace: block partials min, max [nblk][len] | per-day min, max [len]
+    const size_t part = xs_al((size_t)nblk * len * 8), row = xs_al(len * 8);
+    PQ_TRY(pq_ws_reserve(ctx, 2 * part + 2 * row));
+    unsigned char *ws = (unsigned char *)ctx->ws;
+    double *pmin = (double *)ws, *pmax = (double *)(ws + part), *dmin = (double *)(ws + 2 * part), *dmax = (double *)(ws + 2 * part + row);
+    const dim3 gp((unsigned)((d.len + 63) / 64), (unsigned)nblk), gd((unsigned)((d.len + 63) / 64));
+    hipStream_t st = ctx->stream;
+    hipLaunchKernelGGL(bd_minmax_kernel<false>, gp, dim3(64), 0, st, factor, d, pmin, pmax, (const double *)nullptr, (const double *)nullptr,
+                       (double *)nullptr);
+    hipLaunchKernelGGL(bd_minmax_combine_kernel, gd, dim3(64), 0, st, (const double *)pmin, (const double *)pmax, nblk, d.len, dmin, dmax);
+    hipLaunchKernelGGL(bd_minmax_kernel<true>, gp, dim3(64), 0, st, factor, d, (double *)nullptr, (double *)nullptr, (const double *)dmin,
+                       (const double *)dmax, out);
+    PQ_HIP_TRY(hipGetLastError());
+    return PQ_OK;
+}
+
+pq_status pq_factor_weighted(pq_ctx *ctx, const pq_batch *b, const double *factor, const double *weight, const int32_t *group,
+                             int64_t group_stride, int32_t n_groups, double *out) {
+    PQ_TRY(pq_check(ctx, b));
+    PQ_REQUIRE(!group || (n_groups >= 1 && n_groups <= BD_MAX_G), "pq_factor_weighted: n_groups must be in [1, 256]");
+    PQ_REQUIRE(!group || group_stride == 0 || group_stride >= b->len, "pq_factor_weighted: group_stride must be 0 ([n_series] codes) or >= len");
+    PQ_REQUIRE(b->n_series == 0 || b->len == 0 || (factor && weight && out), "pq_factor_weighted: null pointer");
+    if (ctx->rec) { pq_set_error("pq_factor_weighted cannot be recorded into a suite"); return PQ_ERR_UNSUPPORTED; }
+    PQ_NO_RAGGED(b, "pq_factor_weighted (a cross-section needs every symbol on every day)");
+    if (b->len == 0 || b->n_series == 0) return PQ_OK;
+    const Dims d = dims_of(b);
+    const size_t len = (size_t)d.len;
+    const int G = group ? n_groups : 1;
+    const int64_t nblk = (d.n + XS_BLOCK - 1) / XS_BLOCK;
+    const BdW in{factor, weight, group, group ? group_stride : 0, group ? n_groups : 0, d};
+    // workspace: block partials [nblk][G][len] | W [G][len]
+    const size_t part = xs_al((size_t)nblk * (size_t)G * len * 8);
+    PQ_TRY(pq_ws_reserve(ctx, part + xs_al((size_t)G * len * 8)));
+    unsigned char *ws = (unsigned char *)ctx->ws;
+    double *ps = (double *)ws, *W = (double *)(ws + part);
+    const dim3 gp((unsigned)((d.len + 63) / 64), (unsigned)nblk), gc((unsigned)((d.len + 63) / 64), (unsigned)G);
+    hipStream_t st = ctx->stream;
+    if (group) {
+        const size_t lds = (size_t)G * 64 * 8;
+        PQ_HIP_TRY(hipFuncSetAttribute((const void *)bd_weighted_kernel<BD_W_GSUM>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(bd_weighted_kernel<BD_W_GSUM>, gp, dim3(64), lds, st, in, ps, (const double *)nullptr, (double *)nullptr);
+    } else {
+        hipLaunchKernelGGL(bd_weighted_kernel<BD_W_SUM>, gp, dim3(64), 0, st, in, ps, (const double *)nullptr, (double *)nullptr);
+    }
+    hipLaunchKernelGGL(bd_weighted_combine_kernel, gc, dim3(64), 0, st, (const double *)ps, nblk, d.len, G, W);
+    hipLaunchKernelGGL(bd_weighted_kernel<BD_W_WRITE>, gp, dim3(64), 0, st, in, (double *)nullptr, (const double *)W, out);
+    PQ_HIP_TRY(hipGetLastError());
+    return PQ_OK;
+}
+
+pq_status pq_factor_binary(pq_ctx *ctx, const pq_batch *b, const double *a, const double *bcol, int32_t op, double *out) {
+    PQ_TRY(pq_check(ctx, b));
+    PQ_REQUIRE(op >= BD_RATIO && op <= BD_RELDIFF, "pq_factor_binary: op must be 0 (a / b), 1 (a - b) or 2 ((a - b) / |b|)");
+    PQ_REQUIRE(b->n_series == 0 || b->len == 0 || (a && bcol && out), "pq_factor_binary: null pointer");
+    if (ctx->rec) { pq_set_error("pq_factor_binary cannot be recorded into a suite"); return PQ_ERR_UNSUPPORTED; }
+    PQ_NO_RAGGED(b, "pq_factor_binary (the columns of a factor are [n_series][stride])");
+    if (b->len == 0 || b->n_series == 0) return PQ_OK;
+    const Dims d = dims_of(b);
+    const int64_t chunks = (d.len + 255) / 256, total = chunks * d.n;
+    const unsigned grid = (unsigned)(total < (int64_t)1 << 20 ? total : (int64_t)1 << 20);
+    hipLaunchKernelGGL(bd_binary_kernel, dim3(grid), dim3(256), 0, ctx->stream, a, bcol, d, op, chunks, total, out);
+    PQ_HIP_TRY(hipGetLastError());
+    return PQ_OK;
+}
+
+} // extern "C"

@@ -1,10 +1,11 @@
-"""Factor -- the evaluation half of the README's `Factor` class (README.md:1429-1430, :1480-1482, :1626-1634): per-day
-cross-sectional IC, Rank-IC and their rolling mean / information ratio (decision D-12, oracle/backtest.c), and quantile sorts,
-long-short legs, turnover, coverage and IC statistics (decision D-15), and the regressions and significance tests
-ic_test / factor_return / fama_macbeth / time_series_regression (decision D-17), and the robustness tests ic_decay / subsample_test /
-subgroup_test (decision D-18), and the multi-factor orthogonalization / neutralization Factor().clean (decision D-19).  README-only
-in the reference.  Inputs are [N, T] arrays (symbol-major, like every other column of this package): the factor and the forward return
-of every symbol on every day.
+"""Factor -- both halves of the README's `Factor` class.  The general factor calculations ratio / diff / weighted / normalize / rank
+(README.md:1416-1421, :1438-1470; decision D-20) build the [N, T] factor columns; the evaluation half consumes
+them (README.md:1429-1430, :1480-1482, :1626-1634): per-day cross-sectional IC, Rank-IC and their rolling mean / information ratio
+(decision D-12, oracle/backtest.c), and quantile sorts, long-short legs, turnover, coverage and IC statistics (decision D-15), and the
+regressions and significance tests ic_test / factor_return / fama_macbeth / time_series_regression (decision D-17), and the robustness
+tests ic_decay / subsample_test / subgroup_test (decision D-18), and the multi-factor orthogonalization / neutralization Factor().clean
+(decision D-19).  README-only in the reference.  Inputs are [N, T] arrays (symbol-major, like every other column of this package): the
+factor and the forward return of every symbol on every day.
 `clean` is the README's factor cleaning step that comes before the evaluation (decision D-16).
 """
 from __future__ import annotations
@@ -22,6 +23,31 @@ class Factor:
         # class itself carries no `clean` attribute: the package's public-surface contract keeps `Factor.clean` off the class so that it
         # is never taken for the module-level single-factor `clean` (D-16).
         self.clean = self._clean_factors
+
+    # ---- D-20: the general factor calculations (README.md:1416-1421, :1438-1470); every result is a device f64 [N, T] column
+    def ratio(self, a, b):
+        """-> a / b; NULL where either is NULL, otherwise plain IEEE-754 (a zero divisor gives inf or nan)"""
+        return _api.factor_binary(a, b, _api.BINARY_OPS["ratio"])
+
+    def diff(self, a, b, normalize=False):
+        """-> a - b, or (a - b) / |b| with normalize=True; NULL where either is NULL"""
+        return _api.factor_binary(a, b, _api.BINARY_OPS["reldiff" if normalize else "diff"])
+
+    def weighted(self, factor, weight, group=None):
+        """-> (factor * weight) / W per day, W the sum of the weights over the symbols whose factor and weight are both non-null and
+        finite; with group (integer codes [N] or [N, T], negative = unclassified, at most 256 groups) W is the sum over the symbol's
+        group on that day.  NULL outside the sample and where W == 0"""
+        return _api.factor_weighted(factor, weight, group)
+
+    def normalize(self, factor, method="zscore"):
+        """per day over the non-null finite symbols: "zscore" (x - mean) / sample std (clean(factor, standardize=True) itself),
+        "minmax" (x - min) / (max - min) (the day NULL where max == min), "quantile" (average rank - 0.5) / n, in (0, 1)"""
+        return _api.factor_normalize(factor, method)
+
+    def rank(self, factor, ascending=True, pct=False):
+        """per day over the non-null finite symbols: the average rank in 1 .. n (ties share the mean of their positions; -0 ties with
+        +0), ascending=False: n + 1 - rank, pct=True: divided by n; NULL outside the day's sample"""
+        return _api.factor_rank(factor, _api.RANK_MODES["pct" if pct else "rank"], not ascending)
 
     def ic(self, factor, next_return):
         """-> (ic [T], n_valid [T]): Pearson correlation across symbols, per day"""
