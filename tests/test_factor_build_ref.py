@@ -146,6 +146,62 @@ def test_minmax_and_weighted_against_plain_numpy(n):
         assert R.isnull(wg[~mw | (g < 0), t]).all()
 
 
+def test_descending_mid_rank_equals_scipy_rankdata():
+    """rank(f, "quantile", True), which only pq_factor_rank's C ABI reaches: ((n + 1 - rank) - 0.5) / n, the mid-rank position of the
+    descending order -- scipy's average rank of the negated keys, one subtraction and one division"""
+    from scipy.stats import rankdata
+    for discrete in (False, True):
+        _, f = table(7, discrete=discrete)
+        f[f == 0.0] = np.where(np.arange(int((f == 0.0).sum())) % 2 == 0, -0.0, 0.0)
+        q = R.rank(f, "quantile", True)
+        for t in range(f.shape[1]):
+            m = R.valid(f[:, t])
+            same(q[m, t], (rankdata(-f[m, t], method="average") - 0.5) / float(m.sum()))
+            assert R.isnull(q[~m, t]).all()
+
+
+def test_weighted_with_n_groups_below_the_largest_code():
+    """codes >= n_groups, negative codes and the extreme int32 values are in no group: a plain per-group Python loop (n <= 256: the
+    blocked sum is the plain ascending sum)"""
+    rng, f = table(8, n=200, T=5)
+    w = np.exp(rng.standard_normal(f.shape))
+    w[rng.random(f.shape) < 0.05] = NULL
+    kinds = np.array(list(range(-3, 9)) + [-2 ** 31, 2 ** 31 - 1], dtype=np.int64)
+    for G, shape in ((4, (200,)), (4, (200, 5)), (1, (200, 5))):
+        g = rng.choice(kinds, shape)
+        got = R.weighted(f, w, g, G)
+        g2 = np.broadcast_to(g[:, None] if g.ndim == 1 else g, f.shape)
+        exp = np.full(f.shape, NULL)
+        for t in range(f.shape[1]):
+            for c in range(G):
+                mem = [s for s in range(f.shape[0]) if g2[s, t] == c and R.valid(f[s, t]) and R.valid(w[s, t])]
+                W = 0.0
+                for s in mem:
+                    W += w[s, t]
+                for s in mem:
+                    exp[s, t] = (f[s, t] * w[s, t]) / W
+        same(got, exp)
+        assert R.isnull(got[(g2 < 0) | (g2 >= G)]).all() and not R.isnull(got[g2 == 0]).all()
+
+
+def test_minmax_subnormal_range_against_fractions():
+    """members m * 2^-1074 over a range of 1 and of 1 000 units: the quotient is the correctly rounded m / range, in exact rationals"""
+    from fractions import Fraction
+    sub = 5e-324
+    rng = np.random.default_rng(9)
+    f = np.stack([np.where(rng.random(60) < 0.5, 0.0, sub), rng.integers(0, 1001, 60) * sub], axis=1)
+    f[:3, 0] = -0.0, sub, NULL
+    f[:2, 1] = 0.0, 1000 * sub
+    got = R.minmax(f)
+    for t in range(f.shape[1]):
+        mem = [s for s in range(60) if R.valid(f[s, t])]
+        lo, hi = min(Fraction(f[s, t]) for s in mem), max(Fraction(f[s, t]) for s in mem)
+        assert hi > lo
+        for s in mem:
+            assert got[s, t] == float((Fraction(f[s, t]) - lo) / (hi - lo)), (s, t)
+    assert R.isnull(got[2, 0]) and set(got[[0, 1], 0]) == {0.0, 1.0} and got[1, 1] == 1.0
+
+
 # ---------------------------------------------------------------- the public surface
 def test_public_surface():
     import polars_quant_amd as pq

@@ -1,4 +1,4 @@
-"""-m gpu: the cross-sectional kernels of D-15 .. D-19 (csrc/xsec/: sorts, clean, regress, robust, orth) at every size class and
+"""-m gpu: the cross-sectional kernels of D-15 .. D-20 (csrc/xsec/: sorts, clean, regress, robust, orth, build) at every size class and
 template branch they dispatch on, bit for bit against the numpy restatements (p-values within close_p's bound), with the helpers of the
 feature test modules.
 
@@ -58,12 +58,43 @@ Where each branch is reached (the failure tags name function, shape, Q / K / L /
 | more than three symbol blocks at K > 3          | test_orth_many_blocks[K4, K8]: n = 2 049, 9 blocks                            |
 | CPU pin of K = 2 .. 8 against lstsq             | test_factor_orth_ref.py: test_against_lstsq_and_orthogonal,                   |
 |                                                 |   test_sample_size_thresholds, test_every_solved_level_count                  |
+| D-20, build.hip                                 |                                                                               |
+| bd_rank_lds_kernel at every P = 16 .. 16 384    | test_build_rank_sort_sizes: P = 16 [n16], 32 [n17 .. n32], 64 [n33], 128      |
+|   (64 .. 1 024 threads); bd_run's last slot on  |   [n65, n128], 256 [n255, n256], 512 [n257 .. n512], 1 024 [n513, n1024],     |
+|   a row with n == P and no +inf tail            |   2 048 [n1025, n2048], 4 096 [n2049], 8 192 [n4097, n8192], 16 384 [n8193 .. |
+|                                                 |   n16384]; days 0, 1, 3 have n_valid == n (asserted on the input's sample)    |
+| nv == 0 (the return before the barrier), nv of  |   day 5 has no member, day 4 has 1 - 3, day 0 is one tie run of length n      |
+|   1 - 3 under a +inf tail, one tie run of n     |   (up to n = 16 384)                                                          |
+| pq_factor_rank(mode = 2, descending = 1), which |   every case, and test_build_wide_path, through the C ABI against             |
+|   the Python layer refuses                      |   rank(f, "quantile", True)                                                   |
+| wide (rocPRIM) rank: bd_rank_sorted_kernel on   | test_build_wide_path[n16385, n100000]: days all equal / all NULL / one member |
+|   an all-NULL day, a one-member day, one tie    |   / ties, signed zeros and ~5 % NULL, NaN, +-inf; n = 16 385 also at pitch 5  |
+|   run of n; the limit and above it              | test_build_above_the_limit: n = 100 001, the rank family raises and writes    |
+|                                                 |   nothing, minmax / zscore / weighted (G = 6, 256) / ratio / diff compute     |
+| bd_prep / bd_transpose 32 x 32 tiles and the    | test_build_tiles: (n, T) over {31, 32, 33} x {1, 31, 32, 33}, (5, 300),       |
+|   64-day passes: both tile edges at once, T = 1 |   (257, 129), every method, the corner cell in every sample; [n32-T33] at     |
+|   many day tiles over few symbols               |   pitch 37                                                                    |
+| look-ahead of 8 of bd_minmax / bd_weighted in   | test_build_look_ahead: n % 8 = 1 .. 7, 0 [n257 .. n264], [n511, n512, n513],  |
+|   the last of several blocks                    |   nine blocks [n2049]; T = 63 and 65; the last symbol is in every sample      |
+| bd_w_member's guard g < G; group_stride above   | test_build_group_codes_outside_the_range: n_groups = 4, codes from -3 .. 8,   |
+|   the batch stride                              |   INT32_MIN, INT32_MAX as [N] and as [N, T] at group_stride T + 5 (pad        |
+|                                                 |   columns hold the live code 0); n_groups = 1 with every code >= 1: all NULL  |
+| bd_binary_kernel's second grid step             | test_build_binary_grid_stride: (2^20 + 3, 1), chunks = 1; (524 289, 257),     |
+|   (total > 2^20 workgroups), s = w / chunks     |   chunks = 2, total = 2^20 + 2: row 524 288 is the second step                |
+| minmax: a day of +-0, a day of one, a subnormal | test_build_minmax_and_weight_edges: one table of days at n = 300; the         |
+|   range, a range that overflows; W = +inf       |   overflowing range and W = +inf compare non-NULL NaN with non-NULL NaN       |
+| ctx->ws reuse: wide rank, LDS rank, grouped     | test_build_workspace_reuse: one context, five calls, the last bitwise equal   |
+|   weighted, minmax, wide rank again             |   to the first                                                                |
 
-Every size family has one case at an odd row pitch: n = 257 (sorts, rank sort sizes, lag tiles, group tiles, every orth K), q = 7,
-n = 257 (xsec K), T = 257 (ts K), T = 2 049 (summaries, robust summaries), the wide percentile clean and the wide rank sub-group."""
+Every size family has one case at an odd row pitch: n = 257 (sorts, rank sort sizes, lag tiles, group tiles, every orth K, the D-20 rank
+sizes), q = 7, n = 257 (xsec K), T = 257 (ts K), T = 2 049 (summaries, robust summaries), the wide percentile clean, the wide rank
+sub-group, the wide D-20 rank at n = 16 385 and the D-20 tiles at (32, 33)."""
+import ctypes as C
+
 import numpy as np
 import pytest
 
+import test_factor_build_gpu as BG
 import test_factor_clean_gpu as CL
 import test_factor_orth_gpu as OG
 import test_factor_orth_ref as OR
@@ -465,3 +496,297 @@ def test_orth_many_blocks(pq, K):
     for method in OG.O.MODES:
         _, exp = OG.check(pq, F, method)
         assert not OG.O.isnull(exp).all(axis=1).any()
+
+
+# ---------------------------------------------------------------- D-20: build.hip
+R = BG.R
+BUILD_NS = sorted(SORT_NS + [511, 512, 513])
+TILE_CASES = [(n, T) for n in (31, 32, 33) for T in (1, 31, 32, 33)] + [(5, 300), (257, 129)]
+AHEAD_NS = [257, 258, 259, 260, 261, 262, 263, 264, 511, 512, 513, 2049]
+AHEAD_TS = [63, 65]
+I32_MIN, I32_MAX = -2 ** 31, 2 ** 31 - 1
+CODE_KINDS = np.array(list(range(-3, 9)) + [I32_MIN, I32_MAX], dtype=np.int64)
+SENTINEL = 7.0
+
+
+def lds_p(n):
+    """pq_factor_rank's padded LDS row: the next power of two >= max(16, n)"""
+    P = 16
+    while P < n:
+        P <<= 1
+    return P
+
+
+# the case tables reach every value the branch table names (checked at import, with or without a GPU)
+assert {lds_p(n) for n in BUILD_NS} == {16 << i for i in range(11)} and {n for n in BUILD_NS if n == lds_p(n)} >= {16, 32, 128, 256, 512}
+assert {n % 8 for n in AHEAD_NS} == set(range(8)) and all(n > 256 for n in AHEAD_NS)
+
+
+def build_c(name, cols, scalars, out=None):
+    """one D-20 entry point through the C ABI on device columns of one row pitch -> out [N, T] at that pitch, prefilled with SENTINEL"""
+    from polars_quant_amd import api
+    from polars_quant_amd._lib import Batch, check, lib
+    n, T = cols[0].shape
+    pitch = max(int(cols[0].stride(0)), T)
+    assert all(max(int(c.stride(0)), T) == pitch and tuple(c.shape) == (n, T) for c in cols)
+    if out is None:
+        out = torch.full((n, pitch), SENTINEL, dtype=torch.float64, device="cuda")[:, :T]
+    b = Batch(n, T, pitch)
+    check(getattr(lib(), name)(api.ctx(), C.byref(b), *[C.c_void_p(c.data_ptr()) for c in cols], *scalars, C.c_void_p(out.data_ptr())))
+    return out
+
+
+def check_mid_descending(f, fd, tag):
+    """mode 2 with descending = 1: (n + 1 - rank - 0.5) / n, which only the C ABI accepts"""
+    got = build_c("pq_factor_rank", [fd], (C.c_int32(2), C.c_int32(1)))
+    BG.same(f"rank mode=2 descending=1 {f.shape} {tag}", got.cpu().numpy(), R.rank(f, "quantile", True))
+
+
+def build_days(n, seed):
+    """size_days' five days and a sixth on which every symbol is NULL; day 2 has at least one NULL"""
+    f, _ = size_days(n, 6, seed)
+    f[n // 2, 2] = X.NULL
+    f[:, 5] = X.NULL
+    return f
+
+
+@pytest.mark.parametrize("n", BUILD_NS, ids=[f"n{n}" for n in BUILD_NS])
+def test_build_rank_sort_sizes(pq, n):
+    """the rank family on both sides of every LDS sort size P = 16 .. 16 384: four rank variants, normalize("quantile") and the
+    descending mid-rank.  Days 0, 1 and 3 are full rows (at n == P no +inf tail: the last slot of both binary searches), day 0 is one
+    tie run of n, day 4 has 1 - 3 members under a +inf tail, day 5 none (the return before the barrier)."""
+    pitch = 11 if n == 257 else None
+    f = build_days(n, 1100 + n)
+    nv = R.valid(f).sum(axis=0)
+    assert (nv[[0, 1, 3]] == n).all() and 1 <= nv[2] < n and 1 <= nv[4] <= 3 and nv[5] == 0
+    assert (f[:, 0] == f[0, 0]).all() and np.signbit(f[f[:, 3] == 0.0, 3]).any() and not np.signbit(f[f[:, 3] == 0.0, 3]).all()
+    fd = BG.to_dev(f, pitch)
+    got = BG.check_rank(pq, f, fd, tag=f"pitch={pitch}")
+    assert pitch is None or got.stride(0) == pitch
+    check_mid_descending(f, fd, f"pitch={pitch}")
+
+
+def wide_days(n, seed):
+    """four days: every key equal; every symbol NULL; one member; ties, zeros of both signs and ~5 % NULL / NaN / +-inf"""
+    rng = np.random.default_rng(seed)
+    f = np.full((n, 4), X.NULL)
+    f[:, 0] = -2.5
+    f[n // 3, 2] = 0.75
+    d = np.round(rng.standard_normal(n) * 4.0) / 4.0
+    d[(d == 0.0) & (rng.random(n) < 0.5)] = -0.0
+    for v in (X.NULL, np.nan, np.inf, -np.inf):
+        d[rng.random(n) < 0.0125] = v
+    f[:, 3] = d
+    return f
+
+
+@pytest.mark.parametrize("n", [16385, 100000], ids=["n16385", "n100000"])
+def test_build_wide_path(pq, n):
+    """n > 16 384: ranks from rocPRIM's segmented sort and bd_rank_sorted_kernel, one symbol above the LDS limit and at the documented
+    limit; n = 16 385 also at an odd row pitch"""
+    f = wide_days(n, n)
+    nv = R.valid(f).sum(axis=0)
+    z = f[f[:, 3] == 0.0, 3]
+    assert nv[:3].tolist() == [n, 0, 1] and 0.9 * n < nv[3] < 0.97 * n and np.signbit(z).any() and not np.signbit(z).all()
+    assert len(np.unique(f[R.valid(f[:, 3]), 3])) < 60                      # long tie runs
+    for pitch in (None, 5) if n == 16385 else (None,):
+        fd = BG.to_dev(f, pitch)
+        got = BG.check_rank(pq, f, fd, tag=f"pitch={pitch}")
+        assert pitch is None or got.stride(0) == pitch
+        check_mid_descending(f, fd, f"pitch={pitch}")
+
+
+def test_build_above_the_limit(pq):
+    """n = 100 001: the rank family raises, naming the limit, and writes nothing; the methods that sort nothing have no limit; an
+    ordinary call on the same context computes afterwards"""
+    from polars_quant_amd._lib import PqError
+    n, T = 100001, 3
+    f, w, grp = BG.make("special", n, T, 21)
+    assert grp.shape == (n, T) and grp.max() == 5 and grp.min() == -1
+    fd, wd = BG.to_dev(f), BG.to_dev(w)
+    F = pq.Factor()
+    for call in (lambda: F.rank(fd), lambda: F.rank(fd, ascending=False, pct=True), lambda: F.normalize(fd, "quantile")):
+        with pytest.raises(PqError, match="at most 100000"):
+            call()
+    out = torch.full((n, T), SENTINEL, dtype=torch.float64, device="cuda")
+    for mode, desc in ((0, 0), (1, 1), (2, 0), (2, 1)):
+        with pytest.raises(PqError, match="at most 100000"):
+            build_c("pq_factor_rank", [fd], (C.c_int32(mode), C.c_int32(desc)), out=out)
+    torch.cuda.synchronize()
+    assert bool((out == SENTINEL).all()), "out was written by a refused call"
+    BG.check_blocked(pq, f, w, grp, fd, wd)
+    g256 = np.random.default_rng(22).integers(0, 256, n)
+    assert g256.max() == 255
+    BG.same("weighted G=256 n=100001", F.weighted(fd, wd, g256).cpu().numpy(), R.weighted(f, w, g256, 256))
+    BG.check_binary(pq, f, w, fd, wd)
+    BG.check_rank(pq, build_days(300, 23), tag="after the refusals")
+
+
+@pytest.mark.parametrize("n,T", TILE_CASES, ids=[f"n{n}-T{t}" for n, t in TILE_CASES])
+def test_build_tiles(pq, n, T):
+    """the 32 x 32 tiles of bd_prep_kernel / bd_transpose_kernel with a symbol-tile edge and a day-tile edge at once, one day, many day
+    tiles over few symbols, and the 64-day (day, block) passes: every method; the last cell of the table is in every sample"""
+    pitch = 37 if (n, T) == (32, 33) else None
+    f, w, grp = BG.make("special", n, T, 100 * n + T)
+    f[-1, -1], w[-1, -1], grp[-1, -1] = 0.5, 2.0, 0
+    f[0, -1], w[0, -1], grp[0, -1] = -0.5, 3.0, 0                  # a second member on the last day: minmax has a range
+    assert grp.shape == (n, T)
+    for exp in (R.rank(f), R.minmax(f), R.weighted(f, w), R.weighted(f, w, grp)):
+        assert not R.isnull(exp[-1, -1]) and not R.isnull(exp[0, -1])
+    fd, wd = BG.to_dev(f, pitch), BG.to_dev(w, pitch)
+    tag = f"pitch={pitch}"
+    BG.check_rank(pq, f, fd, tag=tag)
+    check_mid_descending(f, fd, tag)
+    got = BG.check_blocked(pq, f, w, grp, fd, wd, tag=tag)
+    assert pitch is None or got.stride(0) == pitch
+    BG.check_binary(pq, f, w, fd, wd, tag=tag)
+
+
+@pytest.mark.parametrize("T", AHEAD_TS, ids=[f"T{t}" for t in AHEAD_TS])
+@pytest.mark.parametrize("n", AHEAD_NS, ids=[f"n{n}" for n in AHEAD_NS])
+def test_build_look_ahead(pq, n, T):
+    """bd_minmax_kernel / bd_weighted_kernel read 8 symbols ahead, clamped to the block's last: every n % 8 in the last of several
+    blocks, both sides of the 64-day pass.  The last symbol is in every day's sample, with the largest factor of the day (the first with
+    the smallest)."""
+    for kind in ("special", "discrete"):
+        f, w, grp = BG.make(kind, n, T, 7 * n + T)
+        f[-1], w[-1] = 40.0, 3.0
+        f[0], w[0] = -40.0, 2.0                                     # a second member on every day: minmax has a range
+        grp[-1] = grp[0] = 0
+        for exp in (R.minmax(f), R.weighted(f, w), R.weighted(f, w, grp)):
+            assert not R.isnull(exp[-1]).any()
+        BG.check_blocked(pq, f, w, grp, tag=kind)
+
+
+def test_build_group_codes_outside_the_range(pq):
+    """pq_factor_weighted with n_groups below the largest code: codes >= G, negative codes and the extreme int32 values are outside
+    every group (NULL, and in no sum).  [N, T] codes sit at a group_stride above the batch stride; the pad columns hold code 0, a live
+    group, so a read off the pitch changes a sum."""
+    n, T, G = 521, 70, 4
+    f, w, _ = BG.make("special", n, T, 41)
+    fd, wd = BG.to_dev(f), BG.to_dev(w)
+    ok = R.valid(f) & R.valid(w)
+    rng = np.random.default_rng(42)
+
+    def run(codes, n_groups, gs):
+        if codes.ndim == 1:
+            gd = torch.from_numpy(codes.astype(np.int32)).cuda()
+        else:
+            gd = torch.zeros((n, gs), dtype=torch.int32, device="cuda")
+            gd[:, :T] = torch.from_numpy(codes.astype(np.int32)).cuda()
+        got = build_c("pq_factor_weighted", [fd, wd], (C.c_void_p(gd.data_ptr()), C.c_int64(gs), C.c_int32(n_groups)))
+        exp = R.weighted(f, w, codes, n_groups)
+        BG.same(f"weighted n_groups={n_groups} codes{list(codes.shape)} group_stride={gs}", got.cpu().numpy(), exp)
+        return exp
+
+    for shape, gs in (((n,), 0), ((n, T), T + 5)):
+        codes = rng.choice(CODE_KINDS, shape)
+        c2 = np.broadcast_to(codes[:, None] if codes.ndim == 1 else codes, (n, T))
+        for kind in (c2 < 0, (c2 >= G) & (c2 < 9), c2 == I32_MIN, c2 == I32_MAX):
+            assert (kind & ok).any()                                   # each kind falls on a cell whose factor and weight are valid
+        exp = run(codes, G, gs)
+        assert R.isnull(exp[(c2 < 0) | (c2 >= G)]).all()
+        assert all(not R.isnull(exp[c2 == g]).all() for g in range(G))
+        high = rng.choice(CODE_KINDS[CODE_KINDS >= 1], shape)
+        assert R.isnull(run(high, 1, gs)).all()
+
+
+def test_build_binary_grid_stride(pq):
+    """bd_binary_kernel launches at most 2^20 workgroups and walks the rest with a grid stride.  (2^20 + 3, 1): chunks = 1, three
+    series on the second step, compared in full.  (524 289, 257): chunks = 2, total = 2^20 + 2, so series 524 288 is the second step and
+    s = w / chunks matters there; inputs drawn on the device in [1, 2), no result is the sentinel 7.0 the output starts from."""
+    ops = ("ratio", "diff", "reldiff")
+    n, T = (1 << 20) + 3, 1
+    assert -(-T // 256) * n == (1 << 20) + 3
+    rng = np.random.default_rng(51)
+    a, b = 1.0 + rng.random((n, T)), 1.0 + rng.random((n, T))
+    ad, bd = BG.to_dev(a), BG.to_dev(b)
+    for op, name in enumerate(ops):
+        got = build_c("pq_factor_binary", [ad, bd], (C.c_int32(op),))
+        BG.same(f"{name} {n}x{T}", got.cpu().numpy(), R.binary(a, b, name), ieee_nan=True)
+    n, T = 524289, 257
+    assert -(-T // 256) == 2 and 2 * n == (1 << 20) + 2
+    rows = [0, 1, 262144, 524287, 524288]
+    g = torch.Generator(device="cuda")
+    g.manual_seed(52)
+    ad = torch.rand((n, T), dtype=torch.float64, device="cuda", generator=g).add_(1.0)
+    bd = torch.rand((n, T), dtype=torch.float64, device="cuda", generator=g).add_(1.0)
+    out = torch.empty((n, T), dtype=torch.float64, device="cuda")
+    a, b = ad[rows].cpu().numpy(), bd[rows].cpu().numpy()
+    for op, name in enumerate(ops):
+        out.fill_(SENTINEL)
+        build_c("pq_factor_binary", [ad, bd], (C.c_int32(op),), out=out)
+        assert not bool((out == SENTINEL).any()), f"{name} {n}x{T}: cells were not written"
+        BG.same(f"{name} {n}x{T} rows {rows}", out[rows].cpu().numpy(), R.binary(a, b, name), ieee_nan=True)
+    del ad, bd, out
+    torch.cuda.empty_cache()
+
+
+SUB = 5e-324      # 2^-1074, the smallest subnormal
+
+
+def edge_days(n=300, seed=61):
+    """minmax days -> 0: every member +-0; 1: one member; 2: min = 0, max = 2^-1074; 3: members m * 2^-1074, m in 0 .. 1000; 4: members
+    spanning +-1.5e308, the range overflows; 5: an ordinary day with NULLs"""
+    rng = np.random.default_rng(seed)
+    f = rng.standard_normal((n, 6))
+    f[:, 0] = np.where(rng.random(n) < 0.5, 0.0, -0.0)
+    f[:, 1] = X.NULL
+    f[7, 1] = 3.0
+    f[:, 2] = np.where(rng.random(n) < 0.5, 0.0, SUB)
+    f[:3, 2] = -0.0, SUB, X.NULL
+    f[:, 3] = rng.integers(0, 1001, n) * SUB
+    f[:2, 3] = 0.0, 1000 * SUB
+    f[:, 4] = rng.uniform(-1.5, 1.5, n) * 1e308
+    f[:3, 4] = -1.5e308, 1.5e308, 0.0
+    f[rng.random(n) < 0.05, 5] = X.NULL
+    return f
+
+
+def test_build_minmax_and_weight_edges(pq):
+    """minmax on days that are dead (all +-0, one member), on subnormal ranges (f64 division of denormals: exact, m / 1000 correctly
+    rounded) and on a range that overflows (the plain IEEE quotient: 0, or a NaN that is not NULL); weighted on a day whose W = +inf"""
+    n = 300
+    f = edge_days(n)
+    exp = R.minmax(f)
+    assert R.isnull(exp[:, :2]).all() and set(exp[R.valid(f[:, 2]), 2]) == {0.0, 1.0} and R.isnull(exp[2, 2])
+    assert (exp[:, 3] == np.round(f[:, 3] / SUB) / 1000.0).all() and (exp[:, 3] > 0.0).any()
+    over = exp[:, 4]
+    assert (np.isnan(over) & ~R.isnull(over)).any() and (over == 0.0).any() and ((over == 0.0) | np.isnan(over)).all()
+    got = pq.Factor().normalize(BG.to_dev(f), "minmax").cpu().numpy()
+    keep = [0, 1, 2, 3, 5]
+    BG.same("minmax edge days", got[:, keep], exp[:, keep])
+    BG.same("minmax overflowing range", got[:, 4], over, ieee_nan=True)
+    f, w, grp = BG.make("plain", n, 6, 62)
+    w[:, 2] = 1e308
+    for g in (None, grp):
+        exp = R.weighted(f, w, g)
+        assert ((exp[:, 2] == 0.0) | (np.isnan(exp[:, 2]) & ~R.isnull(exp[:, 2]))).all() and np.isnan(exp[:, 2]).any()
+        assert (exp[:, 2] == 0.0).any() and not R.isnull(exp).any()
+        got = pq.Factor().weighted(BG.to_dev(f), BG.to_dev(w), g).cpu().numpy()
+        keep = [0, 1, 3, 4, 5]
+        BG.same(f"weighted beside W = inf grouped={g is not None}", got[:, keep], exp[:, keep])
+        BG.same(f"weighted W = inf grouped={g is not None}", got[:, 2], exp[:, 2], ieee_nan=True)
+
+
+def test_build_workspace_reuse(pq):
+    """one context: the wide rank (keys, counts, sorted keys, offsets and rocPRIM's temporary in ctx->ws), the LDS rank, the grouped
+    weighted at G = 256, minmax, then the first call again; no result depends on what the call before left in the workspace"""
+    F = pq.Factor()
+    rng = np.random.default_rng(71)
+    fw = BG.size_class(20000, 4, 72)
+    fw[rng.random(fw.shape) < 0.05] = X.NULL
+    fwd = BG.to_dev(fw)
+    exp_w = R.rank(fw, "pct", True)
+    first = F.rank(fwd, ascending=False, pct=True).cpu().numpy()
+    BG.same("wide rank, first", first, exp_w)
+    BG.check_rank(pq, build_days(300, 73), tag="after the wide rank")
+    f, w, _ = BG.make("special", 700, 40, 74)
+    grp = rng.integers(-1, 256, 700)
+    grp[0] = 255
+    BG.same("weighted G=256 after the ranks", F.weighted(f, w, grp).cpu().numpy(), R.weighted(f, w, grp, 256))
+    f, _, _ = BG.make("special", 513, 20, 75)
+    BG.same("minmax after weighted", F.normalize(f, "minmax").cpu().numpy(), R.minmax(f))
+    again = F.rank(fwd, ascending=False, pct=True).cpu().numpy()
+    BG.same("wide rank, again", again, exp_w)
+    BG.same("wide rank, again against first", again, first)
