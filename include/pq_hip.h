@@ -550,6 +550,24 @@ pq_status pq_factor_weighted(pq_ctx *, const pq_batch *, const double *factor, c
  * otherwise plain IEEE-754 (a zero divisor gives inf or NaN). */
 pq_status pq_factor_binary(pq_ctx *, const pq_batch *, const double *a, const double *b, int32_t op, double *out);
 
+/* ---- rank 3, continued: the common technical factors, Factor.moving_average / momentum / volatility / skewness / relative_strength
+ * (README.md:1423-1426, :1472-1477; README-only, decision D-21 in DESIGN.md section 2).  x: f64 [n_series][stride], usually a price; out:
+ * f64 [n_series][stride] on the same pitch.  Everything runs along the days of one symbol.  valid(j): 0 <= j and x[j] non-null and
+ * finite; r[j] = (x[j] - x[j-1]) / x[j-1] and d[j] = x[j] - x[j-1] where j-1 and j are valid; w = window; every sum starts at 0.0 and adds
+ * in ascending j.
+ *   op 0 mean:              valid(t-w+1 .. t): (sum of x[j]) / w
+ *   op 1 momentum:          valid(t-skip) and valid(t-skip-w): (a - b) / b, a = x[t-skip], b = x[t-skip-w]
+ *   op 2 volatility:        valid(t-w .. t) and r[t-w+1 .. t] finite, w >= 2: m = (sum r) / w, sqrt((sum (r-m)(r-m)) / (w-1))
+ *   op 3 skewness:          the same sample, w >= 3: e = r-m, m2 = (sum e e) / w, m3 = (sum (e e) e) / w, m3 / (m2 sqrt(m2)); NULL at m2 == 0
+ *   op 4 relative strength: valid(t-w .. t): G = sum of the d[j] > 0, L = sum of -d[j] over the d[j] < 0, (100 G) / (G + L); NULL at G + L == 0
+ * A row whose sample is incomplete is NULL, and so is a result that comes out NaN (+-inf passes).  1 <= window <= 1024 and at least the
+ * op's minimum; skip >= 0, and 0 except for momentum; anything else is PQ_ERR_ARG.  out must NOT overlap x (PQ_ERR_ARG): unlike the
+ * elementwise calls above, a workgroup reads a halo of days that another workgroup writes.  Ragged batches and suite recording are
+ * refused; n_series = 0 or len = 0 launches nothing.  No workspace. */
+#define PQ_FACTOR_ROLLING_MAX_WINDOW 1024
+/* op 0 mean, 1 momentum, 2 volatility, 3 skewness, 4 relative strength (decision D-21) */
+pq_status pq_factor_rolling(pq_ctx *, const pq_batch *, const double *x, int32_t op, int64_t window, int64_t skip, double *out);
+
 /* ---- suites: record many calls, replay them as a few chip-filling grids ----
  * One indicator over N symbols is only N/64 wavefronts -- far too few for 256 CUs -- but a DataFrame query asks
  * for many indicators at once (df.with_columns([...]) in the reference; Polars then calls the plugin once per

@@ -135,6 +135,8 @@ def lib() -> C.CDLL:
         L.pq_ma_stack_signals.argtypes = [vp, C.POINTER(Batch), vp, C.c_int32, vp, vp]
         L.pq_factor_ic.restype = C.c_int32
         L.pq_factor_ic.argtypes = [vp, C.POINTER(Batch), vp, vp, C.c_int32, vp, vp]
+        L.pq_factor_rolling.restype = C.c_int32
+        L.pq_factor_rolling.argtypes = [vp, C.POINTER(Batch), vp, C.c_int32, C.c_int64, C.c_int64, vp]
         L.pq_rolling_ic.restype = C.c_int32
         L.pq_rolling_ic.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp]
         L.pq_backtest_leveraged.restype = C.c_int32

@@ -914,6 +914,30 @@ def factor_binary(a, b, op: int = 0):
     return _build_call("pq_factor_binary", [a, b], lambda bb, dev: (C.c_int32(op),))
 
 
+ROLLING_OPS = {"mean": 0, "momentum": 1, "volatility": 2, "skewness": 3, "relative_strength": 4}   # pq_factor_rolling's op codes
+ROLLING_MIN_WINDOW = {0: 1, 1: 1, 2: 2, 3: 3, 4: 1}            # per op code
+ROLLING_MAX_WINDOW = 1024                                      # PQ_FACTOR_ROLLING_MAX_WINDOW
+
+
+def factor_rolling(x, op: int, window: int, skip: int = 0):
+    """D-21: one rolling technical factor along the days of every symbol of an [N, T] column -> device tensor [N, T], NULL where the
+    row's sample is incomplete or the result is NaN.  op (ROLLING_OPS) 0: mean of x over the last `window` days, 1: momentum
+    (x[t-skip] - x[t-skip-window]) / x[t-skip-window], 2: sample std and 3: population skewness of the last `window` period-1 simple
+    returns, 4: relative strength 100 G / (G + L) over the last `window` differences.  1 <= window <= 1024 and at least
+    ROLLING_MIN_WINDOW[op]; skip >= 0 is momentum's alone."""
+    if isinstance(op, bool) or op not in ROLLING_MIN_WINDOW:
+        raise ValueError(f"op must be one of {sorted(ROLLING_OPS.values())} (ROLLING_OPS), not {op!r}")
+    for nm, v in (("window", window), ("skip", skip)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{nm} must be an integer, not {v!r}")
+    if not ROLLING_MIN_WINDOW[op] <= window <= ROLLING_MAX_WINDOW:
+        raise ValueError(f"window must be in {ROLLING_MIN_WINDOW[op]}..{ROLLING_MAX_WINDOW} for op {op}, not {window!r}")
+    if skip < 0 or (skip != 0 and op != ROLLING_OPS["momentum"]):
+        raise ValueError(f"skip must be >= 0, and 0 except for momentum, not {skip!r}")
+    _build_shapes(("factor",), (x,))
+    return _build_call("pq_factor_rolling", [x], lambda b, dev: (C.c_int32(int(op)), C.c_int64(int(window)), C.c_int64(int(skip))))
+
+
 def split_periods(T: int, n_splits: int):
     """numpy.array_split(range(T), n_splits) as inclusive (start, end) day indices -> two int64 numpy arrays; 1 <= n_splits <= T"""
     if isinstance(n_splits, bool) or not isinstance(n_splits, (int, np.integer)) or not 1 <= n_splits <= T:

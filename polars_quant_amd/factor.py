@@ -4,7 +4,8 @@ them (README.md:1429-1430, :1480-1482, :1626-1634): per-day cross-sectional IC, 
 (decision D-12, oracle/backtest.c), and quantile sorts, long-short legs, turnover, coverage and IC statistics (decision D-15), and the
 regressions and significance tests ic_test / factor_return / fama_macbeth / time_series_regression (decision D-17), and the robustness
 tests ic_decay / subsample_test / subgroup_test (decision D-18), and the multi-factor orthogonalization / neutralization Factor().clean
-(decision D-19).  README-only in the reference.  Inputs are [N, T] arrays (symbol-major, like every other column of this package): the
+(decision D-19).  The common technical factors moving_average / momentum / volatility / skewness / relative_strength
+(README.md:1423-1426, :1472-1477; decision D-21) roll along the days of every symbol.  README-only in the reference.  Inputs are [N, T] arrays (symbol-major, like every other column of this package): the
 factor and the forward return of every symbol on every day.
 `clean` is the README's factor cleaning step that comes before the evaluation (decision D-16).
 """
@@ -48,6 +49,32 @@ class Factor:
         """per day over the non-null finite symbols: the average rank in 1 .. n (ties share the mean of their positions; -0 ties with
         +0), ascending=False: n + 1 - rank, pct=True: divided by n; NULL outside the day's sample"""
         return _api.factor_rank(factor, _api.RANK_MODES["pct" if pct else "rank"], not ascending)
+
+    # ---- D-21: the common technical factors (README.md:1423-1426, :1472-1477), along the days of every symbol; a row without its full
+    # sample is NULL, so is a result that comes out NaN; 1 <= window <= 1024
+    def moving_average(self, factor, window=20):
+        """-> the mean of the last `window` days, NULL unless all of them are non-null and finite"""
+        return _api.factor_rolling(factor, _api.ROLLING_OPS["mean"], window)
+
+    def momentum(self, factor, window=20, skip=0):
+        """-> (a - b) / b with a = x[t - skip], b = x[t - skip - window] (skip=21, window=231: the usual "12-1" form); NULL unless both
+        are non-null and finite; returns(x, period=window) itself at skip=0, a zero base gives inf"""
+        return _api.factor_rolling(factor, _api.ROLLING_OPS["momentum"], window, skip)
+
+    def volatility(self, factor, window=20):
+        """-> the sample std (ddof 1) of the last `window` period-1 simple returns (window >= 2, not annualised); NULL unless the
+        window + 1 prices are non-null and finite and every return is finite; 0.0 over a constant stretch"""
+        return _api.factor_rolling(factor, _api.ROLLING_OPS["volatility"], window)
+
+    def skewness(self, factor, window=20):
+        """-> the population skewness m3 / m2^1.5 (scipy.stats.skew(bias=True)) of the last `window` period-1 simple returns
+        (window >= 3), on volatility's sample; NULL where m2 == 0 (a constant stretch)"""
+        return _api.factor_rolling(factor, _api.ROLLING_OPS["skewness"], window)
+
+    def relative_strength(self, factor, window=14):
+        """-> 100 G / (G + L) over the last `window` day-to-day differences, G the sum of the rises and L of the falls (the
+        simple-average form, no warm-up memory); NULL unless the window + 1 values are non-null and finite, and where G + L == 0"""
+        return _api.factor_rolling(factor, _api.ROLLING_OPS["relative_strength"], window)
 
     def ic(self, factor, next_return):
         """-> (ic [T], n_valid [T]): Pearson correlation across symbols, per day"""
