@@ -421,6 +421,35 @@ pq_status pq_backtest_leveraged(pq_ctx *, const pq_batch *, const double *price,
 pq_status pq_portfolio_metrics(pq_ctx *, const pq_batch *, const double *total_value, double initial_total,
                                const double *benchmark, double *out);
 
+/* ---- rank 1, continued: the statistics report of `Backtest` (README.md:511-548, :627-640; README-only, decision D-22 in DESIGN.md).
+ * One row of PQ_REPORT_COLS f64 per symbol (names: _spec.REPORT_COLS), from its total_value row [n_series][stride], the initial capital,
+ * the first min(trade_count, max_trades) records of pq_backtest_leveraged and ONE shared benchmark series (or NULL):
+ *   0-14  the curve: final value, P&L, total / annualized / mean daily return, max drawdown and its longest run of under-water days,
+ *         daily / annualized volatility, Sharpe, Sortino, Calmar, positive / negative days, daily win rate
+ *   15-37 the trades: counts, win rate, gross profit / loss, profit factor, average / largest win and loss, holding days, the longest
+ *         winning / losing streak, turnover, fees (the engine's own, bit for bit), fee ratio, average trade amount, capital use,
+ *         margin calls
+ *   38-44 the benchmark: its return, excess return, daily alpha, beta, information ratio, days ahead and their rate
+ *   45-47 carriers of the portfolio row: hold days of winners, of losers, and the summed entry amount
+ * Sums run in ONE order: 64 partials (partial k adds x[k], x[k + 64], ... from +0.0), folded p[k] += p[k + s], s = 32 .. 1.  A count is
+ * stored as f64, a missing value (a ratio over 0, an empty maximum) is PQ_NULL_BITS.  A NULL or non-finite total_value makes 0-14 and
+ * 38-44 NULL, a NULL or non-finite benchmark 38-44; trade_count > max_trades (records cut short) or no record arrays make 16-37 NULL;
+ * without trade_count 15 is NULL too.  The seven record arrays are all passed or all NULL; params is read for commission_rate and
+ * min_commission.  initial_capital must be positive and finite.  Ragged batches: PQ_ERR_UNSUPPORTED. */
+#define PQ_REPORT_COLS 48
+pq_status pq_backtest_report(pq_ctx *, const pq_batch *, const double *total_value, double initial_capital, const double *benchmark,
+                             const pq_lev_params *params, int32_t max_trades, const int32_t *trade_count, const int32_t *entry_day,
+                             const int32_t *exit_day, const double *entry_price, const double *exit_price, const double *quantity,
+                             const double *pnl, const int32_t *reason, double *report);
+/* The portfolio row (D-22) from the [n_symbols][PQ_REPORT_COLS] rows: 0-14 and 38-44 are copied from curve_row, the report row of the
+ * portfolio_value series (pq_portfolio_metrics column 0 with initial_capital * n_symbols as its capital); trade counts are integer sums,
+ * the trade sums are added in D-10's order (blocks of 256 symbols, ascending), the ratios are formed from the sums (capital use over the
+ * per-symbol initial_capital), extrema and streaks are the extremes over the symbols; 45 / 46: index of the best / worst symbol by total
+ * return (ties: the lowest index; a NULL return is skipped), 47: symbols with total_trades > 0.  One symbol with NULL trade columns
+ * makes 16-37 NULL.  out: PQ_REPORT_COLS values. */
+pq_status pq_report_portfolio(pq_ctx *, int64_t n_symbols, const double *report, const double *curve_row, double initial_capital,
+                              double *out);
+
 /* ---- cross-sectional factor evaluation, Factor.ic / rank_ic / rolling_ic (README.md:1429-1430,
  * :1480-1482, :1626-1634; README-only, decision D-12 in oracle/backtest.c).  factor / fwd_return: [n_series][stride];
  * per day the cross-section = symbols where both values are non-null and finite.  method 0: Pearson IC (sums over

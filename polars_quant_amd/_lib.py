@@ -143,6 +143,10 @@ def lib() -> C.CDLL:
         L.pq_backtest_leveraged.argtypes = [vp, C.POINTER(Batch), vp, vp, vp, vp, C.POINTER(LevParams), vp, vp, vp, C.c_int32] + [vp] * 10
         L.pq_portfolio_metrics.restype = C.c_int32
         L.pq_portfolio_metrics.argtypes = [vp, C.POINTER(Batch), vp, C.c_double, vp, vp]
+        L.pq_backtest_report.restype = C.c_int32
+        L.pq_backtest_report.argtypes = [vp, C.POINTER(Batch), vp, C.c_double, vp, C.POINTER(LevParams), C.c_int32] + [vp] * 9
+        L.pq_report_portfolio.restype = C.c_int32
+        L.pq_report_portfolio.argtypes = [vp, C.c_int64, vp, vp, C.c_double, vp]
         L.pq_recommended_stride.restype = C.c_int64
         L.pq_recommended_stride.argtypes = [C.c_int64]
         L.pq_layout_check.restype = C.c_int32

@@ -128,5 +128,35 @@ BT_DEFAULTS = dict(initial_capital=100000.0, buy_slippage=0.0, sell_slippage=0.0
 LEV_DEFAULTS = dict(initial_capital=100000.0, position_size=1.0, leverage=1.0, margin_call_threshold=0.3,
                     interest_rate=0.06, commission_rate=0.0003, min_commission=5.0, slippage=0.0)
 TRADE_FIELDS = ("entry_day", "exit_day", "entry_price", "exit_price", "quantity", "pnl", "pnl_pct", "reason")
+# pq_backtest_report / pq_report_portfolio (decision D-22): the PQ_REPORT_COLS columns in order.  The last three carry the portfolio
+# row's meaning; in a symbol row they hold the hold days of winners, of losers, and the summed entry amount.
+REPORT_COLS = ("final_value", "total_pnl", "total_return", "annualized_return", "mean_daily_return", "max_drawdown",
+               "max_drawdown_days", "daily_volatility", "annualized_volatility", "sharpe", "sortino", "calmar", "positive_days",
+               "negative_days", "daily_win_rate",
+               "total_trades", "winning_trades", "losing_trades", "win_rate", "gross_profit", "gross_loss", "profit_factor", "avg_win",
+               "avg_loss", "max_win", "max_loss", "avg_hold_win", "avg_hold_loss", "avg_hold", "total_hold_days",
+               "max_consecutive_wins", "max_consecutive_losses", "turnover", "total_fees", "fee_ratio", "avg_trade_amount",
+               "capital_use", "margin_calls",
+               "benchmark_return", "excess_return", "alpha_daily", "beta", "information_ratio", "days_ahead", "ahead_rate",
+               "best_symbol_index", "worst_symbol_index", "active_symbols")
+REPORT_SYMBOL_COLS = 45  # the columns that mean the same in a symbol row and in the portfolio row
+REPORT_TRADE_FIELDS = ("entry_day", "exit_day", "entry_price", "exit_price", "quantity", "pnl", "reason")  # pq_backtest_report's records
+# the thirteen headings of summary() (README.md:517-533) and the columns printed under each
+REPORT_SECTIONS = (
+    ("basic information", ("final_value", "total_pnl")),
+    ("return metrics", ("total_return", "annualized_return", "mean_daily_return")),
+    ("risk metrics", ("max_drawdown", "max_drawdown_days", "daily_volatility", "annualized_volatility")),
+    ("risk-adjusted return", ("sharpe", "sortino", "calmar")),
+    ("trade statistics", ("total_trades", "winning_trades", "losing_trades", "win_rate", "profit_factor")),
+    ("profit analysis", ("gross_profit", "avg_win", "max_win", "avg_hold_win")),
+    ("loss analysis", ("gross_loss", "avg_loss", "max_loss", "avg_hold_loss")),
+    ("holding analysis", ("avg_hold", "total_hold_days", "max_consecutive_wins", "max_consecutive_losses", "margin_calls")),
+    ("trading costs", ("turnover", "total_fees", "fee_ratio")),
+    ("capital usage", ("avg_trade_amount", "capital_use")),
+    ("daily return analysis", ("positive_days", "negative_days", "daily_win_rate")),
+    ("symbol dimension", ()),
+    ("benchmark comparison", ("benchmark_return", "excess_return", "alpha_daily", "beta", "information_ratio", "days_ahead",
+                              "ahead_rate")),
+)
 PORTFOLIO_COLS = ("portfolio_value", "daily_pnl", "daily_return_pct", "cumulative_pnl", "cumulative_return_pct",
                   "benchmark_return_pct", "alpha_pct", "relative_return_pct", "beta")

@@ -1113,6 +1113,115 @@ def portfolio_metrics(total_value, initial_total: float, benchmark=None):
     return out
 
 
+def _rp_meta(x, what, ndim):
+    """shape and dtype kind of an array-like, without moving it to the device"""
+    shape = tuple(x.shape) if isinstance(x, torch.Tensor) else np.shape(x)
+    if len(shape) != ndim:
+        raise ValueError(f"{what} must have {ndim} dimension{'s' if ndim > 1 else ''}, got shape {shape}")
+    dt = x.dtype if isinstance(x, torch.Tensor) else np.asarray(x).dtype
+    if isinstance(dt, torch.dtype):
+        numeric = dt.is_floating_point or dt in (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8, torch.bool)
+    else:
+        numeric = dt.kind in "fiub"
+    if not numeric:
+        raise ValueError(f"{what} must be numeric, got {dt}")
+    return shape
+
+
+def _rp_numel(x, what):
+    shape = tuple(x.shape) if isinstance(x, torch.Tensor) else np.shape(x)
+    return int(np.prod(_rp_meta(x, what, len(shape))))
+
+
+def _rp_dev(x, dtype, dev=None):
+    t = x if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x)))
+    return t.to(device=dev if dev is not None else "cuda", dtype=dtype)
+
+
+def backtest_report(total_value, initial_capital: float, benchmark=None, trades=None, trade_count=None, max_trades: int = 0, **lev_params):
+    """The statistics report of `Backtest` (decision D-22): total_value [N, T], benchmark [T] or None, trades = {field: [N, max_trades]}
+    with the fields _spec.REPORT_TRADE_FIELDS (further fields are ignored) and trade_count [N], as backtest_leveraged returns them;
+    max_trades = 0 takes the records' width.  lev_params: the engine's commission_rate / min_commission (and the rest of its parameters).
+    -> device [N, 48] f64, columns _spec.REPORT_COLS; a missing value is NULL.  Every check raises ValueError before any device work."""
+    from ._lib import LevParams
+    from ._spec import LEV_DEFAULTS, REPORT_COLS, REPORT_TRADE_FIELDS
+    n, T = _rp_meta(total_value, "total_value", 2)
+    if T < 1:
+        raise ValueError("total_value needs at least one day")
+    c0 = float(initial_capital)
+    if not (c0 > 0.0 and np.isfinite(c0)):
+        raise ValueError("initial_capital must be positive and finite")
+    unknown = set(lev_params) - set(LEV_DEFAULTS)
+    if unknown:
+        raise ValueError(f"unknown parameters {sorted(unknown)}")
+    if benchmark is not None and _rp_numel(benchmark, "benchmark") != T:
+        raise ValueError("benchmark must be one series with as many rows as total_value")
+    width = 0
+    if trades is not None:
+        if trade_count is None:
+            raise ValueError("trades need trade_count")
+        missing = [k for k in REPORT_TRADE_FIELDS if k not in trades]
+        if missing:
+            raise ValueError(f"trades lack the fields {missing}")
+        shapes = {k: _rp_meta(trades[k], f"trades[{k!r}]", 2) for k in REPORT_TRADE_FIELDS}
+        if len(set(shapes.values())) != 1:
+            raise ValueError(f"the trade arrays must have one shape, got {shapes}")
+        rows, width = shapes["pnl"]
+        if rows != n:
+            raise ValueError(f"the trade arrays have {rows} rows for {n} symbols")
+        if int(max_trades) not in (0, width):
+            raise ValueError(f"max_trades = {max_trades} but the trade arrays are {width} wide")
+    elif int(max_trades) < 0:
+        raise ValueError("max_trades < 0")
+    if trade_count is not None and _rp_meta(trade_count, "trade_count", 1) != (n,):
+        raise ValueError(f"trade_count must have one entry per symbol ({n})")
+    _require_gpu()
+    prm = LevParams(**{**LEV_DEFAULTS, **lev_params})
+    tv = _rp_dev(total_value, torch.float64)
+    if tv.stride(1) != 1 or tv.stride(0) < T:
+        tv = tv.contiguous()
+    dev = tv.device
+    out = torch.empty((n, len(REPORT_COLS)), dtype=torch.float64, device=dev)
+    if n == 0:
+        return out
+    bm = _rp_dev(benchmark, torch.float64, dev).reshape(-1).contiguous() if benchmark is not None else None
+    cnt = _rp_dev(trade_count, torch.int32, dev).contiguous() if trade_count is not None else None
+    rec = [None] * len(REPORT_TRADE_FIELDS)
+    if trades is not None and width > 0:
+        rec = [_rp_dev(trades[k], torch.int32 if k in ("entry_day", "exit_day", "reason") else torch.float64, dev).contiguous()
+               for k in REPORT_TRADE_FIELDS]
+    vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
+    b = Batch(n, T, tv.stride(0) if n > 1 else T)
+    with torch.cuda.device(dev):
+        check(lib().pq_backtest_report(ctx(dev.index), C.byref(b), vp(tv), c0, vp(bm), C.byref(prm), int(width), vp(cnt),
+                                       *[vp(t) for t in rec], vp(out)))
+    return out
+
+
+def report_portfolio(report, curve_row, initial_capital: float):
+    """The portfolio row of the report (D-22): report = backtest_report's [N, 48] rows, curve_row = the [48] report row of the
+    portfolio_value series on N times the capital, initial_capital = one symbol's -> device [48] f64"""
+    from ._spec import REPORT_COLS
+    ncol = len(REPORT_COLS)
+    shape = _rp_meta(report, "report", 2)
+    if shape[1] != ncol or shape[0] < 1:
+        raise ValueError(f"report must be [N >= 1, {ncol}], got {shape}")
+    if _rp_numel(curve_row, "curve_row") != ncol:
+        raise ValueError(f"curve_row must hold {ncol} values")
+    c0 = float(initial_capital)
+    if not (c0 > 0.0 and np.isfinite(c0)):
+        raise ValueError("initial_capital must be positive and finite")
+    _require_gpu()
+    rep = _rp_dev(report, torch.float64).contiguous()
+    dev = rep.device
+    cur = _rp_dev(curve_row, torch.float64, dev).reshape(-1).contiguous()
+    out = torch.zeros(ncol, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().pq_report_portfolio(ctx(dev.index), shape[0], C.c_void_p(rep.data_ptr()), C.c_void_p(cur.data_ptr()), c0,
+                                        C.c_void_p(out.data_ptr())))
+    return out
+
+
 def macd_cross_signals(close, fastperiod=12, slowperiod=26, signalperiod=9):
     p, kind, squeeze = _to_device(close)
     p = p.contiguous()

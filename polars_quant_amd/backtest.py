@@ -7,9 +7,10 @@ symbol), in which case run() returns batched curves and a list of N summary dict
 from __future__ import annotations
 
 import numpy as np
+import torch
 
 from . import api as _api
-from ._spec import BT_DEFAULTS, PORTFOLIO_COLS, SUMMARY_KEYS, TRADE_FIELDS
+from ._spec import BT_DEFAULTS, PORTFOLIO_COLS, REPORT_COLS, REPORT_SECTIONS, REPORT_SYMBOL_COLS, SUMMARY_KEYS, TRADE_FIELDS
 
 
 class VectorizedBacktester:
@@ -79,7 +80,7 @@ class Backtest:
                            margin_call_threshold=margin_call_threshold, interest_rate=interest_rate,
                            commission_rate=commission_rate, min_commission=min_commission, slippage=slippage)
         self.max_trades = max_trades
-        self._r = None
+        self._r = self._stats = None
 
     @staticmethod
     def _table(cols: dict):
@@ -90,8 +91,14 @@ class Backtest:
             return cols
 
     def run(self) -> None:
-        r = _api.backtest_leveraged(self._price, self._buy, self._sell, self._bench, self.max_trades, **self.params)
-        self._metrics = _api.portfolio_metrics(r["total_value"], self.params["initial_capital"] * len(self.symbols), self._bench)
+        _api._require_gpu()
+        bench = None if self._bench is None else torch.from_numpy(self._bench).cuda()   # one upload for the run and the report
+        r = _api.backtest_leveraged(self._price, self._buy, self._sell, bench, self.max_trades, **self.params)
+        self._metrics = _api.portfolio_metrics(r["total_value"], self.params["initial_capital"] * len(self.symbols), bench)
+        # what the statistics report reads stays on the device (D-22)
+        self._dev = dict(total_value=r["total_value"], trade_count=r["trade_count"], trades=r["trades"], benchmark=bench,
+                         portfolio_value=self._metrics[:, 0].contiguous())
+        self._stats = None
         self._r = {k: (v.cpu().numpy() if hasattr(v, "cpu") else v) for k, v in r.items() if k != "trades"}
         self._r["trades"] = {k: v.cpu().numpy() for k, v in r["trades"].items()}
         self._metrics = self._metrics.cpu().numpy()
@@ -146,13 +153,57 @@ class Backtest:
             cols.update({"benchmark_return_pct": m[:, 5], "alpha_pct": m[:, 6], "relative_return_pct": m[:, 7]})
         return self._table(cols)
 
+    def _report(self):
+        """(symbol rows [N, 48], portfolio row [48]) on the host, NULL as nan: pq_backtest_report on the device tensors run() kept,
+        once more on the portfolio_value series, and pq_report_portfolio; computed on first use"""
+        self._need()
+        if self._stats is None:
+            d, c0, n = self._dev, self.params["initial_capital"], len(self.symbols)
+            prm = {k: v for k, v in self.params.items() if k != "initial_capital"}
+            rep = _api.backtest_report(d["total_value"], c0, d["benchmark"], d["trades"] if self.max_trades > 0 else None,
+                                       d["trade_count"], **prm)
+            curve = _api.backtest_report(d["portfolio_value"].reshape(1, -1), c0 * n, d["benchmark"])
+            port = _api.report_portfolio(rep, curve[0], c0)
+            self._stats = tuple(torch.where(torch.isnan(t), float("nan"), t).cpu().numpy() for t in (rep, port))
+        return self._stats
+
+    def statistics(self) -> dict:
+        """README.md:517-533 as values: {"portfolio": {name: value}, "symbols": {name: array [N]}, "best_symbol", "worst_symbol"};
+        names = _spec.REPORT_COLS, a missing value is nan"""
+        rep, port = self._report()
+        pick = lambda v: None if np.isnan(v) else self.symbols[int(v)]
+        return {"portfolio": {k: float(v) for k, v in zip(REPORT_COLS, port)},
+                "symbols": {k: rep[:, j].copy() for j, k in enumerate(REPORT_COLS[:REPORT_SYMBOL_COLS])},
+                "best_symbol": pick(port[REPORT_COLS.index("best_symbol_index")]),
+                "worst_symbol": pick(port[REPORT_COLS.index("worst_symbol_index")])}
+
+    def get_stock_statistics(self, symbol) -> dict:
+        rep, _ = self._report()
+        return {k: float(v) for k, v in zip(REPORT_COLS[:REPORT_SYMBOL_COLS], rep[self.symbols.index(symbol)])}
+
+    def _report_lines(self, values: dict, dimension: list) -> list:
+        lines = []
+        for k, (title, names) in enumerate(REPORT_SECTIONS, 1):
+            if title == "benchmark comparison" and self._bench is None:
+                continue
+            lines.append(f"[{k}] {title}")
+            lines += [f"  {nm}: {values[nm]:.6g}" for nm in names]
+            if title == "symbol dimension":
+                lines += dimension
+        return lines
+
     def get_stock_summary(self, symbol) -> str:
         self._need()
         i = self.symbols.index(symbol)
-        return "\n".join(f"{k}: {v:.6g}" for k, v in zip(SUMMARY_KEYS, self._r["summary"][i]))
+        head = [f"{k}: {v:.6g}" for k, v in zip(SUMMARY_KEYS, self._r["summary"][i])]
+        return "\n".join(head + self._report_lines(self.get_stock_statistics(symbol), [f"  symbol: {symbol}"]))
 
     def summary(self) -> None:
         self._need()
         m = self._metrics
         print(f"symbols: {len(self.symbols)}  days: {len(self.dates)}  trades: {int(self._r['trade_count'].sum())}")
         print(f"final portfolio value: {m[-1, 0]:.2f}  cumulative return: {m[-1, 4]:.4f} %")
+        st = self.statistics()
+        dim = [f"  active_symbols: {st['portfolio']['active_symbols']:.6g}", f"  best_symbol: {st['best_symbol']}",
+               f"  worst_symbol: {st['worst_symbol']}"]
+        print("\n".join(self._report_lines(st["portfolio"], dim)))
