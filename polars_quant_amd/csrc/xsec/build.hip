@@ -3,9 +3,8 @@
 //
 // Columns are symbol-major [n_series][stride]; a day's cross-section is a strided column.  Every output is a full [n_series][stride] f64
 // column, NULL outside the day's sample.
-//  rank family: a tiled transpose writes day-major keys (the factor where it is non-null and finite, +0 for -0, else +inf) and counts n
-//               per day; each day's row is sorted (LDS bitonic up to XS_LDS_MAX symbols, rocPRIM's segmented radix sort above); every
-//               symbol finds the tie run [a, b) of its own key by two binary searches and overwrites its key by the finished value (rank,
+//  rank family: D-15's day-sort stage (xsec_dev.h, daysort.hip) with the key "the factor where it is non-null and finite, +0 for -0";
+//               every symbol finds the tie run [a, b) of its own key (xs_tie_run) and overwrites its key by the finished value (rank,
 //               reversed rank, pct or mid-rank position), still day-major; a second tiled transpose brings the values symbol-major, so the
 //               final stores run along days, 256 contiguous bytes per half-wave.
 //  minmax:      one thread per (day, block of 256 symbols), consecutive threads on consecutive days (coalesced), takes the block's min
@@ -16,7 +15,6 @@
 //  ratio, diff: one elementwise kernel with an op code, rows along days.
 // The zscore of Factor.normalize is pq_factor_clean(standardize = 1) itself (clean.hip), not restated here.
 #include "xsec_dev.h"
-#include <rocprim/rocprim.hpp>
 
 namespace {
 
@@ -26,46 +24,14 @@ enum BdRank { BD_RANK = 0, BD_PCT = 1, BD_MID = 2 };
 enum BdOp { BD_RATIO = 0, BD_DIFF = 1, BD_RELDIFF = 2 };
 
 // ---------------------------------------------------------------- rank family
-// [n][stride] factor -> day-major [len][n] keys (the factor where it is valid, +0 for -0, else +inf), n per day
-__global__ __launch_bounds__(256) void bd_prep_kernel(const double *f, Dims d, double *key, int32_t *n_valid) {
-    __shared__ double tile[32][33];
-    __shared__ int cnt[32];
-    const int64_t t0 = (int64_t)blockIdx.x * 32, s0 = (int64_t)blockIdx.y * 32;
-    const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5; // 32 x 8
-    if (threadIdx.x < 32) cnt[threadIdx.x] = 0;
-    for (int i = ly; i < 32; i += 8) { // rows = symbols, lanes along days (coalesced reads)
-        const int64_t s = s0 + i, t = t0 + lx;
-        double k = xs_inf();
-        if (s < d.n && t < d.len) {
-            const double x = f[s * d.stride + t];
-            if (xs_valid(x)) k = x == 0.0 ? 0.0 : x;
-        }
-        tile[i][lx] = k;
+// the key of xs_prep_kernel: the factor where it is valid, +0 for -0
+struct BdKey {
+    const double *f;
+    __device__ double operator()(int64_t o) const {
+        const double x = f[o];
+        return xs_valid(x) ? (x == 0.0 ? 0.0 : x) : xs_inf();
     }
-    __syncthreads();
-    for (int i = ly; i < 32; i += 8) { // rows = days, lanes along symbols (coalesced writes)
-        const int64_t t = t0 + i, s = s0 + lx;
-        const double k = tile[lx][i];
-        if (t < d.len && s < d.n) {
-            key[t * d.n + s] = k;
-            if (k != xs_inf()) atomicAdd(&cnt[i], 1);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 32 && t0 + threadIdx.x < d.len && cnt[threadIdx.x]) atomicAdd(&n_valid[t0 + threadIdx.x], cnt[threadIdx.x]);
-}
-
-// a + b for the tie run [a, b) of `key` in the ascending row S[0 .. nv) (key is one of its entries; PAD: an LDS row indexed through
-// xs_phys): two binary searches, so a discrete factor's long runs of equal keys cost O(log nv) per symbol
-template <bool PAD> __device__ __forceinline__ int64_t bd_run(const double *S, int nv, double key) {
-    auto at = [&](int i) { return S[PAD ? xs_phys(i) : i]; };
-    int lo = 0, hi = nv;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (at(mid) < key) lo = mid + 1; else hi = mid; }
-    const int a = lo;
-    lo = a + 1; hi = nv;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (at(mid) <= key) lo = mid + 1; else hi = mid; }
-    return (int64_t)a + (int64_t)lo;
-}
+};
 
 // m = a + b -> the average rank ((a + 1) + b) / 2 (a half-integer: exact), reversed as n + 1 - rank (exact), then one division
 __device__ __forceinline__ double bd_value(int64_t m, int nv, int mode, int desc) {
@@ -87,12 +53,10 @@ __global__ __launch_bounds__(1024) void bd_rank_lds_kernel(double *key, const in
         for (int s = tid; s < n; s += nthr) row[s] = pq_null();
         return;
     }
-    for (int i = tid; i < P; i += nthr) S[xs_phys(i)] = i < n ? row[i] : xs_inf();
-    __syncthreads();
-    xs_sort_lds(S, P, (int)n, tid, nthr);
+    xs_load_sort_row(S, row, n, P, tid, nthr);
     for (int s = tid; s < n; s += nthr) {
         const double k = row[s];
-        row[s] = k == xs_inf() ? pq_null() : bd_value(bd_run<true>(S, nv, k), nv, mode, desc);
+        row[s] = k == xs_inf() ? pq_null() : bd_value(xs_tie_run(XsRow<true>{S}, nv, k), nv, mode, desc);
     }
 }
 
@@ -105,7 +69,7 @@ __global__ __launch_bounds__(256) void bd_rank_sorted_kernel(double *key, const 
     const int nv = n_valid[t];
     for (int64_t s = threadIdx.x; s < n; s += 256) {
         const double k = row[s];
-        row[s] = k == xs_inf() ? pq_null() : bd_value(bd_run<false>(S, nv, k), nv, mode, desc);
+        row[s] = k == xs_inf() ? pq_null() : bd_value(xs_tie_run(XsRow<false>{S}, nv, k), nv, mode, desc);
     }
 }
 
@@ -278,41 +242,27 @@ pq_status pq_factor_rank(pq_ctx *ctx, const pq_batch *b, const double *factor, i
     if (b->len == 0 || b->n_series == 0) return PQ_OK;
     const Dims d = dims_of(b);
     const size_t cells = (size_t)d.len * (size_t)d.n, len = (size_t)d.len;
-    const bool wide = d.n > XS_LDS_MAX;
-    if (wide) {
-        PQ_REQUIRE(d.n <= 100000, "pq_factor_rank supports at most 100000 series");
-        PQ_REQUIRE(cells < (1ull << 32), "pq_factor_rank needs n_series * len < 2^32 above 16384 series");
-    }
-    size_t tmp_bytes = 0;
-    if (wide)
-        PQ_HIP_TRY(rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes, (double *)nullptr, (double *)nullptr, (unsigned)cells,
-                                                      (unsigned)d.len, (unsigned *)nullptr, (unsigned *)nullptr, 0, 64, ctx->stream));
+    XsDaySort plan;
+    PQ_TRY(xs_day_sort_plan(ctx, d, "pq_factor_rank", &plan));
     // workspace: keys, then values (f64, day-major) | n per day (i32) | wide: sorted keys (f64), offsets (u32), rocPRIM temp
-    const size_t o_cnt = xs_al(cells * 8), o_srt = o_cnt + xs_al(len * 4), o_off = o_srt + (wide ? xs_al(cells * 8) : 0),
-                 o_tmp = o_off + (wide ? xs_al((len + 1) * 4) : 0), total = o_tmp + (wide ? xs_al(tmp_bytes) : 0);
-    PQ_TRY(pq_ws_reserve(ctx, total));
+    const size_t o_cnt = xs_al(cells * 8), o_srt = o_cnt + xs_al(len * 4);
+    PQ_TRY(pq_ws_reserve(ctx, o_srt + plan.bytes));
     unsigned char *ws = (unsigned char *)ctx->ws;
     double *key = (double *)ws;
     int32_t *nv = (int32_t *)(ws + o_cnt);
     hipStream_t st = ctx->stream;
     const dim3 gt((unsigned)((d.len + 31) / 32), (unsigned)((d.n + 31) / 32));
     PQ_HIP_TRY(hipMemsetAsync(nv, 0, len * 4, st));
-    hipLaunchKernelGGL(bd_prep_kernel, gt, dim3(256), 0, st, factor, d, key, nv);
-    if (!wide) {
-        int P = 16;
-        while (P < d.n) P <<= 1;
-        const int nthr = P / 16 < 64 ? 64 : (P / 16 > 1024 ? 1024 : P / 16);
-        const size_t lds = (size_t)(P + P / 16) * 8;
-        PQ_HIP_TRY(hipFuncSetAttribute((const void *)bd_rank_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(bd_rank_lds_kernel, dim3((unsigned)d.len), dim3(nthr), lds, st, key, (const int32_t *)nv, d.n, P, mode, descending);
+    hipLaunchKernelGGL(xs_prep_kernel<BdKey>, gt, dim3(256), 0, st, BdKey{factor}, d, key, nv);
+    if (!plan.wide) {
+        const XsLds L = xs_lds_shape(d.n);
+        PQ_HIP_TRY(hipFuncSetAttribute((const void *)bd_rank_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.bytes));
+        hipLaunchKernelGGL(bd_rank_lds_kernel, dim3((unsigned)d.len), dim3(L.nthr), L.bytes, st, key, (const int32_t *)nv, d.n, L.P, mode,
+                           descending);
     } else {
-        double *srt = (double *)(ws + o_srt);
-        unsigned *off = (unsigned *)(ws + o_off);
-        hipLaunchKernelGGL(xs_offsets_kernel, dim3((unsigned)((d.len + 256) / 256)), dim3(256), 0, st, off, d.len, d.n);
-        PQ_HIP_TRY(rocprim::segmented_radix_sort_keys(ws + o_tmp, tmp_bytes, key, srt, (unsigned)cells, (unsigned)d.len, off, off + 1, 0, 64,
-                                                      st));
-        hipLaunchKernelGGL(bd_rank_sorted_kernel, dim3((unsigned)d.len), dim3(256), 0, st, key, (const double *)srt, (const int32_t *)nv, d.n,
-                           mode, descending);
+        const double *srt;
+        PQ_TRY(xs_day_sort_wide(ctx, d, plan, ws + o_srt, key, &srt));
+        hipLaunchKernelGGL(bd_rank_sorted_kernel, dim3((unsigned)d.len), dim3(256), 0, st, key, srt, (const int32_t *)nv, d.n, mode, descending);
     }
     hipLaunchKernelGGL(bd_transpose_kernel, gt, dim3(256), 0, st, (const double *)key, d.n, d.len, out, d.stride);
     PQ_HIP_TRY(hipGetLastError());

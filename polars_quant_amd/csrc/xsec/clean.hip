@@ -3,9 +3,8 @@
 //
 // Columns are symbol-major [n_series][stride]; a day's cross-section is a strided column.  Every step is a per-day statistic of the
 // step before it, so the work is a chain of passes over the inputs; no intermediate [N, T] column is written.
-//  1. bounds:   mad / percentile: a tiled transpose writes day-major keys (the factor where the symbol is in the cross-section, +inf
-//               elsewhere, -0 read as +0) and counts n per day; each day's row is sorted (LDS bitonic up to XS_LDS_MAX symbols, rocPRIM's
-//               segmented radix sort above) and one thread reads the clip bounds off it.  MAD needs no second sort: the deviations
+//  1. bounds:   mad / percentile: D-15's day-sort stage (xsec_dev.h, daysort.hip) with the key "the factor where the symbol is in the
+//               cross-section, -0 read as +0"; one thread reads the clip bounds off the sorted row.  MAD needs no second sort: the deviations
 //               |S[i] - med| are two ascending runs (leftwards from the median and rightwards from it), and the k-th smallest of two
 //               sorted runs is a binary search.  sigma: two blocked passes (mean, then squared deviations).
 //  2. passes:   one thread per (day, block of 256 symbols), consecutive threads on consecutive days (coalesced); each recomputes the
@@ -15,7 +14,6 @@
 //               writes the next per-day parameters.
 //  4. write:    the pass body once more, writing the cleaned value (NULL outside the cross-section and on dead days) symbol-major.
 #include "xsec_dev.h"
-#include <rocprim/rocprim.hpp>
 
 namespace {
 
@@ -64,36 +62,14 @@ __device__ __forceinline__ double cl_clip(double x, double lo, double hi) {
     return y > hi ? hi : y;
 }
 
-// [n][stride] inputs -> day-major [len][n] keys (the factor where the symbol is in the cross-section, +0 for -0, else +inf), n per day
-__global__ __launch_bounds__(256) void cl_prep_kernel(ClIn in, double *key, int32_t *n_valid) {
-    __shared__ double tile[32][33];
-    __shared__ int cnt[32];
-    const Dims d = in.d;
-    const int64_t t0 = (int64_t)blockIdx.x * 32, s0 = (int64_t)blockIdx.y * 32;
-    const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5; // 32 x 8
-    if (threadIdx.x < 32) cnt[threadIdx.x] = 0;
-    for (int i = ly; i < 32; i += 8) { // rows = symbols, lanes along days (coalesced reads)
-        const int64_t s = s0 + i, t = t0 + lx;
-        double k = xs_inf();
-        if (s < d.n && t < d.len) {
-            const int64_t o = s * d.stride + t;
-            const double x = in.f[o];
-            if (cl_member(in, x, in.z ? in.z[o] : 0.0, in.ind ? in.ind[o] : 0)) k = x == 0.0 ? 0.0 : x;
-        }
-        tile[i][lx] = k;
+// the key of xs_prep_kernel: the factor where the symbol is in the cross-section, +0 for -0
+struct ClKey {
+    ClIn in;
+    __device__ double operator()(int64_t o) const {
+        const double x = in.f[o];
+        return cl_member(in, x, in.z ? in.z[o] : 0.0, in.ind ? in.ind[o] : 0) ? (x == 0.0 ? 0.0 : x) : xs_inf();
     }
-    __syncthreads();
-    for (int i = ly; i < 32; i += 8) { // rows = days, lanes along symbols (coalesced writes)
-        const int64_t t = t0 + i, s = s0 + lx;
-        const double k = tile[lx][i];
-        if (t < d.len && s < d.n) {
-            key[t * d.n + s] = k;
-            if (k != xs_inf()) atomicAdd(&cnt[i], 1);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 32 && t0 + threadIdx.x < d.len && cnt[threadIdx.x]) atomicAdd(&n_valid[t0 + threadIdx.x], cnt[threadIdx.x]);
-}
+};
 
 struct ClWin {
     int32_t mode;
@@ -101,13 +77,8 @@ struct ClWin {
     double qlo, qhi;   // percentile: p, 1 - p
 };
 
-template <bool PAD> struct ClRow {
-    const double *S;
-    __device__ __forceinline__ double operator()(int i) const { return S[PAD ? xs_phys(i) : i]; }
-};
-
 // numpy's "linear" quantile, written in the D-16 order: h = q (n - 1), i = floor(h), g = h - i, S[i] + g (S[i+1] - S[i]) unless g == 0
-template <bool PAD> __device__ double cl_quantile(ClRow<PAD> S, int nv, double q) {
+template <bool PAD> __device__ double cl_quantile(XsRow<PAD> S, int nv, double q) {
     const double h = q * (double)(nv - 1);
     const int i = (int)floor(h);
     const double g = h - (double)i;
@@ -117,7 +88,7 @@ template <bool PAD> __device__ double cl_quantile(ClRow<PAD> S, int nv, double q
 // k-th smallest (from 0) of |S[i] - med| over S[0 .. nv): the run A (a = m entries, A[j] = |S[m-1-j] - med|) and the run B (B[j] =
 // |S[m+j] - med|) are both ascending (m = the first index with S[i] >= med).  Find the smallest i with A[i] >= B[k-i]: then the k + 1
 // smallest are A[0 .. i) and B[0 .. k+1-i), and the k-th is the larger of their last entries.
-template <bool PAD> __device__ double cl_dev_kth(ClRow<PAD> S, int nv, int m, double med, int k) {
+template <bool PAD> __device__ double cl_dev_kth(XsRow<PAD> S, int nv, int m, double med, int k) {
     const int a = m, b = nv - m;
     auto A = [&](int j) { return fabs(S(m - 1 - j) - med); };
     auto B = [&](int j) { return fabs(S(m + j) - med); };
@@ -131,12 +102,12 @@ template <bool PAD> __device__ double cl_dev_kth(ClRow<PAD> S, int nv, int m, do
     return x < y ? y : x;
 }
 
-template <bool PAD> __device__ double cl_median(ClRow<PAD> S, int nv) {
+template <bool PAD> __device__ double cl_median(XsRow<PAD> S, int nv) {
     return (nv & 1) ? S((nv - 1) / 2) : (S(nv / 2 - 1) + S(nv / 2)) * 0.5;
 }
 
 // clip bounds of one day from its ascending members S[0 .. nv)
-template <bool PAD> __device__ void cl_bounds(ClRow<PAD> S, int nv, const ClWin &w, double &lo, double &hi) {
+template <bool PAD> __device__ void cl_bounds(XsRow<PAD> S, int nv, const ClWin &w, double &lo, double &hi) {
     lo = -xs_inf(); hi = xs_inf();
     if (nv < 2) return;
     if (w.mode == CL_WIN_PCT) {
@@ -163,17 +134,15 @@ __global__ __launch_bounds__(1024) void cl_bounds_lds_kernel(const double *key, 
     const int tid = threadIdx.x, nthr = blockDim.x, nv = day.n[t];
     if (nv >= 2) { // uniform across the workgroup
         const double *row = key + t * n;
-        for (int i = tid; i < P; i += nthr) S[xs_phys(i)] = i < n ? row[i] : xs_inf();
-        __syncthreads();
-        xs_sort_lds(S, P, (int)n, tid, nthr);
+        xs_load_sort_row(S, row, n, P, tid, nthr);
     }
-    if (tid == 0) cl_bounds(ClRow<true>{S}, nv, w, day.lo[t], day.hi[t]);
+    if (tid == 0) cl_bounds(XsRow<true>{S}, nv, w, day.lo[t], day.hi[t]);
 }
 
 // n > XS_LDS_MAX: the day-major rows were sorted by rocPRIM; one thread per day
 __global__ __launch_bounds__(64) void cl_bounds_sorted_kernel(const double *sorted, int64_t n, int64_t len, ClWin w, ClDay day) {
     const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    if (t < len) cl_bounds(ClRow<false>{sorted + t * n}, day.n[t], w, day.lo[t], day.hi[t]);
+    if (t < len) cl_bounds(XsRow<false>{sorted + t * n}, day.n[t], w, day.lo[t], day.hi[t]);
 }
 
 // one thread per (day, block of 256 symbols).  The value chain of one member, up to the step pass P sums:
@@ -334,24 +303,16 @@ pq_status pq_factor_clean(pq_ctx *ctx, const pq_batch *b, const double *factor, 
     const ClIn in{factor, cap_z, industry, G, standardize, d};
     const size_t cells = (size_t)d.len * (size_t)d.n, len = (size_t)d.len;
     const int64_t nblk = (d.n + XS_BLOCK - 1) / XS_BLOCK;
-    const bool sorted = winsorize == CL_WIN_MAD || winsorize == CL_WIN_PCT, wide = sorted && d.n > XS_LDS_MAX;
-    if (wide) {
-        PQ_REQUIRE(d.n <= 100000, "pq_factor_clean: mad / percentile winsorize support at most 100000 series");
-        PQ_REQUIRE(cells < (1ull << 32), "pq_factor_clean: mad / percentile winsorize need n_series * len < 2^32 above 16384 series");
-    }
-    size_t tmp_bytes = 0;
-    if (wide)
-        PQ_HIP_TRY(rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes, (double *)nullptr, (double *)nullptr, (unsigned)cells,
-                                                      (unsigned)d.len, (unsigned *)nullptr, (unsigned *)nullptr, 0, 64, ctx->stream));
+    const bool sorted = winsorize == CL_WIN_MAD || winsorize == CL_WIN_PCT;
+    XsDaySort plan{};
+    if (sorted) PQ_TRY(xs_day_sort_plan(ctx, d, "pq_factor_clean (mad / percentile winsorize)", &plan));
     // workspace: per-day n (i32) and 8 parameter rows (f64) | industry means [G][len] | block partials: 2 sums (f64) + count (i32) |
     // industry partials: sums (f64) + counts (u16) [nblk][G][len] | sorted modes: keys day-major (f64) | wide: sorted keys, offsets, rocPRIM temp
     const size_t part = (size_t)nblk * len, gpart = part * (size_t)G;
     const size_t o_par = xs_al(len * 4), o_gm = o_par + 8 * xs_al(len * 8), o_ps = o_gm + xs_al((size_t)G * len * 8),
                  o_pc = o_ps + 2 * xs_al(part * 8), o_gs = o_pc + xs_al(part * 4), o_gc = o_gs + xs_al(gpart * 8),
-                 o_key = o_gc + xs_al(gpart * 2), o_srt = o_key + (sorted ? xs_al(cells * 8) : 0),
-                 o_off = o_srt + (wide ? xs_al(cells * 8) : 0), o_tmp = o_off + (wide ? xs_al((len + 1) * 4) : 0),
-                 total = o_tmp + (wide ? xs_al(tmp_bytes) : 0);
-    PQ_TRY(pq_ws_reserve(ctx, total));
+                 o_key = o_gc + xs_al(gpart * 2), o_srt = o_key + (sorted ? xs_al(cells * 8) : 0);
+    PQ_TRY(pq_ws_reserve(ctx, o_srt + plan.bytes));
     unsigned char *ws = (unsigned char *)ctx->ws;
     ClDay day;
     day.n = (int32_t *)ws;
@@ -383,21 +344,16 @@ pq_status pq_factor_clean(pq_ctx *ctx, const pq_batch *b, const double *factor, 
     } else if (sorted) {
         double *key = (double *)(ws + o_key);
         PQ_HIP_TRY(hipMemsetAsync(day.n, 0, len * 4, st));
-        hipLaunchKernelGGL(cl_prep_kernel, dim3((unsigned)((d.len + 31) / 32), (unsigned)((d.n + 31) / 32)), dim3(256), 0, st, in, key, day.n);
-        if (!wide) {
-            int P = 16;
-            while (P < d.n) P <<= 1;
-            const int nthr = P / 16 < 64 ? 64 : (P / 16 > 1024 ? 1024 : P / 16);
-            const size_t lds = (size_t)(P + P / 16) * 8;
-            PQ_HIP_TRY(hipFuncSetAttribute((const void *)cl_bounds_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(cl_bounds_lds_kernel, dim3((unsigned)d.len), dim3(nthr), lds, st, (const double *)key, d.n, P, w, day);
+        hipLaunchKernelGGL(xs_prep_kernel<ClKey>, dim3((unsigned)((d.len + 31) / 32), (unsigned)((d.n + 31) / 32)), dim3(256), 0, st,
+                           ClKey{in}, d, key, day.n);
+        if (!plan.wide) {
+            const XsLds L = xs_lds_shape(d.n);
+            PQ_HIP_TRY(hipFuncSetAttribute((const void *)cl_bounds_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.bytes));
+            hipLaunchKernelGGL(cl_bounds_lds_kernel, dim3((unsigned)d.len), dim3(L.nthr), L.bytes, st, (const double *)key, d.n, L.P, w, day);
         } else {
-            double *srt = (double *)(ws + o_srt);
-            unsigned *off = (unsigned *)(ws + o_off);
-            hipLaunchKernelGGL(xs_offsets_kernel, dim3((unsigned)((d.len + 256) / 256)), dim3(256), 0, st, off, d.len, d.n);
-            PQ_HIP_TRY(rocprim::segmented_radix_sort_keys(ws + o_tmp, tmp_bytes, key, srt, (unsigned)cells, (unsigned)d.len, off, off + 1, 0,
-                                                          64, st));
-            hipLaunchKernelGGL(cl_bounds_sorted_kernel, gd, dim3(64), 0, st, (const double *)srt, d.n, d.len, w, day);
+            const double *srt;
+            PQ_TRY(xs_day_sort_wide(ctx, d, plan, ws + o_srt, key, &srt));
+            hipLaunchKernelGGL(cl_bounds_sorted_kernel, gd, dim3(64), 0, st, srt, d.n, d.len, w, day);
         }
     }
     // 2. size neutralization

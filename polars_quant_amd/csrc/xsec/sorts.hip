@@ -3,12 +3,13 @@
 // README.md:1479-1487, :1535-1545, :1589-1599; README-only => decision D-15).
 //
 // Columns are symbol-major [n_series][stride]; a day's cross-section is a strided column.
-//  1. prep:      a tiled transpose turns the factor column into day-major key rows (+inf where the (factor, return) pair is not in
-//                the cross-section) and counts each day's cross-section n.
-//  2. label:     up to XS_LDS_MAX symbols one workgroup per day sorts its key row in LDS (bitonic, keys only); wider cross-sections
-//                use rocPRIM's segmented radix sort (keys only) in global memory.  Each symbol then finds its tie run [a, b) by two
-//                binary searches of its own key in the sorted row -- m = a + b, so ties share a label and nothing depends on sort
-//                stability -- and writes one uint8 label per cell, day-major.
+//  1. prep:      the day-sort stage of xsec_dev.h (also clean.hip's and build.hip's): xs_prep_kernel, a tiled transpose, turns the
+//                factor column into day-major key rows (+inf where the (factor, return) pair is not in the cross-section) and counts
+//                each day's cross-section n.
+//  2. label:     up to XS_LDS_MAX symbols one workgroup per day sorts its key row in LDS (xs_load_sort_row: bitonic, keys only); wider
+//                cross-sections go through daysort.hip (rocPRIM's segmented radix sort, keys only, in global memory).  Each symbol then
+//                finds its tie run [a, b) by binary searches of its own key in the sorted row (xs_tie_run) -- m = a + b, so ties share
+//                a label and nothing depends on sort stability -- and writes one uint8 label per cell, day-major.
 //  3. transpose: labels day-major -> symbol-major, 64 x 64 byte tiles.
 //  4. aggregate: one thread per (day, block of 256 symbols), consecutive threads on consecutive days (coalesced); the per-group sums
 //                are D-12's order (ascending symbols inside a block, from 0.0), counts and "new member" counts are integers.  A per-day
@@ -16,7 +17,6 @@
 //  5. summary:   one 64-lane workgroup per output row; chunks of the series are staged in LDS and summed by one lane in ascending day
 //                order (the stated sequential order), two-pass sample std.
 #include "xsec_dev.h"
-#include <rocprim/rocprim.hpp>
 
 namespace {
 
@@ -27,51 +27,14 @@ struct XsRule {
     double top, bottom;
 };
 
-// [n][stride] factor + return -> day-major [len][n] keys (the factor where the pair is valid, else +inf) and n per day
-__global__ __launch_bounds__(256) void xs_prep_kernel(const double *f, const double *r, Dims d, double *key, int32_t *n_valid) {
-    __shared__ double tile[32][33];
-    __shared__ int cnt[32];
-    const int64_t t0 = (int64_t)blockIdx.x * 32, s0 = (int64_t)blockIdx.y * 32;
-    const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5; // 32 x 8
-    if (threadIdx.x < 32) cnt[threadIdx.x] = 0;
-    for (int i = ly; i < 32; i += 8) { // rows = symbols, lanes along days (coalesced reads)
-        const int64_t s = s0 + i, t = t0 + lx;
-        double k = xs_inf();
-        if (s < d.n && t < d.len) {
-            const double a = f[s * d.stride + t], b = r[s * d.stride + t];
-            if (xs_valid(a) && xs_valid(b)) k = a;
-        }
-        tile[i][lx] = k;
+// the key of xs_prep_kernel: the factor, as it is, where the (factor, return) pair is valid
+struct XsKey {
+    const double *f, *r;
+    __device__ double operator()(int64_t o) const {
+        const double a = f[o], b = r[o];
+        return (xs_valid(a) & xs_valid(b)) ? a : xs_inf(); // &, not &&: both loads are issued before either test
     }
-    __syncthreads();
-    for (int i = ly; i < 32; i += 8) { // rows = days, lanes along symbols (coalesced writes)
-        const int64_t t = t0 + i, s = s0 + lx;
-        const double k = tile[lx][i];
-        if (t < d.len && s < d.n) {
-            key[t * d.n + s] = k;
-            if (k != xs_inf()) atomicAdd(&cnt[i], 1);
-        }
-    }
-    __syncthreads();
-    if (threadIdx.x < 32 && t0 + threadIdx.x < d.len && cnt[threadIdx.x]) atomicAdd(&n_valid[t0 + threadIdx.x], cnt[threadIdx.x]);
-}
-
-// m = a + b for the tie run [a, b) of `key` in the ascending row S[0 .. nv) (key is one of its entries; PAD: S is an LDS row indexed
-// through xs_phys): binary searches only, so a discrete factor's runs of thousands of equal keys cost O(log nv) per symbol, not O(run)
-template <bool PAD>
-__device__ __forceinline__ int64_t xs_pos2(const double *S, int nv, double key) {
-    auto at = [&](int i) { return S[PAD ? xs_phys(i) : i]; };
-    int lo = 0, hi = nv;
-    while (lo < hi) { const int mid = (lo + hi) >> 1; if (at(mid) < key) lo = mid + 1; else hi = mid; }
-    const int a = lo;
-    int b = a + 1;
-    if (b < nv && at(b) == key) {
-        lo = b + 1; hi = nv;
-        while (lo < hi) { const int mid = (lo + hi) >> 1; if (at(mid) <= key) lo = mid + 1; else hi = mid; }
-        b = lo;
-    }
-    return (int64_t)a + (int64_t)b;
-}
+};
 
 __device__ __forceinline__ uint8_t xs_label(int64_t m, int64_t nv, const XsRule &rule) {
     if (rule.mode == 0) return (uint8_t)((m * rule.q) / (2 * nv)); // floor(m Q / 2n) in integers: m < 2n => [0, Q)
@@ -94,12 +57,10 @@ __global__ __launch_bounds__(1024) void xs_label_lds_kernel(const double *key, c
         for (int s = tid; s < n; s += nthr) out[s] = PQ_LABEL_OUT;
         return;
     }
-    for (int i = tid; i < P; i += nthr) S[xs_phys(i)] = i < n ? row[i] : xs_inf();
-    __syncthreads();
-    xs_sort_lds(S, P, (int)n, tid, nthr);
+    xs_load_sort_row(S, row, n, P, tid, nthr);
     for (int s = tid; s < n; s += nthr) {
         const double k = row[s];
-        out[s] = k == xs_inf() ? (uint8_t)PQ_LABEL_OUT : xs_label(xs_pos2<true>(S, nv, k), nv, rule);
+        out[s] = k == xs_inf() ? (uint8_t)PQ_LABEL_OUT : xs_label(xs_tie_run(XsRow<true>{S}, nv, k), nv, rule);
     }
 }
 
@@ -112,7 +73,7 @@ __global__ __launch_bounds__(256) void xs_label_sorted_kernel(const double *key,
     const int nv = n_valid[t];
     for (int64_t s = threadIdx.x; s < n; s += 256) {
         const double k = row[s];
-        out[s] = (nv < rule.min_n || k == xs_inf()) ? (uint8_t)PQ_LABEL_OUT : xs_label(xs_pos2<false>(S, nv, k), nv, rule);
+        out[s] = (nv < rule.min_n || k == xs_inf()) ? (uint8_t)PQ_LABEL_OUT : xs_label(xs_tie_run(XsRow<false>{S}, nv, k), nv, rule);
     }
 }
 
@@ -269,23 +230,15 @@ pq_status xs_groups(pq_ctx *ctx, const pq_batch *b, const double *factor, const 
     const Dims d = dims_of(b);
     const size_t cells = (size_t)d.len * (size_t)d.n, len = (size_t)d.len;
     const int64_t nblk = (d.n + XS_BLOCK - 1) / XS_BLOCK > 0 ? (d.n + XS_BLOCK - 1) / XS_BLOCK : 1;
-    const bool wide = d.n > XS_LDS_MAX;
-    if (wide) {
-        PQ_REQUIRE(d.n <= 100000, "factor sorts support at most 100000 series");
-        PQ_REQUIRE(cells < (1ull << 32), "factor sorts need n_series * len < 2^32 above 16384 series");
-    }
-    size_t tmp_bytes = 0;
-    if (wide)
-        PQ_HIP_TRY(rocprim::segmented_radix_sort_keys(nullptr, tmp_bytes, (double *)nullptr, (double *)nullptr, (unsigned)cells,
-                                                      (unsigned)d.len, (unsigned *)nullptr, (unsigned *)nullptr, 0, 64, ctx->stream));
+    XsDaySort plan;
+    PQ_TRY(xs_day_sort_plan(ctx, d, "factor sorts", &plan));
     // workspace: keys (f64, day-major) | n per day (i32) | labels day-major (u8) | labels symbol-major (u8, when the caller passes
     // none) | block partials: sums (f64), counts, new members (i32) | wide: sorted keys (f64), offsets (u32), rocPRIM temp
     const size_t part = (size_t)nblk * (size_t)ng * len;
     const size_t o_cnt = xs_al(cells * 8), o_ldm = o_cnt + xs_al(len * 4), o_lsm = o_ldm + xs_al(cells),
                  o_ps = o_lsm + (labels ? 0 : xs_al(cells)), o_pc = o_ps + xs_al(part * 8), o_pn = o_pc + xs_al(part * 4),
-                 o_srt = o_pn + xs_al(part * 4), o_off = o_srt + (wide ? xs_al(cells * 8) : 0),
-                 o_tmp = o_off + (wide ? xs_al((len + 1) * 4) : 0), total = o_tmp + (wide ? xs_al(tmp_bytes) : 0);
-    PQ_TRY(pq_ws_reserve(ctx, total));
+                 o_srt = o_pn + xs_al(part * 4);
+    PQ_TRY(pq_ws_reserve(ctx, o_srt + plan.bytes));
     unsigned char *w = (unsigned char *)ctx->ws;
     double *key = (double *)w;
     int32_t *nv = (int32_t *)(w + o_cnt);
@@ -296,24 +249,18 @@ pq_status xs_groups(pq_ctx *ctx, const pq_batch *b, const double *factor, const 
     int32_t *pcnt = (int32_t *)(w + o_pc), *pnew = (int32_t *)(w + o_pn);
     if (d.n > 0) {
         PQ_HIP_TRY(hipMemsetAsync(nv, 0, len * 4, ctx->stream));
-        hipLaunchKernelGGL(xs_prep_kernel, dim3((unsigned)((d.len + 31) / 32), (unsigned)((d.n + 31) / 32)), dim3(256), 0, ctx->stream,
-                           factor, fwd_return, d, key, nv);
-        if (!wide) {
-            int P = 16;
-            while (P < d.n) P <<= 1;
-            const int nthr = P / 16 < 64 ? 64 : (P / 16 > 1024 ? 1024 : P / 16);
-            const size_t lds = (size_t)(P + P / 16) * 8;
-            PQ_HIP_TRY(hipFuncSetAttribute((const void *)xs_label_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(xs_label_lds_kernel, dim3((unsigned)d.len), dim3(nthr), lds, ctx->stream, (const double *)key,
-                               (const int32_t *)nv, d.n, P, rule, ldm);
+        hipLaunchKernelGGL(xs_prep_kernel<XsKey>, dim3((unsigned)((d.len + 31) / 32), (unsigned)((d.n + 31) / 32)), dim3(256), 0,
+                           ctx->stream, XsKey{factor, fwd_return}, d, key, nv);
+        if (!plan.wide) {
+            const XsLds L = xs_lds_shape(d.n);
+            PQ_HIP_TRY(hipFuncSetAttribute((const void *)xs_label_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.bytes));
+            hipLaunchKernelGGL(xs_label_lds_kernel, dim3((unsigned)d.len), dim3(L.nthr), L.bytes, ctx->stream, (const double *)key,
+                               (const int32_t *)nv, d.n, L.P, rule, ldm);
         } else {
-            double *srt = (double *)(w + o_srt);
-            unsigned *off = (unsigned *)(w + o_off);
-            hipLaunchKernelGGL(xs_offsets_kernel, dim3((unsigned)((d.len + 256) / 256)), dim3(256), 0, ctx->stream, off, d.len, d.n);
-            PQ_HIP_TRY(rocprim::segmented_radix_sort_keys(w + o_tmp, tmp_bytes, key, srt, (unsigned)cells, (unsigned)d.len, off, off + 1, 0,
-                                                          64, ctx->stream));
-            hipLaunchKernelGGL(xs_label_sorted_kernel, dim3((unsigned)d.len), dim3(256), 0, ctx->stream, (const double *)key,
-                               (const double *)srt, (const int32_t *)nv, d.n, rule, ldm);
+            const double *srt;
+            PQ_TRY(xs_day_sort_wide(ctx, d, plan, w + o_srt, key, &srt));
+            hipLaunchKernelGGL(xs_label_sorted_kernel, dim3((unsigned)d.len), dim3(256), 0, ctx->stream, (const double *)key, srt,
+                               (const int32_t *)nv, d.n, rule, ldm);
         }
         hipLaunchKernelGGL(xs_label_transpose_kernel, dim3((unsigned)((d.len + 63) / 64), (unsigned)((d.n + 63) / 64)), dim3(256), 0,
                            ctx->stream, (const uint8_t *)ldm, d.n, d.len, lsm, lstride);

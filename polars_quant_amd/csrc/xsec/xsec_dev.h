@@ -1,5 +1,7 @@
-// xsec/xsec_dev.h -- device helpers shared by the cross-sectional kernels (sorts.hip: D-15, clean.hip: D-16, regress.hip: D-17): the
-// summation block, the LDS bitonic sort of one day's keys, the segment offsets of rocPRIM's segmented sort, the sequential summaries.
+// xsec/xsec_dev.h -- helpers shared by the cross-sectional kernels (sorts.hip: D-15, clean.hip: D-16, regress.hip: D-17, robust.hip:
+// D-18, build.hip: D-20): the summation block, the day-sort stage (D-15: the prep transpose to day-major keys, the LDS bitonic sort of
+// one day's keys, the row accessor and the tie-run search on a sorted row, and the host interface of daysort.hip for rows too wide for
+// LDS), the sequential summaries.
 #pragma once
 #include "../pq_dev.h"
 
@@ -76,9 +78,58 @@ __device__ __forceinline__ void xs_sort_lds(double *S, int P, int n, int tid, in
     }
 }
 
-__global__ __launch_bounds__(256) void xs_offsets_kernel(unsigned *off, int64_t segs, int64_t n) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i <= segs) off[i] = (unsigned)(i * n);
+// S[0 .. P) <- row[0 .. n) with a +inf tail, sorted ascending (one workgroup; S is an LDS row of xs_lds_shape(n).bytes)
+__device__ __forceinline__ void xs_load_sort_row(double *S, const double *row, int64_t n, int P, int tid, int nthr) {
+    for (int i = tid; i < P; i += nthr) S[xs_phys(i)] = i < n ? row[i] : xs_inf();
+    __syncthreads();
+    xs_sort_lds(S, P, (int)n, tid, nthr);
+}
+
+// [n][stride] columns -> day-major [len][n] keys and n per day.  key(o) is the key of the cell at offset o = s * stride + t, or +inf where
+// the cell is not in the day's sample; the callers differ only in it.  32 x 32 tiles, LDS rows padded to 33 words.
+template <class Key> __global__ __launch_bounds__(256) void xs_prep_kernel(Key key, Dims d, double *out, int32_t *n_valid) {
+    __shared__ double tile[32][33];
+    __shared__ int cnt[32];
+    const int64_t t0 = (int64_t)blockIdx.x * 32, s0 = (int64_t)blockIdx.y * 32;
+    const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5; // 32 x 8
+    if (threadIdx.x < 32) cnt[threadIdx.x] = 0;
+    for (int i = ly; i < 32; i += 8) { // rows = symbols, lanes along days (coalesced reads)
+        const int64_t s = s0 + i, t = t0 + lx;
+        tile[i][lx] = (s < d.n && t < d.len) ? key(s * d.stride + t) : xs_inf();
+    }
+    __syncthreads();
+    for (int i = ly; i < 32; i += 8) { // rows = days, lanes along symbols (coalesced writes)
+        const int64_t t = t0 + i, s = s0 + lx;
+        const double k = tile[lx][i];
+        if (t < d.len && s < d.n) {
+            out[t * d.n + s] = k;
+            if (k != xs_inf()) atomicAdd(&cnt[i], 1);
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 32 && t0 + threadIdx.x < d.len && cnt[threadIdx.x]) atomicAdd(&n_valid[t0 + threadIdx.x], cnt[threadIdx.x]);
+}
+
+// one sorted day: an LDS row indexed through xs_phys (PAD) or a plain global row
+template <bool PAD> struct XsRow {
+    const double *S;
+    __device__ __forceinline__ double operator()(int i) const { return S[PAD ? xs_phys(i) : i]; }
+};
+
+// m = a + b for the tie run [a, b) of `key` in the ascending row S[0 .. nv) (key is one of its entries, -0 == +0): binary searches only,
+// so a discrete factor's runs of thousands of equal keys cost O(log nv) per symbol, not O(run); the second search is skipped where the
+// next entry already differs.  Ties share m and nothing depends on sort stability.
+template <bool PAD> __device__ __forceinline__ int64_t xs_tie_run(XsRow<PAD> S, int nv, double key) {
+    int lo = 0, hi = nv;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (S(mid) < key) lo = mid + 1; else hi = mid; }
+    const int a = lo;
+    int b = a + 1;
+    if (b < nv && S(b) == key) {
+        lo = b + 1; hi = nv;
+        while (lo < hi) { const int mid = (lo + hi) >> 1; if (S(mid) <= key) lo = mid + 1; else hi = mid; }
+        b = lo;
+    }
+    return (int64_t)a + (int64_t)b;
 }
 
 // Sequential statistics of a series x[0 .. len) over its non-NaN entries, in ascending order from 0.0.  SQ = false: count, sum and
@@ -127,3 +178,20 @@ __device__ void xs_seq(const double *x, int64_t len, double center, double *buf,
 inline size_t xs_al(size_t x) { return (x + 255) / 256 * 256; }
 
 } // namespace
+
+// ---------------------------------------------------------------- host side of the day sort (daysort.hip)
+// launch shape of a kernel that sorts one day of n <= XS_LDS_MAX keys in LDS: P = the power of two >= max(16, n), one thread per 16-key
+// chunk clamped to 64 .. 1024, and the padded row's bytes
+struct XsLds { int P, nthr; size_t bytes; };
+inline XsLds xs_lds_shape(int64_t n) {
+    int P = 16;
+    while (P < n) P <<= 1;
+    return XsLds{P, P / 16 < 64 ? 64 : (P / 16 > 1024 ? 1024 : P / 16), (size_t)(P + P / 16) * 8};
+}
+// n > XS_LDS_MAX: rocPRIM's segmented radix sort in global memory.  The caller appends `bytes` to its workspace (0 when !wide) and hands
+// the start of that tail to xs_day_sort_wide; the offsets are relative to it: sorted keys (f64), segment offsets (u32), rocPRIM temp.
+struct XsDaySort { bool wide; size_t tmp_bytes, o_off, o_tmp, bytes; };
+// the width limits (PQ_ERR_ARG, the message prefixed with `who`) and rocPRIM's size query
+pq_status xs_day_sort_plan(pq_ctx *ctx, const Dims &d, const char *who, XsDaySort *plan);
+// sorts every day-major row of key[len][n] on ctx->stream; *sorted = the sorted rows (inside the tail)
+pq_status xs_day_sort_wide(pq_ctx *ctx, const Dims &d, const XsDaySort &plan, unsigned char *tail, const double *key, const double **sorted);
