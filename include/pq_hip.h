@@ -450,6 +450,34 @@ pq_status pq_backtest_report(pq_ctx *, const pq_batch *, const double *total_val
 pq_status pq_report_portfolio(pq_ctx *, int64_t n_symbols, const double *report, const double *curve_row, double initial_capital,
                               double *out);
 
+/* ---- SequentialBacktester (src/backtest/sequential.rs:48-171, :207-336; decision D-23 in DESIGN.md): the shared-cash portfolio engine,
+ * replayed from order tapes.  The reference's callback sees an OrderContext and the period index only (:291-294), so its orders do not
+ * depend on the engine's state: they are recorded first and matched here, one wavefront per tape.
+ *   A tape has n_periods periods over the assets 0 .. n_assets - 1.  Orders (asset, quantity, price) lie in callback order; quantity is
+ *   signed (buy > 0, sell < 0).  period_offsets [n_tapes][n_periods + 1] holds ABSOLUTE indices into the order arrays: period t of tape b
+ *   owns orders [off[b][t], off[b][t + 1]).  Two tapes may point at the same orders (one tape under many parameter sets).  An offset is
+ *   clamped into [0, n_orders], a decreasing pair is an empty period, an order whose asset is outside [0, n_assets) is skipped.
+ *   An order takes part iff price is not NaN and > 0 and quantity is not NaN and not 0 (:185-204); it then sets board[asset] = price
+ *   whether it fills or not (:298).  Buy (:56-73, :129-135): fp = price + buy_slippage, cost = q fp, com = max(cost buy_rate, min_fee),
+ *   fills iff cash >= cost + com; cash -= cost + com, pos += q, entry = fp (overwritten, not averaged), trades += 1.  Sell (:74-92,
+ *   :136-156): fills iff pos >= |q|; fp = price - sell_slippage, rev = |q| fp, com = max(rev sell_rate, min_fee), cash += rev - com,
+ *   pos += q, wins += 1 iff rev - com > |q| entry, pos <= 1e-8 becomes 0; a sell is not counted in trades.
+ *   equity[t] = cash + V (:161-171), V = the sum of pos[a] board[a] over the held assets (pos > 0) in D-22's order over a: 64 partials
+ *   (partial k adds a = k, k + 64, ... from +0.0; an asset not held adds +0.0), folded p[k] += p[k + s], s = 32 .. 1.
+ * params: HOST array of n_params = 1 or n_tapes entries.  benchmark: ONE device series of n_periods rows or NULL.  equity [n_tapes]
+ * [n_periods]; cash the same or NULL; position [n_tapes][n_assets] (the final holdings) or NULL; counts [n_tapes][2] = trades, wins;
+ * summary [n_tapes][PQ_SUMMARY_COLS] (calculate_summary of the equity row, metrics.rs:7-152) or NULL.  n_assets > 6144 (24 bytes of LDS
+ * per asset and tape) is PQ_ERR_ARG and launches nothing; n_tapes = 0 or n_periods = 0 launches nothing.  Uses the context workspace for
+ * the parameters when n_params > 1.  Suite recording is refused. */
+typedef struct {
+    double initial_capital, buy_slippage, sell_slippage, buy_commission_rate, sell_commission_rate, minimum_commission_fee;
+} pq_seq_params; /* sequential.rs:232 defaults: 1e5, 0, 0, 3e-4, 3e-4, 5 */
+#define PQ_SEQ_MAX_ASSETS 6144
+pq_status pq_backtest_sequential(pq_ctx *, int64_t n_tapes, int64_t n_periods, int32_t n_assets, const int64_t *period_offsets,
+                                 const int32_t *asset, const double *quantity, const double *price, int64_t n_orders,
+                                 const double *benchmark, const pq_seq_params *params, int64_t n_params, double *equity, double *cash,
+                                 double *position, int64_t *counts, double *summary);
+
 /* ---- cross-sectional factor evaluation, Factor.ic / rank_ic / rolling_ic (README.md:1429-1430,
  * :1480-1482, :1626-1634; README-only, decision D-12 in oracle/backtest.c).  factor / fwd_return: [n_series][stride];
  * per day the cross-section = symbols where both values are non-null and finite.  method 0: Pearson IC (sums over

@@ -43,6 +43,11 @@ class LevParams(C.Structure):
                                           "interest_rate", "commission_rate", "min_commission", "slippage")]
 
 
+class SeqParams(C.Structure):
+    _fields_ = [(k, C.c_double) for k in ("initial_capital", "buy_slippage", "sell_slippage", "buy_commission_rate",
+                                          "sell_commission_rate", "minimum_commission_fee")]
+
+
 _lib = None
 
 
@@ -147,6 +152,9 @@ def lib() -> C.CDLL:
         L.pq_backtest_report.argtypes = [vp, C.POINTER(Batch), vp, C.c_double, vp, C.POINTER(LevParams), C.c_int32] + [vp] * 9
         L.pq_report_portfolio.restype = C.c_int32
         L.pq_report_portfolio.argtypes = [vp, C.c_int64, vp, vp, C.c_double, vp]
+        L.pq_backtest_sequential.restype = C.c_int32
+        L.pq_backtest_sequential.argtypes = [vp, C.c_int64, C.c_int64, C.c_int32, vp, vp, vp, vp, C.c_int64, vp, C.POINTER(SeqParams),
+                                             C.c_int64, vp, vp, vp, vp, vp]
         L.pq_recommended_stride.restype = C.c_int64
         L.pq_recommended_stride.argtypes = [C.c_int64]
         L.pq_layout_check.restype = C.c_int32

@@ -123,6 +123,9 @@ SUMMARY_KEYS = ["annualized_return", "max_drawdown", "alpha", "beta", "sharpe_ra
                 "total_trades"]  # metrics.rs:142-149
 BT_DEFAULTS = dict(initial_capital=100000.0, buy_slippage=0.0, sell_slippage=0.0, buy_commission_rate=0.0003,
                    sell_commission_rate=0.0003, min_commission=5.0, position_size=1.0)  # vectorized.rs:38
+# pq_seq_params, in the order of SequentialBacktester's constructor (sequential.rs:232; decision D-23)
+SEQ_DEFAULTS = dict(initial_capital=100000.0, buy_slippage=0.0, sell_slippage=0.0, buy_commission_rate=0.0003,
+                    sell_commission_rate=0.0003, minimum_commission_fee=5.0)
 
 # README.md:350-366 `Backtest(...)` defaults (decision D-10)
 LEV_DEFAULTS = dict(initial_capital=100000.0, position_size=1.0, leverage=1.0, margin_call_threshold=0.3,

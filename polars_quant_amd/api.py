@@ -1222,6 +1222,63 @@ def report_portfolio(report, curve_row, initial_capital: float):
     return out
 
 
+def backtest_sequential(period_offsets, asset, quantity, price, n_assets: int, benchmark=None, params=None, out=None):
+    """SequentialBacktester's engine on order tapes (decision D-23): period_offsets [B, T + 1] (or [T + 1]) int64, absolute indices
+    into the order arrays asset int32 / quantity / price [n_orders] (quantity signed); two tapes may point at the same orders.
+    benchmark: [T] or None.  params: None (the defaults), one dict for every tape or a list of B dicts over _spec.SEQ_DEFAULTS.
+    out: optional dict of preallocated device tensors under the result's names.
+    -> dict of device tensors: equity, cash [B, T]; position [B, A]; counts [B, 2] int64 (trades, wins); summary [B, 8].
+    T = 0 launches nothing.  Shape checks raise ValueError before any device work; n_assets above 6144 (PQ_SEQ_MAX_ASSETS) is the
+    library's argument error (PqError)."""
+    from ._lib import SeqParams
+    from ._spec import SEQ_DEFAULTS
+    shape = tuple(period_offsets.shape) if isinstance(period_offsets, torch.Tensor) else np.shape(period_offsets)
+    if len(shape) == 1:
+        shape = (1,) + shape
+    if len(shape) != 2 or shape[1] < 1:
+        raise ValueError(f"period_offsets must be [B, T + 1], got shape {shape}")
+    B, T = int(shape[0]), int(shape[1]) - 1
+    n_orders = _rp_numel(asset, "asset")
+    if _rp_numel(quantity, "quantity") != n_orders or _rp_numel(price, "price") != n_orders:
+        raise ValueError("asset, quantity and price must have one entry per order")
+    A = int(n_assets)
+    if A < 0:
+        raise ValueError("n_assets < 0")
+    if benchmark is not None and _rp_numel(benchmark, "benchmark") != T:
+        raise ValueError("benchmark must be one series with one row per period")
+    plist = [{}] if params is None else ([params] if isinstance(params, dict) else list(params))
+    if len(plist) not in (1, B):
+        raise ValueError(f"params must hold 1 or {B} entries, got {len(plist)}")
+    for d in plist:
+        unknown = set(d) - set(SEQ_DEFAULTS)
+        if unknown:
+            raise ValueError(f"unknown parameters {sorted(unknown)}")
+    prm = (SeqParams * len(plist))(*[SeqParams(**{**SEQ_DEFAULTS, **{k: float(v) for k, v in d.items()}}) for d in plist])
+    _require_gpu()
+    off = _rp_dev(period_offsets, torch.int64).reshape(B, T + 1).contiguous()
+    dev = off.device
+    a = _rp_dev(asset, torch.int32, dev).reshape(-1).contiguous()
+    q = _rp_dev(quantity, torch.float64, dev).reshape(-1).contiguous()
+    px = _rp_dev(price, torch.float64, dev).reshape(-1).contiguous()
+    bm = _rp_dev(benchmark, torch.float64, dev).reshape(-1).contiguous() if benchmark is not None else None
+    spec = dict(equity=((B, T), torch.float64), cash=((B, T), torch.float64), position=((B, A), torch.float64),
+                counts=((B, 2), torch.int64), summary=((B, 8), torch.float64))
+    r = {}
+    for k, (shp, dt) in spec.items():
+        t = None if out is None else out.get(k)
+        if t is None:
+            t = torch.zeros(shp, dtype=dt, device=dev)
+        elif tuple(t.shape) != shp or t.dtype != dt or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"out[{k!r}] must be a contiguous {dt} tensor of shape {shp} on {dev}")
+        r[k] = t
+    vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+    if B and T:
+        with torch.cuda.device(dev):
+            check(lib().pq_backtest_sequential(ctx(dev.index), B, T, A, vp(off), vp(a), vp(q), vp(px), n_orders, vp(bm), prm, len(plist),
+                                               vp(r["equity"]), vp(r["cash"]), vp(r["position"]), vp(r["counts"]), vp(r["summary"])))
+    return r
+
+
 def macd_cross_signals(close, fastperiod=12, slowperiod=26, signalperiod=9):
     p, kind, squeeze = _to_device(close)
     p = p.contiguous()
