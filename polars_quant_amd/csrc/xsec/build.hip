@@ -277,7 +277,7 @@ pq_status pq_factor_minmax(pq_ctx *ctx, const pq_batch *b, const double *factor,
     if (b->len == 0 || b->n_series == 0) return PQ_OK;
     const Dims d = dims_of(b);
     const size_t len = (size_t)d.len;
-    const int64_t nblk = (d.n + XS_BLOCK - 1) / XS_BLOCK;
+    const int64_t nblk = xs_nblk(d.n);
     // workspace: block partials min, max [nblk][len] | per-day min, max [len]
     const size_t part = xs_al((size_t)nblk * len * 8), row = xs_al(len * 8);
     PQ_TRY(pq_ws_reserve(ctx, 2 * part + 2 * row));
@@ -306,7 +306,7 @@ pq_status pq_factor_weighted(pq_ctx *ctx, const pq_batch *b, const double *facto
     const Dims d = dims_of(b);
     const size_t len = (size_t)d.len;
     const int G = group ? n_groups : 1;
-    const int64_t nblk = (d.n + XS_BLOCK - 1) / XS_BLOCK;
+    const int64_t nblk = xs_nblk(d.n);
     const BdW in{factor, weight, group, group ? group_stride : 0, group ? n_groups : 0, d};
     // workspace: block partials [nblk][G][len] | W [G][len]
     const size_t part = xs_al((size_t)nblk * (size_t)G * len * 8);

@@ -302,7 +302,7 @@ pq_status pq_factor_clean(pq_ctx *ctx, const pq_batch *b, const double *factor, 
     const int G = industry ? n_industries : 0;
     const ClIn in{factor, cap_z, industry, G, standardize, d};
     const size_t cells = (size_t)d.len * (size_t)d.n, len = (size_t)d.len;
-    const int64_t nblk = (d.n + XS_BLOCK - 1) / XS_BLOCK;
+    const int64_t nblk = xs_nblk(d.n);
     const bool sorted = winsorize == CL_WIN_MAD || winsorize == CL_WIN_PCT;
     XsDaySort plan{};
     if (sorted) PQ_TRY(xs_day_sort_plan(ctx, d, "pq_factor_clean (mad / percentile winsorize)", &plan));

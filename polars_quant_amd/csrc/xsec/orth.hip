@@ -3,22 +3,21 @@
 //
 // Columns are symbol-major [n_series][stride]; a day's cross-section is a strided column.  The sample of a day is every symbol whose K
 // factors are all non-null and finite.  orthogonalize: e_k (k = 1 .. K-1) is D-17's residual of f_k on f_0 .. f_{k-1} with an
-// intercept (sequential Gram-Schmidt); neutralize: e_k is D-17's residual of f_k on f_0 alone.  The shape is regress.hip's:
+// intercept (sequential Gram-Schmidt); neutralize: e_k is D-17's residual of f_k on f_0 alone.  The last level of orthogonalize(K) is
+// regress(K - 1) with r = f_{K-1}; the combine, the means, the factorization and the substitutions are D-17's own code, in xsec_ols.h:
 //  1. passes:  one thread per (day, block of 256 symbols), consecutive threads on consecutive days (coalesced), sums its block in
 //              ascending symbol order from 0.0, members only: pass 1 n and sum f_j; pass 2 the centred cross-products C[j][m]
-//              (m <= j; neutralize: column 0 only).
-//  2. combine: one thread per day adds the block sums in ascending block order from 0.0.  After pass 2 it factorises C = L D L^T once
-//              by rows (prefix-consistent: the leading k x k block is what D-17 factorises for k regressors) and solves the K - 1
-//              nested systems by forward then back substitution (neutralize: b = C[k][0] / C[0][0]).
+//              (m <= j; neutralize: column 0 only).  This file's own kernel, as regress.hip has its own (xsec_ols.h says why).
+//  2. combine: one thread per day adds the block sums in ascending block order from 0.0 (xo_combine, xo_means_kernel).  After pass 2
+//              it factorises C = L D L^T once by rows (xo_ldl; prefix-consistent: the leading k x k block is what D-17 factorises for
+//              k regressors) and solves the K - 1 nested systems, level k on row k of the triangle by xo_forward then xo_back as
+//              D-17 solves on its row K (neutralize: b = C[k][0] / C[0][0]).
 //  3. write:   the pass body once more: e = (f_k - fbar_k) - fit, fit = 0.0; fit += b_j (f_j - fbar_j) for ascending j.  A thread reads
 //              all K inputs of a symbol before it writes that symbol's residuals, so out[j] may be factors[j + 1].
-// Every operation is in D-17's order (restated in tests/xsec_orth_ref.py), so the residuals are bit-identical to the e of D-17's pass 3.
-#include "xsec_dev.h"
+// Every operation is D-17's, in its order (restated in tests/xsec_orth_ref.py), so the residuals are bit-identical to the e of D-17's pass 3.
+#include "xsec_ols.h"
 
 namespace {
-
-constexpr int OR_MAX_K = 8;             // PQ_REGRESS_MAX_K
-constexpr double OR_SINGULAR = 1e-12;   // pivot D_j <= 1e-12 * C[j][j]: singular (D-17)
 
 enum OrPass { OR_P1 = 1, OR_P2 = 2, OR_P3 = 3 };
 
@@ -29,8 +28,8 @@ template <int K, bool NEUT> struct OrNa {
 };
 
 struct OrIn {
-    const double *f[OR_MAX_K];
-    double *out[OR_MAX_K - 1];
+    const double *f[XO_MAX_K];
+    double *out[XO_MAX_K - 1];
     Dims d;
 };
 
@@ -70,7 +69,7 @@ __global__ __launch_bounds__(64) void or_pass_kernel(OrIn in, OrDay day, double 
     for (int q = 0; q < NA; q++) acc[q] = 0.0;
     int cnt = 0;
     const int64_t i_lo = (int64_t)blockIdx.y * XS_BLOCK, i_hi = i_lo + XS_BLOCK < d.n ? i_lo + XS_BLOCK : d.n;
-    constexpr int B = K <= 2 ? 8 : (K <= 4 ? 4 : 2);   // symbols loaded ahead: about 16 loads in flight per lane
+    constexpr int B = xo_ahead(K);
     for (int64_t i0 = i_lo; i0 < i_hi; i0 += B) {
         double fv[B][K];
 #pragma unroll
@@ -132,30 +131,6 @@ __global__ __launch_bounds__(64) void or_pass_kernel(OrIn in, OrDay day, double 
     if (P == OR_P1) pcnt[(int64_t)blockIdx.y * units + u] = cnt;
 }
 
-template <int NA>
-__device__ __forceinline__ void or_combine(const double *ps, int64_t nblk, int64_t units, int64_t u, double (&s)[NA]) {
-#pragma unroll
-    for (int q = 0; q < NA; q++) s[q] = 0.0;
-    for (int64_t k = 0; k < nblk; k++)
-#pragma unroll
-        for (int q = 0; q < NA; q++) s[q] += ps[(k * NA + q) * units + u];
-}
-
-// after pass 1: n and the means
-template <int K>
-__global__ __launch_bounds__(64) void or_means_kernel(const double *ps, const int32_t *pcnt, int64_t nblk, int64_t units, OrDay day) {
-    const int64_t u = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    if (u >= units) return;
-    double s[K];
-    or_combine<K>(ps, nblk, units, u, s);
-    int32_t n = 0;
-    for (int64_t k = 0; k < nblk; k++) n += pcnt[k * units + u];
-    day.n[u] = n;
-    const double dn = (double)n;
-#pragma unroll
-    for (int q = 0; q < K; q++) day.mean[(int64_t)q * units + u] = s[q] / dn;
-}
-
 // after pass 2: the coefficients of every level.  orthogonalize: C[0:K-1, 0:K-1] = L D L^T by rows once; level k (regressors
 // f_0 .. f_{k-1}) is solved on the leading k x k block as D-17 solves it: z_m = c_m - sum_{i < m} L[m][i] z_i, then
 // b_j = z_j / D_j - sum_{m > j} L[m][j] b_m (sums ascending from 0.0), c = C[k][0:k].  It has a solution while n >= k + 2 and every pivot
@@ -167,59 +142,24 @@ __global__ __launch_bounds__(64) void or_solve_kernel(const double *ps, int64_t 
     if (u >= units) return;
     constexpr int NA = OrNa<K, NEUT>::P2;
     double s[NA];
-    or_combine<NA>(ps, nblk, units, u, s);
+    xo_combine<NA>(ps, nblk, units, u, s);
     const int32_t n = day.n[u];
     if (NEUT) {
-        const bool ok = n >= 3 && s[0] > OR_SINGULAR * s[0];
+        const bool ok = n >= 3 && s[0] > XO_SINGULAR * s[0];
         day.nok[u] = ok ? K - 1 : 0;
 #pragma unroll
         for (int k = 1; k < K; k++) day.b[(int64_t)(k - 1) * units + u] = s[k] / s[0];
         return;
     }
     constexpr int R = K - 1;   // regressor rows: f_{K-1} is never a regressor
-    double L[R][R], D[R], W[R][R];
-#pragma unroll
-    for (int j = 0; j < R; j++)
-#pragma unroll
-        for (int k = 0; k < R; k++) { L[j][k] = j == k ? 1.0 : 0.0; W[j][k] = 0.0; }
-    int nok = 0;
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < R; j++) {
-#pragma unroll
-        for (int k = 0; k < j; k++) {
-            double w = s[j * (j + 1) / 2 + k];
-#pragma unroll
-            for (int m = 0; m < k; m++) w -= W[j][m] * L[k][m];
-            W[j][k] = w;
-            L[j][k] = w / D[k];
-        }
-        const double cjj = s[j * (j + 1) / 2 + j];
-        double dj = cjj;
-#pragma unroll
-        for (int m = 0; m < j; m++) dj -= W[j][m] * L[j][m];
-        D[j] = dj;
-        ok = ok && dj > OR_SINGULAR * cjj;   // NaN from an overflow counts as singular
-        if (ok && n >= j + 3) nok = j + 1;    // level j + 1 (regressors 0 .. j) is solved
-    }
-    day.nok[u] = nok;
+    double L[R][R], D[R];
+    const int npiv = xo_ldl<R>(s, L, D), nok = npiv < n - 2 ? npiv : n - 2;   // level k also needs n >= k + 2
+    day.nok[u] = nok > 0 ? nok : 0;
 #pragma unroll
     for (int k = 1; k < K; k++) {
         double z[R], b[R];
-#pragma unroll
-        for (int m = 0; m < k; m++) {
-            double t = 0.0;
-#pragma unroll
-            for (int i = 0; i < m; i++) t += L[m][i] * z[i];
-            z[m] = s[k * (k + 1) / 2 + m] - t;
-        }
-#pragma unroll
-        for (int j = k - 1; j >= 0; j--) {
-            double t = 0.0;
-#pragma unroll
-            for (int m = j + 1; m < k; m++) t += L[m][j] * b[m];
-            b[j] = z[j] / D[j] - t;
-        }
+        xo_forward<R>(L, s + xo_tri(k), k, z);   // row k of the triangle, as D-17 solves on its row K
+        xo_back<R>(L, D, z, k, b);
 #pragma unroll
         for (int j = 0; j < k; j++) day.b[(int64_t)(k * (k - 1) / 2 + j) * units + u] = b[j];
     }
@@ -229,25 +169,16 @@ template <int K, bool NEUT>
 pq_status or_run(pq_ctx *ctx, const OrIn &in) {
     const Dims d = in.d;
     const int64_t units = d.len;
-    const int64_t nblk = (d.n + XS_BLOCK - 1) / XS_BLOCK > 0 ? (d.n + XS_BLOCK - 1) / XS_BLOCK : 1;
-    const size_t U = (size_t)units, part = (size_t)nblk * U;
-    constexpr int NB = OrNa<K, NEUT>::NB;
-    // workspace: n, nok (i32) | mean [K], b [NB] (f64 rows) | block partials [nblk][NA][units] (f64) | block counts (i32)
-    const size_t o_nok = xs_al(U * 4), o_rows = o_nok + xs_al(U * 4), row = xs_al(U * 8), o_ps = o_rows + (K + NB) * row,
-                 o_pc = o_ps + xs_al(part * OrNa<K, NEUT>::P2 * 8), total = o_pc + xs_al(part * 4);
-    PQ_TRY(pq_ws_reserve(ctx, total));
-    unsigned char *ws = (unsigned char *)ctx->ws;
-    OrDay day;
-    day.n = (int32_t *)ws;
-    day.nok = (int32_t *)(ws + o_nok);
-    day.mean = (double *)(ws + o_rows);
-    day.b = (double *)(ws + o_rows + K * row);
-    double *ps = (double *)(ws + o_ps);
-    int32_t *pc = (int32_t *)(ws + o_pc);
+    const int64_t nblk = xs_nblk(d.n);
+    XoWs w;
+    PQ_TRY(xo_workspace(ctx, units, nblk, K, K + OrNa<K, NEUT>::NB, OrNa<K, NEUT>::P2, &w));   // own rows: b [NB]
+    const OrDay day{w.n, w.flag, w.mean, w.own};
+    double *ps = w.ps;
+    int32_t *pc = w.pcnt;
     const dim3 gp((unsigned)((units + 63) / 64), (unsigned)nblk), gu((unsigned)((units + 63) / 64));
     hipStream_t st = ctx->stream;
     hipLaunchKernelGGL((or_pass_kernel<K, NEUT, OR_P1>), gp, dim3(64), 0, st, in, day, ps, pc);
-    hipLaunchKernelGGL(or_means_kernel<K>, gu, dim3(64), 0, st, (const double *)ps, (const int32_t *)pc, nblk, units, day);
+    hipLaunchKernelGGL(xo_means_kernel<K>, gu, dim3(64), 0, st, (const double *)ps, (const int32_t *)pc, nblk, units, day.n, day.mean);
     hipLaunchKernelGGL((or_pass_kernel<K, NEUT, OR_P2>), gp, dim3(64), 0, st, in, day, ps, pc);
     hipLaunchKernelGGL((or_solve_kernel<K, NEUT>), gu, dim3(64), 0, st, (const double *)ps, nblk, units, day);
     hipLaunchKernelGGL((or_pass_kernel<K, NEUT, OR_P3>), gp, dim3(64), 0, st, in, day, ps, pc);
@@ -276,7 +207,7 @@ pq_status pq_factor_orthogonalize(pq_ctx *ctx, const pq_batch *b, const double *
                                   double *const *out) {
     const char *what = "pq_factor_orthogonalize";
     PQ_TRY(pq_check(ctx, b));
-    if (k < 2 || k > OR_MAX_K) { pq_set_error("%s: k must be in [2, 8]", what); return PQ_ERR_ARG; }
+    if (k < 2 || k > XO_MAX_K) { pq_set_error("%s: k must be in [2, 8]", what); return PQ_ERR_ARG; }
     if (mode != 0 && mode != 1) { pq_set_error("%s: mode must be 0 (orthogonalize) or 1 (neutralize)", what); return PQ_ERR_ARG; }
     if (ctx->rec) { pq_set_error("%s cannot be recorded into a suite", what); return PQ_ERR_UNSUPPORTED; }
     if (b->offsets) { pq_set_error("%s: ragged batches are not supported", what); return PQ_ERR_UNSUPPORTED; }

@@ -10,17 +10,18 @@
 //              consecutive symbols, each walking its own row; a factor flagged in series_mask is one [len] series read by every symbol.
 //  2. combine: one thread per unit adds the block sums in ascending block order from 0.0.  After pass 2 it factorises C = L D L^T,
 //              solves for b and the intercept, and keeps diag(C^-1) and fbar^T C^-1 fbar for the standard errors; after pass 3 it
-//              writes coef / t / p / R^2 / n.  The operation order is D-17's, restated in tests/xsec_regress_ref.py.
+//              writes coef / t / p / R^2 / n.  The operation order is D-17's, restated in tests/xsec_regress_ref.py.  The combine,
+//              the means, the factorization, the two substitutions and the head of the workspace are in xsec_ols.h, which orth.hip
+//              (D-19) shares: pass 2's sums are the packed triangle of the K + 1 columns f_0 .. f_{K-1}, r, and D-19's last level is
+//              this regression with r = f_{K-1}.  The pass kernel is this file's own (xsec_ols.h says why).
 //  3. summary: (cross-sectional) one 64-lane workgroup per regressor: the Fama-MacBeth mean / std / t / p over the days with a solution.
 // p-values: two-sided Student t, p = I_{df / (df + t^2)}(df / 2, 1/2), by the Lentz continued fraction in double-double arithmetic
 // (near x = 1 the fraction loses ~log10(1 / (1 - x)) digits in plain f64), with log Gamma(a + 1/2) / Gamma(a) from its asymptotic
 // series (lgamma(a) - lgamma(a + 1/2) cancels at large df).  Accurate to a few 1e-13 relative on df in [1, 1e5], |t| <= 50.
+#include "xsec_ols.h"
 #include "xsec_ttest.h"
 
 namespace {
-
-constexpr int RG_MAX_K = 8;             // PQ_REGRESS_MAX_K
-constexpr double RG_SINGULAR = 1e-12;   // pivot D_j <= 1e-12 * C[j][j]: singular
 
 // ---------------------------------------------------------------- passes
 enum RgPass { RG_P1 = 1, RG_P2 = 2, RG_P3 = 3 };
@@ -30,7 +31,7 @@ template <int K> struct RgNa {   // accumulators per pass
 };
 
 struct RgIn {
-    const double *f[RG_MAX_K];
+    const double *f[XO_MAX_K];
     const double *r;
     uint32_t series;       // time-series form: bit j = f[j] is one [len] series shared by every symbol
     Dims d;
@@ -70,7 +71,7 @@ __global__ __launch_bounds__(64) void rg_pass_kernel(RgIn in, RgUnit un, double 
     for (int q = 0; q < NA; q++) acc[q] = 0.0;
     int cnt = 0;
     const int64_t i_lo = (int64_t)blockIdx.y * XS_BLOCK, i_hi = i_lo + XS_BLOCK < span ? i_lo + XS_BLOCK : span;
-    constexpr int B = K + 1 <= 2 ? 8 : (K + 1 <= 4 ? 4 : 2);   // indices loaded ahead: about 16 loads in flight per lane
+    constexpr int B = xo_ahead(K + 1);
     for (int64_t i0 = i_lo; i0 < i_hi; i0 += B) {
         double rv[B], fv[B][K];
 #pragma unroll
@@ -121,41 +122,6 @@ __global__ __launch_bounds__(64) void rg_pass_kernel(RgIn in, RgUnit un, double 
     if (P == RG_P1) pcnt[(int64_t)blockIdx.y * units + u] = cnt;
 }
 
-template <int NA>
-__device__ __forceinline__ void rg_combine(const double *ps, int64_t nblk, int64_t units, int64_t u, double (&s)[NA]) {
-#pragma unroll
-    for (int q = 0; q < NA; q++) s[q] = 0.0;
-    for (int64_t k = 0; k < nblk; k++)
-#pragma unroll
-        for (int q = 0; q < NA; q++) s[q] += ps[(k * NA + q) * units + u];
-}
-
-// after pass 1: n and the means
-template <int K>
-__global__ __launch_bounds__(64) void rg_means_kernel(const double *ps, const int32_t *pcnt, int64_t nblk, int64_t units, RgUnit un) {
-    const int64_t u = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    if (u >= units) return;
-    double s[K + 1];
-    rg_combine<K + 1>(ps, nblk, units, u, s);
-    int32_t n = 0;
-    for (int64_t k = 0; k < nblk; k++) n += pcnt[k * units + u];
-    un.n[u] = n;
-    const double dn = (double)n;
-#pragma unroll
-    for (int q = 0; q <= K; q++) un.mean[(int64_t)q * units + u] = s[q] / dn;
-}
-
-// forward substitution with the unit lower-triangular L: z_m = v_m - sum_{i < m} L[m][i] z_i (sum ascending from 0.0)
-template <int K> __device__ __forceinline__ void rg_forward(const double (&L)[K][K], const double (&v)[K], double (&z)[K]) {
-#pragma unroll
-    for (int m = 0; m < K; m++) {
-        double s = 0.0;
-#pragma unroll
-        for (int i = 0; i < m; i++) s += L[m][i] * z[i];
-        z[m] = v[m] - s;
-    }
-}
-
 // after pass 2: C = L D L^T by rows, the solution b, the intercept, diag(C^-1) and 1/n + fbar^T C^-1 fbar
 template <int K>
 __global__ __launch_bounds__(64) void rg_solve_kernel(const double *ps, int64_t nblk, int64_t units, RgUnit un) {
@@ -163,45 +129,18 @@ __global__ __launch_bounds__(64) void rg_solve_kernel(const double *ps, int64_t 
     if (u >= units) return;
     constexpr int NA = RgNa<K>::P2;
     double s[NA];
-    rg_combine<NA>(ps, nblk, units, u, s);
+    xo_combine<NA>(ps, nblk, units, u, s);
     un.srr[u] = s[NA - 1];
     const int32_t n = un.n[u];
-    bool ok = n >= K + 2;
-    double L[K][K], D[K], W[K][K];
-#pragma unroll
-    for (int j = 0; j < K; j++)
-#pragma unroll
-        for (int k = 0; k < K; k++) { L[j][k] = j == k ? 1.0 : 0.0; W[j][k] = 0.0; }
-#pragma unroll
-    for (int j = 0; j < K; j++) {
-#pragma unroll
-        for (int k = 0; k < j; k++) {
-            double w = s[j * (j + 1) / 2 + k];
-#pragma unroll
-            for (int m = 0; m < k; m++) w -= W[j][m] * L[k][m];
-            W[j][k] = w;
-            L[j][k] = w / D[k];
-        }
-        const double cjj = s[j * (j + 1) / 2 + j];
-        double dj = cjj;
-#pragma unroll
-        for (int m = 0; m < j; m++) dj -= W[j][m] * L[j][m];
-        D[j] = dj;
-        ok = ok && dj > RG_SINGULAR * cjj;   // singular: D_j <= 1e-12 C[j][j] (NaN from an overflow counts as singular)
-    }
+    double L[K][K], D[K];
+    const bool ok = xo_ldl<K>(s, L, D) == K && n >= K + 2;
     un.ok[u] = ok ? 1 : 0;
     if (!ok) return;
-    double c[K], z[K], b[K], fbar[K];
+    double z[K], b[K], fbar[K];
 #pragma unroll
-    for (int j = 0; j < K; j++) { c[j] = s[K * (K + 1) / 2 + j]; fbar[j] = un.mean[(int64_t)(j + 1) * units + u]; }
-    rg_forward<K>(L, c, z);
-#pragma unroll
-    for (int j = K - 1; j >= 0; j--) {   // y_j = z_j / D_j; b_j = y_j - sum_{m > j} L[m][j] b_m (m ascending, from 0.0)
-        double t = 0.0;
-#pragma unroll
-        for (int m = j + 1; m < K; m++) t += L[m][j] * b[m];
-        b[j] = z[j] / D[j] - t;
-    }
+    for (int j = 0; j < K; j++) fbar[j] = un.mean[(int64_t)(j + 1) * units + u];
+    xo_forward<K>(L, s + xo_tri(K), K, z);   // c = row K of the triangle
+    xo_back<K>(L, D, z, K, b);
     double sa = 0.0;
 #pragma unroll
     for (int j = 0; j < K; j++) sa += b[j] * fbar[j];
@@ -214,14 +153,14 @@ __global__ __launch_bounds__(64) void rg_solve_kernel(const double *ps, int64_t 
         double e[K], w[K];
 #pragma unroll
         for (int m = 0; m < K; m++) e[m] = m == j ? 1.0 : 0.0;
-        rg_forward<K>(L, e, w);
+        xo_forward<K>(L, e, K, w);
         double vj = 0.0;
 #pragma unroll
         for (int m = 0; m < K; m++) vj += w[m] * w[m] / D[m];
         un.v[(int64_t)j * units + u] = vj;
     }
     double w[K], q = 0.0;
-    rg_forward<K>(L, fbar, w);
+    xo_forward<K>(L, fbar, K, w);
 #pragma unroll
     for (int m = 0; m < K; m++) q += w[m] * w[m] / D[m];
     un.v[(int64_t)K * units + u] = 1.0 / (double)n + q;
@@ -235,7 +174,7 @@ __global__ __launch_bounds__(64) void rg_final_kernel(const double *ps, int64_t 
     const int64_t u = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (u >= units) return;
     double sse[1];
-    rg_combine<1>(ps, nblk, units, u, sse);
+    xo_combine<1>(ps, nblk, units, u, sse);
     const int32_t n = un.n[u];
     n_obs[u] = n;
     const bool ok = un.ok[u] != 0;
@@ -276,26 +215,16 @@ template <int K, bool TS>
 pq_status rg_run(pq_ctx *ctx, const RgIn &in, const RgOut &out) {
     const Dims d = in.d;
     const int64_t units = TS ? d.n : d.len, span = TS ? d.len : d.n;
-    const int64_t nblk = (span + XS_BLOCK - 1) / XS_BLOCK > 0 ? (span + XS_BLOCK - 1) / XS_BLOCK : 1;
-    const size_t U = (size_t)units, part = (size_t)nblk * U;
-    // workspace: n, ok (i32) | mean, b, v [K + 1] and srr (f64 rows) | block partials [nblk][NA][units] (f64) | block counts (i32)
-    const size_t o_ok = xs_al(U * 4), o_rows = o_ok + xs_al(U * 4), row = xs_al(U * 8), o_ps = o_rows + (3 * (K + 1) + 1) * row,
-                 o_pc = o_ps + xs_al(part * RgNa<K>::P2 * 8), total = o_pc + xs_al(part * 4);
-    PQ_TRY(pq_ws_reserve(ctx, total));
-    unsigned char *ws = (unsigned char *)ctx->ws;
-    RgUnit un;
-    un.n = (int32_t *)ws;
-    un.ok = (int32_t *)(ws + o_ok);
-    un.mean = (double *)(ws + o_rows);
-    un.b = (double *)(ws + o_rows + (K + 1) * row);
-    un.v = (double *)(ws + o_rows + 2 * (K + 1) * row);
-    un.srr = (double *)(ws + o_rows + 3 * (K + 1) * row);
-    double *ps = (double *)(ws + o_ps);
-    int32_t *pc = (int32_t *)(ws + o_pc);
+    const int64_t nblk = xs_nblk(span);
+    XoWs w;
+    PQ_TRY(xo_workspace(ctx, units, nblk, K + 1, 3 * (K + 1) + 1, RgNa<K>::P2, &w));   // own rows: b, v [K + 1] and srr
+    const RgUnit un{w.n, w.flag, w.mean, w.own, w.own + (K + 1) * w.row, w.own + 2 * (K + 1) * w.row};
+    double *ps = w.ps;
+    int32_t *pc = w.pcnt;
     const dim3 gp((unsigned)((units + 63) / 64), (unsigned)nblk), gu((unsigned)((units + 63) / 64));
     hipStream_t st = ctx->stream;
     hipLaunchKernelGGL((rg_pass_kernel<K, RG_P1, TS>), gp, dim3(64), 0, st, in, un, ps, pc);
-    hipLaunchKernelGGL(rg_means_kernel<K>, gu, dim3(64), 0, st, (const double *)ps, (const int32_t *)pc, nblk, units, un);
+    hipLaunchKernelGGL(xo_means_kernel<K + 1>, gu, dim3(64), 0, st, (const double *)ps, (const int32_t *)pc, nblk, units, un.n, un.mean);
     hipLaunchKernelGGL((rg_pass_kernel<K, RG_P2, TS>), gp, dim3(64), 0, st, in, un, ps, pc);
     hipLaunchKernelGGL(rg_solve_kernel<K>, gu, dim3(64), 0, st, (const double *)ps, nblk, units, un);
     hipLaunchKernelGGL((rg_pass_kernel<K, RG_P3, TS>), gp, dim3(64), 0, st, in, un, ps, pc);
@@ -323,7 +252,7 @@ pq_status rg_dispatch(pq_ctx *ctx, int k, const RgIn &in, const RgOut &out) {
 
 pq_status rg_args(pq_ctx *ctx, const pq_batch *b, const char *what, const double *const *factors, int32_t k, const double *ret, RgIn &in) {
     PQ_TRY(pq_check(ctx, b));
-    if (k < 1 || k > RG_MAX_K) { pq_set_error("%s: k must be in [1, 8]", what); return PQ_ERR_ARG; }
+    if (k < 1 || k > XO_MAX_K) { pq_set_error("%s: k must be in [1, 8]", what); return PQ_ERR_ARG; }
     if (ctx->rec) { pq_set_error("%s cannot be recorded into a suite", what); return PQ_ERR_UNSUPPORTED; }
     if (b->offsets) { pq_set_error("%s: ragged batches are not supported", what); return PQ_ERR_UNSUPPORTED; }
     const bool empty = b->n_series == 0 || b->len == 0;

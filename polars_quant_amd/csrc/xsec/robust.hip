@@ -8,12 +8,13 @@
 //    tile of views at once -- decay: RB_LT lags in registers, the factor read once for the tile and the lag window of the return shared
 //    through the caches (consecutive lanes read consecutive days); sub-group: RB_GT groups in LDS, one [group][lane] column per lane.
 //    One thread per (view, day) then adds the block sums in ascending block order, as ic_combine_kernel does.
-//  * Rank-IC, n_series <= XS_LDS_MAX: each day's valid factor keys and valid return keys are sorted once (LDS bitonic sort), and every
+//  * Rank-IC, n_series <= XS_LDS_MAX: each day's valid factor keys and valid return keys are sorted once (xsec_dev.h's LDS bitonic sort
+//    at its launch shape xs_lds_shape, the LDS half of D-15's day-sort stage; the key load and the searches are this file's), and every
 //    symbol records its tie-run start a_s = #{valid keys of the day < its key}.  Ordering by a_s is ordering by value with ties kept,
 //    on any subset of the day's valid keys.  Decay: per (day, lag) a histogram c[p] = #{members with a_s = p} and its exclusive scan E
 //    give 2 rank_s = 2 E[a_s] + c[a_s] + 1 over the joint members.  Sub-group: the composite key g * 2^14 + a_s of every member is sorted
 //    once per side and day; rank within the group = position - the group's first position, ties kept.  Ranks are half-integers, so the
-//    five rank sums are exact in any order and D-12's closed form gives the same bits as pq_factor_ic.
+//    five rank sums are exact in any order and D-12's closed form (xs_rank_corr, xsec_dev.h) gives the same bits as pq_factor_ic.
 //  * Rank-IC, n_series > XS_LDS_MAX: pq_factor_ic per lag on shifted pointers (decay) or per group on a masked copy of the factor
 //    (sub-group) -- bit-identical by definition.
 //  * Summary rows: rg_summary_row (xsec_ttest.h), D-17's Fama-MacBeth rules; sub-periods are numpy.array_split's contiguous slices.
@@ -241,12 +242,7 @@ __device__ double rb_rank_close(unsigned long long (&v)[5], int nv, unsigned lon
     if (tid == 0) {
         for (int w = 1; w < RB_WAVES; w++)
             for (int k = 0; k < 5; k++) v[k] += red[w][k];
-        if (nv >= 2) {
-            const double nn = (double)nv, Sx = (double)v[0] / 2.0, Sy = (double)v[1] / 2.0, Sxx = (double)v[2] / 4.0, Syy = (double)v[3] / 4.0,
-                         Sxy = (double)v[4] / 4.0;
-            const double vx = nn * Sxx - Sx * Sx, vy = nn * Syy - Sy * Sy;
-            if (vx > 0.0 && vy > 0.0) out = (nn * Sxy - Sx * Sy) / (sqrt(vx) * sqrt(vy));
-        }
+        out = xs_rank_corr(nv, v[0], v[1], v[2], v[3], v[4]);
     }
     __syncthreads(); // red is reused
     return out;
@@ -335,14 +331,7 @@ __global__ __launch_bounds__(RB_THR) void rb_group_rank_kernel(const int32_t *A,
     }
     for (int g = tid; g < G; g += RB_THR) {
         const int nv = gcnt[g];
-        double out = pq_null();
-        if (nv >= 2) {
-            const double nn = (double)nv, Sx = (double)gs[g][0] / 2.0, Sy = (double)gs[g][1] / 2.0, Sxx = (double)gs[g][2] / 4.0,
-                         Syy = (double)gs[g][3] / 4.0, Sxy = (double)gs[g][4] / 4.0;
-            const double vx = nn * Sxx - Sx * Sx, vy = nn * Syy - Sy * Sy;
-            if (vx > 0.0 && vy > 0.0) out = (nn * Sxy - Sx * Sy) / (sqrt(vx) * sqrt(vy));
-        }
-        ic[(int64_t)g * d.len + t] = out;
+        ic[(int64_t)g * d.len + t] = xs_rank_corr(nv, gs[g][0], gs[g][1], gs[g][2], gs[g][3], gs[g][4]);
         n_valid[(int64_t)g * d.len + t] = nv;
     }
 }
@@ -387,18 +376,12 @@ pq_status rb_args(pq_ctx *ctx, const pq_batch *b, const char *what, const double
     return PQ_OK;
 }
 
-int rb_pow2(int64_t n) {
-    int P = 16;
-    while (P < n) P <<= 1;
-    return P;
-}
-
 // the Pearson passes over the views: one thread per (day, block of 256 symbols, tile of views), then one per (view, day)
 template <bool GROUP>
 pq_status rb_pearson(pq_ctx *ctx, const RbIn &in, int tile, double *ic, int32_t *n_valid) {
     const Dims d = in.d;
     const int V = in.V;
-    const int64_t nblk = (d.n + XS_BLOCK - 1) / XS_BLOCK > 0 ? (d.n + XS_BLOCK - 1) / XS_BLOCK : 1;
+    const int64_t nblk = xs_nblk(d.n);
     const dim3 gp((unsigned)((d.len + 63) / 64), (unsigned)nblk, (unsigned)((V + tile - 1) / tile));
     const size_t part = (size_t)V * nblk * d.len * 24, mean = (size_t)V * d.len * 24;
     PQ_TRY(pq_ws_reserve(ctx, xs_al(part) + mean));
@@ -421,10 +404,9 @@ pq_status rb_tie_starts(pq_ctx *ctx, const Dims &d, const double *factor, const 
     PQ_TRY(pq_ws_reserve(ctx, a_bytes + extra));
     A = (int32_t *)ctx->ws;
     rest = (unsigned char *)ctx->ws + a_bytes;
-    const int P = rb_pow2(d.n), nthr = P / 16 < 64 ? 64 : (P / 16 > 1024 ? 1024 : P / 16);
-    const size_t lds = (size_t)(P + P / 16) * 8;
-    PQ_HIP_TRY(hipFuncSetAttribute((const void *)rb_tie_start_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    hipLaunchKernelGGL(rb_tie_start_kernel, dim3((unsigned)d.len, 2), dim3(nthr), lds, ctx->stream, factor, ret, d, P, A);
+    const XsLds sh = xs_lds_shape(d.n);
+    PQ_HIP_TRY(hipFuncSetAttribute((const void *)rb_tie_start_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh.bytes));
+    hipLaunchKernelGGL(rb_tie_start_kernel, dim3((unsigned)d.len, 2), dim3(sh.nthr), sh.bytes, ctx->stream, factor, ret, d, sh.P, A);
     PQ_HIP_TRY(hipGetLastError());
     return PQ_OK;
 }
@@ -485,11 +467,10 @@ pq_status pq_ic_subgroup(pq_ctx *ctx, const pq_batch *b, const double *factor, c
             int32_t *A;
             unsigned char *rest;
             PQ_TRY(rb_tie_starts(ctx, d, factor, fwd_return, (size_t)d.len * d.n * 4, A, rest));
-            const int P = rb_pow2(d.n);
-            const size_t lds = (size_t)(P + P / 16) * 8;
-            PQ_HIP_TRY(hipFuncSetAttribute((const void *)rb_group_rank_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(rb_group_rank_kernel, dim3((unsigned)d.len), dim3(RB_THR), lds, ctx->stream, (const int32_t *)A, group,
-                               group_stride, d, G, P, (int32_t *)rest, ic, n_valid);
+            const XsLds sh = xs_lds_shape(d.n);   // the row's P and bytes; the workgroup is RB_THR threads whatever P
+            PQ_HIP_TRY(hipFuncSetAttribute((const void *)rb_group_rank_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh.bytes));
+            hipLaunchKernelGGL(rb_group_rank_kernel, dim3((unsigned)d.len), dim3(RB_THR), sh.bytes, ctx->stream, (const int32_t *)A, group,
+                               group_stride, d, G, sh.P, (int32_t *)rest, ic, n_valid);
             PQ_HIP_TRY(hipGetLastError());
         } else { // wide: D-12's own Rank-IC on the factor masked to each group
             double *masked = nullptr;

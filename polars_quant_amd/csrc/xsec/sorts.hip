@@ -229,7 +229,7 @@ pq_status xs_groups(pq_ctx *ctx, const pq_batch *b, const double *factor, const 
     if (b->len == 0) return PQ_OK;
     const Dims d = dims_of(b);
     const size_t cells = (size_t)d.len * (size_t)d.n, len = (size_t)d.len;
-    const int64_t nblk = (d.n + XS_BLOCK - 1) / XS_BLOCK > 0 ? (d.n + XS_BLOCK - 1) / XS_BLOCK : 1;
+    const int64_t nblk = xs_nblk(d.n);
     XsDaySort plan;
     PQ_TRY(xs_day_sort_plan(ctx, d, "factor sorts", &plan));
     // workspace: keys (f64, day-major) | n per day (i32) | labels day-major (u8) | labels symbol-major (u8, when the caller passes
@@ -327,7 +327,7 @@ pq_status pq_factor_coverage(pq_ctx *ctx, const pq_batch *b, const double *facto
     int32_t *cnt = (int32_t *)ctx->ws;
     PQ_HIP_TRY(hipMemsetAsync(cnt, 0, (size_t)d.len * 4, ctx->stream));
     if (d.n > 0)
-        hipLaunchKernelGGL(xs_coverage_partial_kernel, dim3((unsigned)((d.len + 63) / 64), (unsigned)((d.n + XS_BLOCK - 1) / XS_BLOCK)),
+        hipLaunchKernelGGL(xs_coverage_partial_kernel, dim3((unsigned)((d.len + 63) / 64), (unsigned)xs_nblk(d.n)),
                            dim3(64), 0, ctx->stream, factor, d, cnt);
     hipLaunchKernelGGL(xs_coverage_final_kernel, dim3((unsigned)((d.len + 255) / 256)), dim3(256), 0, ctx->stream, (const int32_t *)cnt,
                        d.len, d.n, coverage);

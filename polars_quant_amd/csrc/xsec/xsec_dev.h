@@ -1,7 +1,8 @@
-// xsec/xsec_dev.h -- helpers shared by the cross-sectional kernels (sorts.hip: D-15, clean.hip: D-16, regress.hip: D-17, robust.hip:
-// D-18, build.hip: D-20): the summation block, the day-sort stage (D-15: the prep transpose to day-major keys, the LDS bitonic sort of
-// one day's keys, the row accessor and the tie-run search on a sorted row, and the host interface of daysort.hip for rows too wide for
-// LDS), the sequential summaries.
+// xsec/xsec_dev.h -- helpers shared by the cross-sectional kernels: the summation block and its count (every file), the day-sort stage
+// of D-15 (sorts.hip, clean.hip: D-16, build.hip: D-20, and its LDS half also robust.hip: D-18) -- the prep transpose to day-major keys,
+// the LDS bitonic sort of one day's keys and its launch shape, the row accessor and the tie-run search on a sorted row, and the host
+// interface of daysort.hip for rows too wide for LDS --, D-12's rank closed form (robust.hip) and the sequential summaries (sorts.hip,
+// xsec_ttest.h).  The OLS core of regress.hip (D-17) and orth.hip (D-19) is xsec_ols.h.
 #pragma once
 #include "../pq_dev.h"
 
@@ -175,7 +176,20 @@ __device__ void xs_seq(const double *x, int64_t len, double center, double *buf,
     acc = __shfl(acc, 0, 64); // the next pass centres on the mean in every lane
 }
 
+// D-12's closed form: the correlation of nv ranks from the five integer sums of 2 x rank (x, y, x x, y y, x y); NULL below two members
+// or where a side is constant.  csrc/factor.hip keeps its own copy (its files are hashed into the committed counter profile).
+__device__ __forceinline__ double xs_rank_corr(int nv, unsigned long long sx, unsigned long long sy, unsigned long long sxx,
+                                               unsigned long long syy, unsigned long long sxy) {
+    if (nv < 2) return pq_null();
+    const double nn = (double)nv, Sx = (double)sx / 2.0, Sy = (double)sy / 2.0, Sxx = (double)sxx / 4.0, Syy = (double)syy / 4.0,
+                 Sxy = (double)sxy / 4.0;
+    const double vx = nn * Sxx - Sx * Sx, vy = nn * Syy - Sy * Sy;
+    return vx > 0.0 && vy > 0.0 ? (nn * Sxy - Sx * Sy) / (sqrt(vx) * sqrt(vy)) : pq_null();
+}
+
 inline size_t xs_al(size_t x) { return (x + 255) / 256 * 256; }
+// summation blocks over `span` indices, at least one (an empty span still gets its zero sums written)
+inline int64_t xs_nblk(int64_t span) { return span > XS_BLOCK ? (span + XS_BLOCK - 1) / XS_BLOCK : 1; }
 
 } // namespace
 

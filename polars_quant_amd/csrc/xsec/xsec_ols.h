@@ -1,0 +1,124 @@
+// xsec/xsec_ols.h -- the moments and L D L^T core of D-17, shared by regress.hip (D-17) and orth.hip (D-19).
+//
+// D-17's return is one more column behind the factors: with NV = K + 1 columns f_0 .. f_{K-1}, r its pass 2 is the packed lower triangle
+// of the centred cross-products, s[j (j + 1) / 2 + l] = sum d_j d_l (l <= j): C in rows 0 .. K-1, then c and Srr in row K.  D-19's pass 2 is
+// the same triangle of its K factors, so the last level of orthogonalize(K) is regress(K - 1) with r = f_{K-1}.  Both files get from here:
+//  * combine:  one thread per unit adds the block sums in ascending block order from 0.0 (xo_combine); after pass 1 it writes n and
+//              the means (xo_means_kernel).
+//  * solve:    xo_ldl factorises the leading R x R block C = L D L^T by rows and counts the leading pivots that are not singular; it is
+//              prefix-consistent, so the leading k x k block is what D-17 factorises for k regressors.  xo_forward and xo_back solve
+//              on that block.  The operation order is D-17's, restated in tests/xsec_regress_ref.py and tests/xsec_orth_ref.py.
+//  * host:     xo_workspace carves what both workspaces begin with; each caller appends its own rows.
+// The blocked pass kernels, and with them the structs of input columns, stay one per file: one kernel on NV columns compiles to other
+// code for regress.hip and its time-series form ran slower (EXPERIMENTS.md, "One pass kernel for regress.hip and orth.hip").
+#pragma once
+#include "xsec_dev.h"
+
+namespace {
+
+constexpr int XO_MAX_K = 8;             // PQ_REGRESS_MAX_K
+constexpr double XO_SINGULAR = 1e-12;   // pivot D_j <= 1e-12 * C[j][j]: singular
+
+constexpr int xo_tri(int nv) { return nv * (nv + 1) / 2; }                    // entries of the packed triangle; row j starts at xo_tri(j)
+constexpr int xo_ahead(int nv) { return nv <= 2 ? 8 : (nv <= 4 ? 4 : 2); }    // indices loaded ahead: about 16 loads in flight per lane
+
+template <int NA>
+__device__ __forceinline__ void xo_combine(const double *ps, int64_t nblk, int64_t units, int64_t u, double (&s)[NA]) {
+#pragma unroll
+    for (int q = 0; q < NA; q++) s[q] = 0.0;
+    for (int64_t k = 0; k < nblk; k++)
+#pragma unroll
+        for (int q = 0; q < NA; q++) s[q] += ps[(k * NA + q) * units + u];
+}
+
+// after pass 1: n and the NV means, [NV][units]
+template <int NV>
+__global__ __launch_bounds__(64) void xo_means_kernel(const double *ps, const int32_t *pcnt, int64_t nblk, int64_t units, int32_t *n_out,
+                                                      double *mean) {
+    const int64_t u = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (u >= units) return;
+    double s[NV];
+    xo_combine<NV>(ps, nblk, units, u, s);
+    int32_t n = 0;
+    for (int64_t k = 0; k < nblk; k++) n += pcnt[k * units + u];
+    n_out[u] = n;
+    const double dn = (double)n;
+#pragma unroll
+    for (int q = 0; q < NV; q++) mean[(int64_t)q * units + u] = s[q] / dn;
+}
+
+// ---------------------------------------------------------------- solve
+// C = L D L^T by rows on the leading R x R block of the packed triangle s; W[j][k] is the numerator of L[j][k].  Returns the number of
+// leading pivots with D_j > 1e-12 C[j][j]: a NaN pivot (from an overflow) is singular, and so is every pivot behind a singular one.
+template <int R> __device__ __forceinline__ int xo_ldl(const double *s, double (&L)[R][R], double (&D)[R]) {
+    double W[R][R];
+#pragma unroll
+    for (int j = 0; j < R; j++)
+#pragma unroll
+        for (int k = 0; k < R; k++) { L[j][k] = j == k ? 1.0 : 0.0; W[j][k] = 0.0; }
+    int npiv = 0;
+#pragma unroll
+    for (int j = 0; j < R; j++) {
+#pragma unroll
+        for (int k = 0; k < j; k++) {
+            double w = s[xo_tri(j) + k];
+#pragma unroll
+            for (int m = 0; m < k; m++) w -= W[j][m] * L[k][m];
+            W[j][k] = w;
+            L[j][k] = w / D[k];
+        }
+        const double cjj = s[xo_tri(j) + j];
+        double dj = cjj;
+#pragma unroll
+        for (int m = 0; m < j; m++) dj -= W[j][m] * L[j][m];
+        D[j] = dj;
+        if (npiv == j && dj > XO_SINGULAR * cjj) npiv = j + 1;
+    }
+    return npiv;
+}
+
+// forward substitution on the leading k x k block: z_m = v_m - sum_{i < m} L[m][i] z_i (sum ascending from 0.0)
+template <int R> __device__ __forceinline__ void xo_forward(const double (&L)[R][R], const double *v, int k, double (&z)[R]) {
+#pragma unroll
+    for (int m = 0; m < k; m++) {
+        double s = 0.0;
+#pragma unroll
+        for (int i = 0; i < m; i++) s += L[m][i] * z[i];
+        z[m] = v[m] - s;
+    }
+}
+
+// back substitution on the leading k x k block: y_j = z_j / D_j; b_j = y_j - sum_{m > j} L[m][j] b_m (m ascending, from 0.0)
+template <int R>
+__device__ __forceinline__ void xo_back(const double (&L)[R][R], const double (&D)[R], const double (&z)[R], int k, double (&b)[R]) {
+#pragma unroll
+    for (int j = k - 1; j >= 0; j--) {
+        double t = 0.0;
+#pragma unroll
+        for (int m = j + 1; m < k; m++) t += L[m][j] * b[m];
+        b[j] = z[j] / D[j] - t;
+    }
+}
+
+// ---------------------------------------------------------------- host
+// workspace: n, flag (i32) | `rows` f64 rows, `row` doubles apart: the nv means, then the caller's own | block partials [nblk][na][units]
+// (f64) | block counts (i32)
+struct XoWs {
+    int32_t *n, *flag;
+    double *mean, *own;   // own = the caller's rows, behind the nv means
+    size_t row;
+    double *ps;
+    int32_t *pcnt;
+};
+inline pq_status xo_workspace(pq_ctx *ctx, int64_t units, int64_t nblk, int nv, int rows, int na, XoWs *w) {
+    const size_t U = (size_t)units, part = (size_t)nblk * U;
+    const size_t o_flag = xs_al(U * 4), o_rows = o_flag + xs_al(U * 4), row = xs_al(U * 8), o_ps = o_rows + (size_t)rows * row,
+                 o_pc = o_ps + xs_al(part * na * 8), total = o_pc + xs_al(part * 4);
+    PQ_TRY(pq_ws_reserve(ctx, total));
+    unsigned char *ws = (unsigned char *)ctx->ws;
+    *w = XoWs{(int32_t *)ws, (int32_t *)(ws + o_flag), (double *)(ws + o_rows), (double *)(ws + o_rows + nv * row), row / 8,
+              (double *)(ws + o_ps), (int32_t *)(ws + o_pc)};
+    return PQ_OK;
+}
+
+} // namespace

@@ -1,10 +1,12 @@
 """-m gpu: multi-factor orthogonalization and neutralization of D-19 (csrc/xsec/orth.hip, Factor().clean(factors, method)) against the
 numpy restatement in tests/xsec_orth_ref.py, bit for bit; the in-place form against the out-of-place one; cross-checks through the D-17
-regression (the residuals carry no loading on their regressors) and the D-16 size neutralization (bit identity)."""
+regression (the residuals carry no loading on their regressors; the last level is D-17 bit for bit) and the D-16 size neutralization
+(bit identity)."""
 import numpy as np
 import pytest
 
 import xsec_orth_ref as O
+from xsec_clean_ref import bsum
 
 pytestmark = pytest.mark.gpu
 
@@ -135,6 +137,29 @@ def test_residuals_have_no_loading_on_their_regressors(pq):
             ok = ~np.isnan(coef)
             assert ok.sum() >= 10 * len(regs)
             assert np.abs(coef[ok]).max() <= 1e-12 * scale, (k, len(regs), np.abs(coef[ok]).max())
+
+
+def test_last_level_is_the_regression_of_the_last_factor(pq):
+    """orthogonalize(K)'s last level is regress(K - 1) with r = f_{K-1}: the slopes pq_xsec_regress returns for f_3 on f_0 .. f_2, put
+    through D-17's pass 3 in numpy (e = (f_3 - fbar_3) - fit, fit = 0.0; fit += b_j (f_j - fbar_j) for ascending j, the means from the
+    restatement's blocked sums), are residual 3 of pq_factor_orthogonalize bit for bit on every member.  K = 4, two summation blocks."""
+    from polars_quant_amd import api
+    K, n, T = 4, 300, 5
+    F = make(K, n, T, 321, special=False)
+    holes = np.random.default_rng(322).random((K, n, T)) < 0.02
+    F[holes] = np.nan
+    mem = O.joint(F)
+    assert holes.any(axis=0).any(axis=0).all() and (mem.sum(axis=0) > 256).all() and mem[256:].any(axis=0).all()
+    coef = api.xsec_regress([to_dev(f) for f in F[:K - 1]], to_dev(F[K - 1]), summary=False)["coef"].cpu().numpy()
+    assert coef.shape == (K, T) and np.isfinite(coef).all()
+    dn = mem.sum(axis=0).astype(np.float64)
+    with np.errstate(all="ignore"):
+        fit = np.zeros((n, T))
+        for j in range(K - 1):
+            fit = fit + coef[j] * (F[j] - bsum(F[j], mem) / dn)
+        e = (F[K - 1] - bsum(F[K - 1], mem) / dn) - fit
+    got = pq.Factor().clean([to_dev(f) for f in F], method="orthogonalize").cpu().numpy()[K - 1]
+    same("residual 3 on the members", got[mem], e[mem])
 
 
 @pytest.mark.parametrize("K", [2, 3, 8])

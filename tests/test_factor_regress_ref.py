@@ -104,6 +104,36 @@ def test_sample_excludes_null_nan_inf_in_any_column():
     assert out1["n"][0] == 4 and np.array_equal(out1["coef"].view(np.uint64), ref1["coef"].view(np.uint64))
 
 
+def pivot_table(K, seed, n=40):
+    """K factors and a return [n, K + 2] on which the first singular pivot of C = L D L^T sits at every position in turn -> day 0:
+    f_0 constant (pivot 0 is 0); day j, 1 <= j < K: f_j = 2 f_{j-1} + 3 (pivot j is rounding noise behind j healthy ones, and every
+    pivot after it is computed from that noise); day K: every factor scaled by 1e160, so C[0][0] overflows and the later pivots are
+    NaN; day K + 1: untouched.  Every symbol is a member on every day."""
+    rng = np.random.default_rng(seed)
+    F = rng.standard_normal((K, n, K + 2))
+    r = (0.1 * np.arange(1, K + 1)[:, None, None] * F).sum(0) + 0.5 * rng.standard_normal((n, K + 2))
+    F[0, :, 0] = 0.375
+    for j in range(1, K):
+        F[j, :, j] = 2.0 * F[j - 1, :, j] + 3.0
+    F[:, :, K] *= 1e160
+    return F, r
+
+
+@pytest.mark.parametrize("K", [3, 8])
+def test_failing_pivot_at_every_position(K):
+    """a day is solved only when all K pivots pass: NULL coefficients on the days whose pivot 0 .. K-1 fails (an interior failure leaves
+    later pivots that may well pass on their own) and on the overflow day, a solution on the untouched day"""
+    F, r = pivot_table(K, 60 + K)
+    out = R.xsec_regress(list(F), r)
+    assert (out["n"] == 40).all()
+    for k in ("coef", "t", "p"):
+        assert R.isnull(out[k][:, :K + 1]).all(), k
+    assert R.isnull(out["r2"][:K + 1]).all()
+    assert np.isfinite(out["coef"][:, K + 1]).all() and np.isfinite(out["t"][:, K + 1]).all() and np.isfinite(out["r2"][K + 1])
+    ts = R.ts_regress([f.T for f in F], r.T)                      # the same table with the days as symbols
+    assert R.isnull(ts["coef"][:K + 1]).all() and np.isfinite(ts["coef"][K + 1]).all() and (ts["n"] == 40).all()
+
+
 # ---- against scipy / numpy
 def test_k1_against_linregress():
     rng = np.random.default_rng(5)

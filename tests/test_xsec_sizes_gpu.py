@@ -15,6 +15,9 @@ Where each branch is reached (the failure tags name function, shape, Q / K / L /
 | rg_dispatch<K, true>, K = 4, 5, 6, 7            | test_ts_regress_every_k[K4-*, K5-*, K6-*, K7-*]                               |
 | CPU pin of K = 4 .. 7 against lstsq             | test_factor_regress_ref.py: test_against_lstsq_and_inverse_normal_equations,  |
 |                                                 |   test_time_series_form_against_lstsq                                         |
+| xo_ldl's count of leading good pivots: the      | test_regress_failing_pivot_at_every_position[K3, K8]: test_factor_regress_    |
+|   first singular pivot at j = 0 .. K - 1, an    |   ref.pivot_table, NULL days asserted on the expected; K8 also transposed     |
+|   overflowing C[0][0] with NaN pivots behind it |   through pq_ts_regress (K + 2 symbols, 40 days)                              |
 | xs_seq at T = 2 047, 2 048, 2 049, 4 097        | test_sequential_summaries_across_chunks[T2047, T2048, T2049, T4097]           |
 | ic_stats past one chunk                         |   (also the group / long-short and Fama-MacBeth summaries)                    |
 | D-12 blocks of 256: 255, 256, 257, 512, 513     | symbols per day: test_sort_size_classes[n255, n256, n257],                    |
@@ -101,6 +104,7 @@ import test_factor_clean_gpu as CL
 import test_factor_orth_gpu as OG
 import test_factor_orth_ref as OR
 import test_factor_regress_gpu as RG
+import test_factor_regress_ref as RR
 import test_factor_robust_gpu as RB
 import test_factor_sorts_gpu as S
 import xsec_ref as X
@@ -242,6 +246,18 @@ def test_ts_regress_every_k(pq, K, T):
         ser[0][::97] = X.NULL
         _, exp = RG.check_ts(pq, ser, r)
         assert exp["r2"][3] == 1.0 and exp["n"][3] == T - len(range(0, T, 97))
+
+
+@pytest.mark.parametrize("K", [3, 8], ids=["K3", "K8"])
+def test_regress_failing_pivot_at_every_position(pq, K):
+    """test_factor_regress_ref.pivot_table: the first singular pivot at every position 0 .. K - 1 and an overflow day; a day whose
+    interior pivot fails is NULL although later pivots, computed from garbage, may pass.  K = 8 also in the time-series form."""
+    F, r = RR.pivot_table(K, 60 + K)
+    _, exp = RG.check_xsec(pq, F, r)
+    assert RG.R.isnull(exp["coef"][:, :K + 1]).all() and np.isfinite(exp["coef"][:, K + 1]).all() and (exp["n"] == 40).all()
+    if K == 8:
+        _, exp = RG.check_ts(pq, [np.ascontiguousarray(f.T) for f in F], np.ascontiguousarray(r.T))
+        assert RG.R.isnull(exp["coef"][:K + 1]).all() and np.isfinite(exp["coef"][K + 1]).all()
 
 
 @pytest.mark.parametrize("T", SEQ_TS, ids=[f"T{t}" for t in SEQ_TS])
