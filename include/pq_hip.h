@@ -551,6 +551,23 @@ pq_status pq_ts_regress(pq_ctx *, const pq_batch *, const double *const *factors
 /* correlation t-test: t = corr sqrt((n - 2) / (1 - corr corr)), p on n - 2; NULL where corr is NaN, n < 3 or 1 - corr^2 == 0 */
 pq_status pq_corr_t_test(pq_ctx *, const double *corr, const int32_t *n_valid, int64_t len, double *t_stat, double *p_value);
 
+/* ---- linear regression, linear(df, x_cols, y_col, pred_col, resid_col, return_stats) (README.md:165-240; README-only, decision D-24
+ * in DESIGN.md section 2): ONE pooled fit y = a + sum_j b_j x_j, 1 <= k <= PQ_REGRESS_MAX_K, over all rows of the columns.  x is a HOST
+ * array of k device pointers; x[j], y, pred and resid are f64 [n_series][stride] on the batch's row pitch (a flat column is n_series = 1),
+ * and the logical row index is s * len + t.  A member is a row where y and all k regressors are non-null and finite.  D-17's three passes
+ * and its C = L D L^T solve; the sums run over tiles of PQ_LINEAR_TILE logical rows and then over the tile partials, PQ_LINEAR_STAGE2 per
+ * step, each folded in a fixed tree (D-24), so coef / t / R^2 / n / pred / resid are bit-exact and do not depend on the row pitch.
+ * pred = a + sum_j b_j x_j wherever all k regressors are valid (also where y is not), resid = y - pred on the members, NULL elsewhere;
+ * both may be NULL pointers together (statistics only).  coef / t_stat / p_value: [k + 1], slopes first and the intercept last, p on
+ * n - k - 1 degrees of freedom; r2 = 1 - sum resid^2 / Syy; n: the members.  These scalars are ALWAYS written, an empty batch included
+ * (n = 0), unlike D-17's per-unit arrays: coef, t, p, R^2 -- and every pred / resid cell -- are NULL where n < k + 2 or a pivot
+ * D_j <= 1e-12 C[j][j]; t and p NULL where se == 0; R^2 NULL where Syy == 0.  Ragged batches and suite recording are refused.  Uses the
+ * context workspace (~8 (k + 1)(k + 2) / 2 bytes per tile). */
+#define PQ_LINEAR_TILE 4096
+#define PQ_LINEAR_STAGE2 256
+pq_status pq_linear(pq_ctx *, const pq_batch *, const double *const *x, int32_t k, const double *y, double *coef, double *t_stat,
+                    double *p_value, double *r2, int64_t *n, double *pred, double *resid);
+
 /* ---- rank 3, continued: multi-factor orthogonalization and neutralization, Factor().clean(factors, method) (README.md:1495-1519;
  * README-only, decision D-19 in DESIGN.md section 2).  factors is a HOST array of k device pointers, 2 <= k <= PQ_REGRESS_MAX_K, and out
  * a HOST array of k - 1, all on the batch's row pitch.  Per day, the sample is every symbol whose k factors are all non-null and finite.

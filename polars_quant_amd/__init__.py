@@ -9,6 +9,7 @@ from ._lib import NullsNotAllowed, PqError
 from ._spec import PATTERN_NAMES, SPEC, SUMMARY_KEYS
 from .backtest import Backtest, VectorizedBacktester
 from .factor import Factor, clean
+from .linear import linear
 from .returns import returns
 from .sequential import OrderContext, OrderTape, SequentialBacktester
 from .strategy import Strategy

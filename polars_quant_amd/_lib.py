@@ -142,6 +142,8 @@ def lib() -> C.CDLL:
         L.pq_factor_ic.argtypes = [vp, C.POINTER(Batch), vp, vp, C.c_int32, vp, vp]
         L.pq_factor_rolling.restype = C.c_int32
         L.pq_factor_rolling.argtypes = [vp, C.POINTER(Batch), vp, C.c_int32, C.c_int64, C.c_int64, vp]
+        L.pq_linear.restype = C.c_int32
+        L.pq_linear.argtypes = [vp, C.POINTER(Batch), C.POINTER(vp), C.c_int32] + [vp] * 8
         L.pq_rolling_ic.restype = C.c_int32
         L.pq_rolling_ic.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp]
         L.pq_backtest_leveraged.restype = C.c_int32

@@ -684,6 +684,53 @@ def corr_t_test(corr, n_valid):
     return t, p
 
 
+LINEAR_TILE = 4096            # PQ_LINEAR_TILE: logical rows per workgroup tile of pq_linear's sums
+LINEAR_STAGE2 = 256           # PQ_LINEAR_STAGE2: tile partials per step of its second stage
+
+
+def linear(xs, y, outputs: bool = True):
+    """D-24: one pooled OLS y = a + sum_j b_j x_j over all rows of the columns.  xs: K columns (a list, or one [K, ...] array), each [M]
+    or [N, T] in the shape of y -> dict of device tensors: coef / t_stat / p_value [K + 1] (slopes first, the intercept last),
+    r_squared and n (int64) 0-dim, and with outputs=True pred (wherever every x is valid) and resid (on the members) in the shape of y"""
+    ys = _shape(y)
+    if len(ys) not in (1, 2):
+        raise ValueError(f"y must be [M] or [N, T], not {ys}")
+    if isinstance(xs, (list, tuple)):
+        cols = list(xs)
+    else:
+        fs = _shape(xs)
+        if len(fs) != len(ys) + 1:
+            raise ValueError(f"xs must be a list of columns shaped like y or one [K, ...] array, not {fs}")
+        cols = [xs[j] for j in range(fs[0])]
+    if not 1 <= len(cols) <= REGRESS_MAX_K:
+        raise ValueError(f"the number of regressors must be in 1..{REGRESS_MAX_K}, not {len(cols)}")
+    for j, c in enumerate(cols):
+        if _shape(c) != ys:
+            raise ValueError(f"x column {j} must have shape {ys}, not {_shape(c)}")
+    K = len(cols)
+    mats = [_to_device(c)[0] for c in cols] + [_to_device(y)[0]]
+    if mats[-1].numel():          # (an empty column has no layout to agree on, and no pointer is passed)
+        mats = _same_layout(mats)
+    r = mats[-1]
+    dev = r.device
+    n, T = r.shape
+    b = _batch_of(r)
+    vp = C.c_void_p
+    ptrs = (vp * K)(*[m.data_ptr() for m in mats[:-1]])
+    f64 = dict(dtype=torch.float64, device=dev)
+    coef, t, p = (torch.empty(K + 1, **f64) for _ in range(3))
+    r2, nobs = torch.empty((), **f64), torch.empty((), dtype=torch.int64, device=dev)
+    cols_out = [torch.empty_strided((n, T), (b.stride, 1), **f64) for _ in range(2)] if outputs else [None, None]
+    with torch.cuda.device(dev):
+        check(lib().pq_linear(ctx(dev.index), C.byref(b), ptrs if n and T else None, C.c_int32(K), vp(r.data_ptr()) if n and T else None,
+                              vp(coef.data_ptr()), vp(t.data_ptr()), vp(p.data_ptr()), vp(r2.data_ptr()), vp(nobs.data_ptr()),
+                              *[vp(o.data_ptr()) if o is not None and o.numel() else None for o in cols_out]))
+    out = {"coef": coef, "t_stat": t, "p_value": p, "r_squared": r2, "n": nobs}
+    if outputs:
+        out["pred"], out["resid"] = (o[0] if len(ys) == 1 else o for o in cols_out)
+    return out
+
+
 ORTH_MODES = {"orthogonalize": 0, "neutralize": 1}
 
 
