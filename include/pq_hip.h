@@ -478,6 +478,29 @@ pq_status pq_backtest_sequential(pq_ctx *, int64_t n_tapes, int64_t n_periods, i
                                  const double *benchmark, const pq_seq_params *params, int64_t n_params, double *equity, double *cash,
                                  double *position, int64_t *counts, double *summary);
 
+/* ---- ParameterSweep (decision D-25 in DESIGN.md): a grid of strategy parameter sets backtested in ONE launch, one lane per parameter
+ * set, one wavefront per symbol and 64 consecutive parameter sets.  lines: HOST array of n_lines device columns, each [n_series][stride]
+ * like price (candidate indicator columns: every distinct moving average once, ...).  params: DEVICE table; set i trades
+ *   rule 0  cross(lines[a], lines[b])  buy = a[t-1] <= b[t-1] && a[t] > b[t], sell = a[t-1] >= b[t-1] && a[t] < b[t]  (oracle/backtest.c:263-270)
+ *   rule 1  band(lines[a], k0, k1)     buy = a[t-1] < k0 && a[t] >= k0,       sell = a[t-1] > k1 && a[t] <= k1        (oracle/backtest.c:271-278; b unused)
+ * (a NULL or NaN compares false, row 0 never signals) through the scan of pq_backtest_vectorized (vectorized.rs:124-194: a null price
+ * is a NaN, a NaN or non-positive price leaves the state untouched, quantity = floor(deploy / exec), fee = max(cost * rate, min_commission),
+ * a buy that cannot afford one share is no trade) into calculate_summary (metrics.rs:7-152) in the reference's left-to-right order.
+ * summary [n_series][n_params][PQ_SUMMARY_COLS] is the ONLY output: no signal, position, cash or equity value is written to memory.
+ * max_drawdown, max_profit, win_rate and total_trades equal the reference bit for bit, the others up to the device pow.
+ * benchmark: NULL, or one [len] series shared by all symbols (bench_series_stride = 0), or series s at benchmark + s * bench_series_stride.
+ * Before anything is launched the table is copied to the host and checked (synchronises the stream): an unknown rule, a outside
+ * [0, n_lines), or b outside it under rule 0 is PQ_ERR_ARG, as is n_lines outside [1, PQ_SWEEP_MAX_LINES].  n_params = 0 or n_series = 0
+ * launches nothing; len = 0 writes zeros (metrics.rs:17-19).  Ragged batches and suite recording: PQ_ERR_UNSUPPORTED.  Uses the context
+ * workspace for the line table.  pq_sweep_row_tile: the rows of one LDS tile for n_lines lines (0: n_lines is out of range). */
+typedef struct { int32_t rule, a, b, _pad; double k0, k1; } pq_sweep_param;
+#define PQ_SWEEP_MAX_LINES 512
+pq_status pq_backtest_sweep(pq_ctx *, const pq_batch *, const double *price, const double *const *lines, int32_t n_lines,
+                            const pq_sweep_param *params /* device */, int64_t n_params,
+                            const double *benchmark, int64_t bench_series_stride /* 0: one [len] series shared by all */,
+                            const pq_bt_params *bt, double *summary /* [n_series][n_params][8] */);
+int32_t pq_sweep_row_tile(int32_t n_lines);
+
 /* ---- cross-sectional factor evaluation, Factor.ic / rank_ic / rolling_ic (README.md:1429-1430,
  * :1480-1482, :1626-1634; README-only, decision D-12 in oracle/backtest.c).  factor / fwd_return: [n_series][stride];
  * per day the cross-section = symbols where both values are non-null and finite.  method 0: Pearson IC (sums over

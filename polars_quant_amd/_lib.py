@@ -157,6 +157,10 @@ def lib() -> C.CDLL:
         L.pq_backtest_sequential.restype = C.c_int32
         L.pq_backtest_sequential.argtypes = [vp, C.c_int64, C.c_int64, C.c_int32, vp, vp, vp, vp, C.c_int64, vp, C.POINTER(SeqParams),
                                              C.c_int64, vp, vp, vp, vp, vp]
+        L.pq_backtest_sweep.restype = C.c_int32
+        L.pq_backtest_sweep.argtypes = [vp, C.POINTER(Batch), vp, C.POINTER(vp), C.c_int32, vp, C.c_int64, vp, C.c_int64, C.POINTER(BtParams), vp]
+        L.pq_sweep_row_tile.restype = C.c_int32
+        L.pq_sweep_row_tile.argtypes = [C.c_int32]
         L.pq_recommended_stride.restype = C.c_int64
         L.pq_recommended_stride.argtypes = [C.c_int64]
         L.pq_layout_check.restype = C.c_int32

@@ -1339,3 +1339,75 @@ def macd_cross_signals(close, fastperiod=12, slowperiod=26, signalperiod=9):
                                           signalperiod, C.c_void_p(bu.data_ptr()), C.c_void_p(se.data_ptr())))
     k = kind if kind in (_Kind.TORCH, _Kind.NUMPY) else _Kind.NUMPY
     return _from_device(bu, k, squeeze), _from_device(se, k, squeeze)
+
+
+# pq_sweep_param (include/pq_hip.h): one parameter set of backtest_sweep -- rule 0: cross(lines[a], lines[b]); 1: band(lines[a], k0, k1)
+SWEEP_PARAM_DTYPE = np.dtype([("rule", "<i4"), ("a", "<i4"), ("b", "<i4"), ("_pad", "<i4"), ("k0", "<f8"), ("k1", "<f8")])
+SWEEP_MAX_LINES = 512
+
+
+def SWEEP_ROW_TILE(n_lines: int) -> int:
+    """pq_sweep_row_tile: the rows of one LDS tile of the sweep kernel for n_lines lines (0: n_lines is out of range)"""
+    return int(lib().pq_sweep_row_tile(int(n_lines)))
+
+
+def sweep_params(rules) -> np.ndarray:
+    """a SWEEP_PARAM_DTYPE array from one, or from a dict of equally long rule / a / b / k0 / k1 columns (missing ones are 0)"""
+    if isinstance(rules, np.ndarray) and rules.dtype == SWEEP_PARAM_DTYPE:
+        return np.ascontiguousarray(rules.reshape(-1))
+    if not isinstance(rules, dict) or "rule" not in rules or "a" not in rules:
+        raise ValueError("rules must be a SWEEP_PARAM_DTYPE array or a dict with at least the columns 'rule' and 'a'")
+    unknown = set(rules) - {"rule", "a", "b", "k0", "k1"}
+    if unknown:
+        raise ValueError(f"unknown rule columns {sorted(unknown)}")
+    out = np.zeros(len(np.atleast_1d(rules["rule"])), dtype=SWEEP_PARAM_DTYPE)
+    for k, v in rules.items():
+        v = np.atleast_1d(np.asarray(v))
+        if v.shape != out.shape:
+            raise ValueError(f"rule column {k!r} has shape {v.shape}, expected {out.shape}")
+        out[k] = v
+    return out
+
+
+def backtest_sweep(price, lines, params, benchmark=None, out=None, offsets=None, **kw):
+    """D-25: every parameter set of `params` (sweep_params) over every symbol in ONE launch -> device summary [P, N, 8], a permuted
+    view of the kernel's [N, P, 8].  price [N, T]; lines: a list of [N, T] candidate indicator columns or one [L, N, T] array;
+    benchmark: None, one [T] series shared by all symbols, or [N, T]; out: a contiguous device [N, P, 8] float64 tensor to write into;
+    offsets: ragged groups of long columns (see call()) are not supported by the sweep and raise."""
+    prm = BtParams(**{**BT_DEFAULTS, **kw})
+    tab = sweep_params(params)
+    cols = list(lines) if isinstance(lines, (list, tuple)) else [lines[j] for j in range(_shape(lines)[0])]
+    if not 1 <= len(cols) <= SWEEP_MAX_LINES:
+        raise PqError(f"backtest_sweep: the number of lines must be in 1..{SWEEP_MAX_LINES}, not {len(cols)}")
+    mats = _same_layout([_to_device(price)[0]] + [_to_device(c)[0] for c in cols])
+    p = mats[0]
+    dev = p.device
+    n, T = p.shape
+    b = _batch_of(p)
+    keep = None
+    if offsets is not None:
+        b, keep = ragged_batch(offsets, dev)
+    P = len(tab)
+    bm, bstride = None, 0
+    if benchmark is not None:
+        bm = _to_device(benchmark)[0]
+        if bm.shape == (1, T):
+            bm = bm.contiguous()
+        elif bm.shape == (n, T):
+            bstride = bm.stride(0)
+        else:
+            raise PqError(f"backtest_sweep: `benchmark` has shape {tuple(bm.shape)}, expected {(T,)} or {(n, T)}")
+    if out is None:
+        out = torch.empty((n, P, 8), dtype=torch.float64, device=dev)
+    elif tuple(out.shape) != (n, P, 8) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"out must be a contiguous float64 tensor of shape {(n, P, 8)} on {dev}")
+    if n and P:
+        dtab = torch.from_numpy(tab.view(np.uint8).reshape(P, SWEEP_PARAM_DTYPE.itemsize)).to(dev)
+        vp = C.c_void_p
+        ptrs = (vp * len(cols))(*[m.data_ptr() for m in mats[1:]])
+        with torch.cuda.device(dev):
+            check(lib().pq_backtest_sweep(ctx(dev.index), C.byref(b), vp(p.data_ptr()), ptrs, C.c_int32(len(cols)), vp(dtab.data_ptr()),
+                                          C.c_int64(P), vp(bm.data_ptr()) if bm is not None else None, C.c_int64(bstride),
+                                          C.byref(prm), vp(out.data_ptr())))
+    del keep
+    return out.permute(1, 0, 2)
