@@ -9,6 +9,8 @@
 //   PQ_EXP_NOCOMPUTE     outputs = the first input: the traffic and the hand-off machinery alone
 //   PQ_EXP_STOREONLY     the store replica: the storer waves of the tiled job bodies issue exactly the step's stores (grids, addresses, piece
 //                        sizes, non-temporal policy) from register values; the compute wave returns at once, no LDS traffic, no barriers
+//   PQ_EXP_ASSIST        assisted stores: the compute wave of an op with an ASSIST trait stores that many columns of every out tile itself
+//                        (pq_dev.h; measured and not taken: a product build reads every trait as 0);  PQ_EXP_ASSIST_ADD=<n>  n columns more
 //   PQ_PROFILE_WAVES     s_memtime accounting of the compute wave per job kind (load wait + LDS fill, rows, hand-off), SIMD histogram
 //   PQ_STORER_ACC=2|4    the storer wave keeps 2 / 4 out tiles and stores them back to back
 //   PQ_PF2_MAX=<n>       a second tile of register prefetch for ops whose inputs need <= n VGPRs
@@ -33,6 +35,14 @@
 #else
 #define PQ_EXP_SO_ALLPAIR_ON 0
 #endif
+#if defined(PQ_EXPERIMENTS) && defined(PQ_EXP_ASSIST_ADD) // every assisted op drains PQ_EXP_ASSIST_ADD columns more (or, negative, fewer)
+#define PQ_ASSIST_MAX (NOUT - (NIN > 1 ? NIN : 1)) // (NIN, NOUT: constants of run_seq_lds)
+#define PQ_HOOK_ASSIST(n) ((n) > 0 ? ((n) + (PQ_EXP_ASSIST_ADD) < 0 ? 0 : ((n) + (PQ_EXP_ASSIST_ADD) > PQ_ASSIST_MAX ? PQ_ASSIST_MAX : (n) + (PQ_EXP_ASSIST_ADD))) : 0)
+#elif defined(PQ_EXPERIMENTS) && defined(PQ_EXP_ASSIST)
+#define PQ_HOOK_ASSIST(n) (n)
+#else
+#define PQ_HOOK_ASSIST(n) 0 // the product: the plain two-wave form for every op
+#endif
 // (SO: a constant of run_seq_lds -- the replica applies to this op)
 #define PQ_HOOK_STORER_BARRIER() do { if constexpr (!SO) __builtin_amdgcn_s_barrier(); } while (0)
 #define PQ_HOOK_STORER_PULL(q, kk, i) (SO ? make_double2((double)(kk), (double)((i) + lane)) : make_double2((q)[0], (q)[1]))
@@ -42,7 +52,7 @@
 // ---------------------------------------------------------------- product: the plain operations
 #define PQ_HOOK_STORE2(w, ptr) __builtin_nontemporal_store((w), (ptr))
 #define PQ_HOOK_ROW_STORE(v, ptr) __builtin_nontemporal_store((v), (ptr))
-#define PQ_HOOK_TILE_LOAD(src, t0, i) (*reinterpret_cast<const double2 *>(src))
+#define PQ_HOOK_TILE_LOAD(src, t0, i) g_load2(src)
 #define PQ_HOOK_FAST_OK(cond) (cond)
 #define PQ_HOOK_FAST_ROWS(Op, FU, NOUT, op, t, xs, ys) fast_rows<Op, FU>(op, t, xs, ys)
 #define PQ_PROF_T(v)
@@ -66,7 +76,7 @@
 #ifdef PQ_EXP_NOLOAD
 #define PQ_HOOK_TILE_LOAD(src, t0, i) make_double2((double)(t0), (double)(i))
 #else
-#define PQ_HOOK_TILE_LOAD(src, t0, i) (*reinterpret_cast<const double2 *>(src))
+#define PQ_HOOK_TILE_LOAD(src, t0, i) g_load2(src)
 #endif
 #ifdef PQ_EXP_NOCOMPUTE
 #define PQ_HOOK_FAST_OK(cond) (true)

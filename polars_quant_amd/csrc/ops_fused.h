@@ -169,6 +169,7 @@ struct SmaDupOp {
     static constexpr bool LDS_ONLY = true;
     static constexpr int NIN = 1, NOUT = 2;
     static constexpr int SEQ_ID = 88;
+    static constexpr int ASSIST = 1;   // (PQ_EXP_ASSIST builds, pq_dev.h Assist: one column per wave)
     static constexpr int ALG_COLS = 4; // the two calls it replaces
     static constexpr int COST_NS = 130;
     SmaOp a;
@@ -971,6 +972,13 @@ struct MavpBlockOp {
 // Two SEQ ops over the SAME input columns as one job: one in-tile, one walk, the outputs side by side.  The sub-ops keep
 // their own state machines (bit-identical results); what is shared is the tile traffic, the per-tile hand-off and the
 // workgroup -- the expensive parts for short jobs.  Nests: Fuse2<ID, Fuse2<0, A, B>, Fuse2<0, C, D>>.
+// Output columns that the compute wave of a fused job drains itself in a PQ_EXP_ASSIST build (pq_dev.h Assist; measured and not taken),
+// by job id.  Nonzero where the wave profile showed the compute wave waiting at the hand-off for clearly longer than it walks rows; the
+// count balances fill + rows + its stores against the storer's remaining columns.  Compute-bound fused jobs (96, 97, 98, 89, 95): 0.
+template <int ID> struct FuseAssist { static constexpr int value = 0; };
+template <> struct FuseAssist<94> { static constexpr int value = 2; }; // macd + macdfix: 6 columns, 2 096 cycles of rows per tile
+// (99, dmi + atr, is store-bound too, but its compute wave has no registers left for the stores under the light kernel's 192-VGPR cap: 0)
+template <> struct FuseAssist<90> { static constexpr int value = 1; }; // ema, dema, tema, trix: 4 columns
 template <int ID, class A, class B>
 struct Fuse2 {
     static_assert(A::NIN == B::NIN, "fused ops must read the same input columns");
@@ -980,6 +988,7 @@ struct Fuse2 {
     static constexpr int NIN = A::NIN, NOUT = A::NOUT + B::NOUT;
     static constexpr int ALG_COLS = AlgCols<A>::value + AlgCols<B>::value; // the calls it replaces
     static constexpr int SEQ_ID = ID;
+    static constexpr int ASSIST = FuseAssist<ID>::value;
     __host__ int cost_ns() const { return (3 * (OpCost<A>::get(a) + OpCost<B>::get(b))) / 4; } // one walk, shared tile traffic
     static constexpr bool HEAVY = IsHeavy<A>::value || IsHeavy<B>::value;
     static constexpr bool LDS_ONLY = true; // (the gather driver's tap plumbing is per op)

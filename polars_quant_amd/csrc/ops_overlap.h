@@ -55,6 +55,7 @@ struct BbandsOp { // overlap.rs:47-116
     static constexpr int NIN = 1, NOUT = 3;
     static constexpr int SEQ_ID = 3;
     static constexpr int COST_NS = 263;
+    static constexpr int ASSIST = 1; // (PQ_EXP_ASSIST builds, pq_dev.h Assist)
     static constexpr int NTAP = 1;
     static constexpr int TAP_COL[1] = {0};
     int64_t p;

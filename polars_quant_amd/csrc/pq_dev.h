@@ -142,6 +142,14 @@ template <class Op, class = void>
 struct HasFinish { static constexpr bool value = false; }; // void finish(double *const *outp, const Dims &, int64_t s): per-series epilogue
 template <class Op>
 struct HasFinish<Op, decltype((void)&Op::finish)> { static constexpr bool value = true; };
+// Assisted stores, an A/B form (experiments.h PQ_EXP_ASSIST; a product build reads every trait as 0): `static constexpr int ASSIST = n;`
+// makes the COMPUTE wave of the tiled body drain the last n output columns of every tile itself (run_seq_lds) -- a second store issuer
+// without a third wave, same values to the same addresses.  Measured after the storer stopped waiting for every store (`uniform` in
+// run_seq_lds): 3.60 against 3.59 ms per step, not taken (EXPERIMENTS.md); the traits record the split that was measured.
+template <class Op, class = void>
+struct Assist { static constexpr int value = 0; };
+template <class Op>
+struct Assist<Op, decltype((void)Op::ASSIST)> { static constexpr int value = Op::ASSIST; };
 
 template <int N>
 struct InCols {
@@ -469,7 +477,9 @@ constexpr size_t SEQ_LDS_LIMIT = 64 * 1024; // above this an op falls back to th
 // and stores in ONE counter (vmcnt), loads retire in order but stores do not, so a wave with stores in flight cannot wait
 // for a prefetched load without also waiting for every store it has issued (measured: a tile copy by one wave runs at
 // ~1 TB/s, split across a loading and a storing wave at ~2 TB/s, scripts/ubench/).  With the stores in another wave,
-// wave 0's counter holds loads only and the prefetch is waited for exactly; wave 1 never waits on vmcnt at all.
+// wave 0's counter holds loads only and the prefetch is waited for exactly; wave 1 never waits on vmcnt at all -- PROVIDED its column
+// pointers sit in registers: until they were read once per workgroup (run_seq_lds, `uniform`), each store stood behind a reload of its
+// pointer from the job table and that load's vmcnt(0), i.e. behind the acknowledgement of the store before it.
 // Hand-off per tile: wave 0 finishes the out tile in LDS -> barrier A -> wave 1 pulls it into registers -> barrier B ->
 // wave 1 issues the global stores while wave 0 already overwrites LDS with the next input tile.
 constexpr int SEQ_LDS_BLOCK = 128;
@@ -480,6 +490,20 @@ typedef double pq_d2v __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void nt_store2(double *p, const double2 &v) {
     pq_d2v w = {v.x, v.y};
     PQ_HOOK_STORE2(w, reinterpret_cast<pq_d2v *>(p));
+}
+// The same through pointers that SAY they point to global memory (a column pointer read from a job table is a generic one): the access
+// is a global_load / global_store with a scalar base and a 32-bit lane offset instead of a flat one with a 64-bit address per lane and
+// access (registers), and it counts in vmcnt alone (a flat access also holds up the LDS-only waits of the hand-off).
+typedef __attribute__((address_space(1))) double pq_gdouble;
+typedef __attribute__((address_space(1))) unsigned char pq_gbyte;
+typedef __attribute__((address_space(1))) pq_d2v pq_gd2v;
+__device__ __forceinline__ void nt_store2(pq_gdouble *p, const double2 &v) {
+    pq_d2v w = {v.x, v.y};
+    PQ_HOOK_STORE2(w, (pq_gd2v *)p);
+}
+__device__ __forceinline__ double2 g_load2(const pq_gdouble *p) {
+    const pq_d2v w = *(const pq_gd2v *)p;
+    return make_double2(w.x, w.y);
 }
 // UNAL: the same tiles for columns whose rows are only 8-byte aligned (an odd row pitch -- a dense odd len --, or columns that start 8
 // bytes off).  The cooperative accesses move 8 bytes per lane: K lanes cover the K rows (K * 8 contiguous bytes, the same piece as in the
@@ -492,6 +516,12 @@ __device__ __forceinline__ void nt_store2(double *p, const double2 &v) {
 // LENS: the batch is a re-housed ragged one (launch_seq, rg_pack): every series is walked over d.len rows of its padded row, but the op
 // is told the series' OWN length (init / init_lds read r.len for their short-series rules); rows beyond it are computed on padding
 // and never leave the padded columns.
+#ifndef PQ_STORER_PAIR
+#define PQ_STORER_PAIR 1 // the storer's pair mode (below)
+#endif
+#ifndef PQ_PAIR_CAP
+#define PQ_PAIR_CAP 136  // registers the storer may spend on held tiles in pair mode
+#endif
 template <class Op, bool UNAL = false, bool LENS = false>
 __device__ __forceinline__ void run_seq_lds(Op &op, const double *const *inp, double *const *outp, const Dims &d,
                                             int64_t tile_s0, unsigned char *lds, int skip = 0) {
@@ -505,6 +535,16 @@ __device__ __forceinline__ void run_seq_lds(Op &op, const double *const *inp, do
     // the store replica (an A/B build, experiments.h PQ_EXP_STOREONLY): the step's grids, addresses, piece sizes and store policy with the
     // compute wave gone -- no loads, no LDS traffic, no barriers; what the write pattern alone costs
     constexpr bool SO = PQ_EXP_STOREONLY_ON && !SeqTile<Op>::DIRECT && !HasFinish<Op>::value && !UNAL;
+    // Assisted stores (the op's ASSIST trait; AS = 0 in a product build): the compute wave drains the last AS out columns of a tile, the storer the first NS.  Only in
+    // the aligned pair-mode body, and not for ops with an epilogue (barrier C and its fence assume that only wave 1 stored) or a time split.
+    // The compute wave has ONE vmcnt for its loads and these stores, so it issues them where its next wait is a whole tile away: its
+    // columns stay in LDS over the hand-off and the fill of the next input tile (the fill writes the first NIN tile slots only, hence
+    // NS >= NIN; its loads are waited for with no store in flight); then the wave issues the following prefetch, then pulls and stores its
+    // columns, then walks the rows -- the wait of the next fill is for loads issued BEFORE the stores, which drain during the walk.
+    constexpr int AS = (K == 8 && PQ_STORER_PAIR && NDer<Op>::value == 0 && !UNAL && !MASKED && !TsOk<Op>::value && !HasFinish<Op>::value &&
+                        !SO && PQ_PF2_MAX == 0) ? PQ_HOOK_ASSIST(Assist<Op>::value) : 0;
+    constexpr int NS = NOUT - AS;
+    static_assert(AS >= 0 && NS >= 1 && (AS == 0 || NS >= NIN), "ASSIST: the storer keeps at least one column, and the assisted tile slots lie behind the input tiles");
     static_assert(NTap<Op>::value == 0 || HasRings<Op>::value, "an op with lag taps needs a ring variant for the LDS body");
     const int lane = threadIdx.x & 63, wave = (int)(threadIdx.x >> 6);
     const int64_t T = d.len, nt = T / K;
@@ -522,15 +562,25 @@ __device__ __forceinline__ void run_seq_lds(Op &op, const double *const *inp, do
     const unsigned stride_b = (unsigned)d.stride * 8u;                   // wave-uniform
     const unsigned lane_part = (unsigned)csym * stride_b + (unsigned)cchunk * (unsigned)EB;
     auto live_i = [&](int i) -> bool { return (unsigned)(csym + i * SPI) <= rel_max; };           // the series of access i exists
+    // (the lane offset is made opaque where it is used: hoisted out of the tile loop as a zero-extended 64-bit value it would no longer
+    //  match the scalar-base form, and every access would get a 64-bit vector address of its own)
+    auto lane_off = [](unsigned o) -> unsigned { asm volatile("" : "+v"(o)); return o; };
     auto toff = [&](int i) -> unsigned {
         const unsigned o = lane_part + (unsigned)(i * SPI) * stride_b;
-        return live_i(i) ? o : rel_max * stride_b + (unsigned)cchunk * (unsigned)EB;
+        return lane_off(live_i(i) ? o : rel_max * stride_b + (unsigned)cchunk * (unsigned)EB);
     };
-    auto at = [&](const double *col, int i, int64_t t0) -> const double * { // col, t0 wave-uniform
-        return reinterpret_cast<const double *>(reinterpret_cast<const unsigned char *>(col + tile_base + t0) + toff(i));
+    // a wave-uniform address, in scalar registers whatever the compiler would have chosen: the base of the global_load / global_store form
+    auto uniform = [](const double *q) -> unsigned long long {
+        const unsigned long long p = reinterpret_cast<unsigned long long>(q);
+        unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)p), hi = __builtin_amdgcn_readfirstlane((unsigned)(p >> 32));
+        asm("" : "+s"(lo), "+s"(hi)); // (opaque: strength reduction otherwise folds base and lane offset into one 64-bit vector address per access)
+        return ((unsigned long long)hi << 32) | lo;
     };
-    auto at_w = [&](double *col, int i, int64_t t0) -> double * {
-        return reinterpret_cast<double *>(reinterpret_cast<unsigned char *>(col + tile_base + t0) + toff(i));
+    auto at = [&](const double *col, int i, int64_t t0) -> const pq_gdouble * { // col, t0 wave-uniform
+        return (const pq_gdouble *)((const pq_gbyte *)uniform(col + tile_base + t0) + toff(i));
+    };
+    auto at_w = [&](double *col, int i, int64_t t0) -> pq_gdouble * {
+        return (pq_gdouble *)((pq_gbyte *)uniform(col + tile_base + t0) + toff(i));
     };
     unsigned char *const co_base = lds + csym * ROWB + cchunk * EB; // this lane's 16-byte slot of a cooperative tile access; access i adds
     auto co_row = [&](int i) -> unsigned char * { return co_base + i * (SPI * ROWB); }; // a compile-time offset (the DS offset field)
@@ -565,20 +615,32 @@ __device__ __forceinline__ void run_seq_lds(Op &op, const double *const *inp, do
         __builtin_amdgcn_s_barrier(); // A: out tile complete, wave 1 may read it
         __builtin_amdgcn_s_barrier(); // B: wave 1 holds the tile in registers, LDS is free again
     };
+    // The column pointers of the cooperative accesses, read ONCE into scalar registers.  inp / outp usually point into the job table in
+    // global memory, and every LDS hand-off is a compiler barrier for memory: read where it is used, a pointer is loaded again in front of
+    // each access, and the wait for that load is a wait for the wave's whole vmcnt -- the storer then waits for the acknowledgement of
+    // store n before it issues store n + 1 (one store in flight per wave), the compute wave for a pointer before every prefetch.
+    // (each wave reads the ones it uses: the storer its NS output columns, the compute wave the inputs and its AS assisted columns)
+    //
+    // Assisted stores: the compute wave's columns of the tile at row t0, out of LDS through the storer's per-tile mapping (64-byte
+    // pieces) and straight to memory -- 4 registers per access in flight, nothing held across the hand-off
+    double *cas[AS > 0 ? AS : 1];
+    auto assist_flush = [&](int64_t t0) {
+#pragma unroll
+        for (int k = 0; k < AS; k++)
+#pragma unroll
+            for (int i = 0; i < NI; i++) g_store(cas[k], i, t0, l_get(i, (NS + k) * TB));
+    };
     // (`wave == 1` for the two-wave form, literally: with `wave >= 1` the compute branch learns that its wave index is 0 and the register
     //  allocation of the light job kernel shifts by two spilled registers under its 192 cap)
     if (wave == 1) { // -------------------------------------------------------------------------- storer
         if constexpr (!MASKED) {
+            double *cout[NS];
+#pragma unroll
+            for (int k = 0; k < NS; k++) cout[k] = reinterpret_cast<double *>(uniform(outp[k]));
             // Tunable: the storer can keep ACC consecutive out tiles in registers and issue their stores back to back (ACC * K * 8
             // contiguous bytes per series within a few cycles).  In a pure tile copy 64-byte pieces scattered over 64 series run
             // the write path at ~3.1 TB/s against ~3.7 (pairs) / ~4.3 TB/s (128-byte pieces and up), scripts/ubench/tilecopy3.hip.
             // (PQ_STORER_ACC, experiments.h: 1; 2 / 4 measured -1 % .. +4 % per suite step: the microbenchmark's gain does not carry over)
-#ifndef PQ_STORER_PAIR
-#define PQ_STORER_PAIR 1
-#endif
-#ifndef PQ_PAIR_CAP
-#define PQ_PAIR_CAP 136
-#endif
             if constexpr (K == 8 && PQ_STORER_PAIR && NDer<Op>::value == 0 && !UNAL) {
                 // Pair mode: the storer re-maps its lanes to (series of a group of 8, one of the 8 chunks of TWO consecutive tiles):
                 // lanes with chunk < 4 pull their 16 bytes out of the even tile, the others out of the odd tile into the same
@@ -588,8 +650,9 @@ __device__ __forceinline__ void run_seq_lds(Op &op, const double *const *inp, do
                 // aligns the 16-row tiles of the 1-in/1-out ops).  No extra LDS, the register count of two held tiles; columns
                 // beyond the register cap go out per tile as before.
                 constexpr int CAP = IsHeavy<Op>::value ? 208 : PQ_PAIR_CAP;
-                constexpr int W0 = (CAP - NOUT * NI * 4) / (NI * 4);
-                constexpr int W = (SO && PQ_EXP_SO_ALLPAIR_ON) ? NOUT : (W0 < 0 ? 0 : (W0 > NOUT ? NOUT : W0)), R = NOUT - W; // (replica variant: every column in 128-byte pieces)
+                // (with assisted stores the wave owns the first NS columns only: fewer per-tile columns, more room for pairs)
+                constexpr int W0 = (CAP - NS * NI * 4) / (NI * 4);
+                constexpr int W = (SO && PQ_EXP_SO_ALLPAIR_ON) ? NOUT : (W0 < 0 ? 0 : (W0 > NS ? NS : W0)), R = NS - W; // (replica variant: every column in 128-byte pieces)
                 const int half = (lane >> 2) & 1, sub = lane >> 3;
                 const unsigned char *pr_row = lds + sub * ROWB + (lane & 3) * 16;
                 static_assert(!TsOk<Op>::value, "a time-split op stores per tile: its check tile and its first own tile go to different columns");
@@ -629,7 +692,7 @@ __device__ __forceinline__ void run_seq_lds(Op &op, const double *const *inp, do
                                 const int kk = W + k;
 #pragma unroll
                                 for (int i = 0; i < NI; i++)
-                                    if (live_i(i)) nt_store2(at_w(outp[kk], i, t0), v[k][i]);
+                                    if (live_i(i)) nt_store2(at_w(cout[kk], i, t0), v[k][i]);
                             }
                         }
                     }
@@ -640,9 +703,9 @@ __device__ __forceinline__ void run_seq_lds(Op &op, const double *const *inp, do
                         const int kk = k;
 #pragma unroll
                         for (int i = 0; i < 8; i++) {
-                            unsigned char *const pb = reinterpret_cast<unsigned char *>(outp[kk] + tile_base + it * K); // wave-uniform
+                            pq_gbyte *const pb = (pq_gbyte *)uniform(cout[kk] + tile_base + it * K); // wave-uniform
                             if (mine && (unsigned)(i * 8 + sub) <= rel_max)
-                                nt_store2(reinterpret_cast<double *>(pb + (pair_part + (unsigned)(i * 8) * stride_b)), w[k][i]);
+                                nt_store2((pq_gdouble *)(pb + lane_off(pair_part + (unsigned)(i * 8) * stride_b)), w[k][i]);
                         }
                     }
                 }
@@ -671,7 +734,7 @@ __device__ __forceinline__ void run_seq_lds(Op &op, const double *const *inp, do
                 if constexpr (TsOk<Op>::value) check_tile = it < skip;
 #pragma unroll
                 for (int k = 0; k < NOUT; k++) {
-                    double *oc = outp[k];
+                    double *oc = cout[k];
                     if constexpr (TsOk<Op>::value) oc = check_tile ? op.chk[k] : oc;
 #pragma unroll
                     for (int i = 0; i < NI; i++)
@@ -718,6 +781,11 @@ __device__ __forceinline__ void run_seq_lds(Op &op, const double *const *inp, do
     } else {
         op.init(r);
     }
+    const double *cin[NIN];
+#pragma unroll
+    for (int k = 0; k < NIN; k++) cin[k] = reinterpret_cast<const double *>(uniform(inp[k]));
+#pragma unroll
+    for (int k = 0; k < AS; k++) cas[k] = reinterpret_cast<double *>(uniform(outp[NS + k]));
     unsigned char *my_row = lds + lane * ROWB;
     // wave 0 has no stores in flight (except for MASKED ops), so its prefetched loads can be waited for exactly
     constexpr int PF = (NIN * NI * 4 <= PQ_PF2_MAX) ? 2 : 1; // a second tile of prefetch costs NIN*NI*4 VGPRs
@@ -726,7 +794,7 @@ __device__ __forceinline__ void run_seq_lds(Op &op, const double *const *inp, do
 #pragma unroll
         for (int k = 0; k < NIN; k++)
 #pragma unroll
-            for (int i = 0; i < NI; i++) buf[k][i] = g_load(inp[k], i, t0);
+            for (int i = 0; i < NI; i++) buf[k][i] = g_load(cin[k], i, t0);
     };
     auto do_tile = [&](double2 (&buf)[NIN][NI], int64_t it) {
         const int64_t t0 = it * K;
@@ -742,6 +810,9 @@ __device__ __forceinline__ void run_seq_lds(Op &op, const double *const *inp, do
                                   (unsigned)__double2loint(buf[k][i].y) == (unsigned)(PQ_NULL_BITS & 0xffffffffu);
             }
         if (it + PF < nt) prefetch(buf, t0 + PF * K);
+        if constexpr (AS > 0) { // behind the loads: the stores drain during the walk
+            if (it > 0) assist_flush(t0 - K);
+        }
         lds_fence();
         PQ_PROF_T(c1);
         if constexpr (HasFast<Op>::value) {
@@ -815,6 +886,9 @@ __device__ __forceinline__ void run_seq_lds(Op &op, const double *const *inp, do
 #pragma unroll
         for (int f = 0; f < PF; f++)
             if (it + f < nt) do_tile(pre[f], it + f);
+    }
+    if constexpr (AS > 0) {
+        if (nt > 0) assist_flush((nt - 1) * K); // the last tile's columns
     }
     // ragged tail: fewer than K rows left.  The series index and its row offset are formed again here (from the lane id as the
     // hardware counts it, which the compiler cannot tie to the value used above) rather than kept -- or spilled -- across the row loop.

@@ -1179,3 +1179,17 @@ pq_status pq_suite_info(const pq_suite *s, int32_t *n_phases, int32_t *n_seq_job
 }
 
 } // extern "C"
+
+// (tests) The static shape of every recordable op, one row per call: {job kind, rows per tile, bytes of its tiles in LDS (seq_lds_bytes
+// adds the op's rings), HEAVY, row-masked}.  Returns 0 past the end of the list.  What decides a job's LDS class and kernel must not
+// move when the tiled body changes how tiles are loaded and stored: tests/test_seq_op_table.py holds the values.
+extern "C" int32_t pq_seq_op_info(int32_t idx, int32_t *row5) {
+    static const int32_t tab[][5] = {
+#define X(OP) {(int32_t)OP::SEQ_ID, SeqTile<OP>::K, SeqTile<OP>::BYTES, IsHeavy<OP>::value, IsMasked<OP>::value},
+        SEQ_OPS_LIGHT(X) SEQ_OPS_HEAVY(X)
+#undef X
+    };
+    if (!row5 || idx < 0 || idx >= (int32_t)(sizeof tab / sizeof tab[0])) return 0;
+    for (int k = 0; k < 5; k++) row5[k] = tab[idx][k];
+    return 1;
+}
