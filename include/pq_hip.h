@@ -500,6 +500,34 @@ pq_status pq_backtest_sweep(pq_ctx *, const pq_batch *, const double *price, con
                             const double *benchmark, int64_t bench_series_stride /* 0: one [len] series shared by all */,
                             const pq_bt_params *bt, double *summary /* [n_series][n_params][8] */);
 int32_t pq_sweep_row_tile(int32_t n_lines);
+/* pq_backtest_sweep_rules: the same launch with a third column index c and every line-based rule of `Strategy`.  pq_sweep_rule has the
+ * layout of pq_sweep_param with _pad read as c; col[c] is lines[c], or the price where c = -1.  Row i against row i - 1, row 0 never signals:
+ *   0 PQ_SWEEP_RULE_CROSS, 1 PQ_SWEEP_RULE_BAND   as above                                  (Strategy.ma / macd; rsi / cci / reversion)
+ *   2 PQ_SWEEP_RULE_CHANNEL         p = col[c], lo = lines[a], hi = lines[b]: buy = p[i] < lo[i] && p[i-1] >= lo[i-1], sell = p[i] > hi[i] &&
+ *                                   p[i-1] <= hi[i-1]; both false unless all six values are non-NULL   (pq_channel_signals mode 0; bband)
+ *   3 PQ_SWEEP_RULE_BREAKOUT        buy = p[i] > hi[i-1], sell = p[i] < lo[i-1]; both false if p[i], lo[i-1] or hi[i-1] is NULL
+ *                                                                                            (pq_channel_signals mode 1; breakout)
+ *   4 PQ_SWEEP_RULE_SCALED_CHANNEL  rule 2 with lo = lines[a] * k0, hi = lines[a] * k1 (one rounded multiply each, NULL where lines[a]
+ *                                   is; b unused)                                            (pq_scale_band + pq_channel_signals mode 0; grid)
+ *   5 PQ_SWEEP_RULE_CROSS_ZONES     cross(lines[a], lines[b]); buys need col[c][i] < k0, sells col[c][i] > k1   (pq_gate_signals mode 0; stoch)
+ *   6 PQ_SWEEP_RULE_CROSS_STRENGTH  cross(lines[a], lines[b]); both need col[c][i] > k0                        (pq_gate_signals mode 1; adx)
+ * Every rule takes the same buy / sell decision on every row as the rule kernels it names, NULL and non-NULL NaN values included (rules
+ * 2-4 test the other side's columns for the NULL itself, like pq_channel_signals: a non-NULL NaN there does not refuse the signal).
+ * Limits, refusals and empty shapes are pq_backtest_sweep's.  The table is checked on the host before anything is launched: rule in
+ * [0, 6], a in [0, n_lines), b in [0, n_lines) under rules 0, 2, 3, 5, 6, c in [-1, n_lines) under rules 2-6; a field that a rule does not
+ * use is ignored.  A table with one rule throughout runs a kernel instantiated for that rule, a mixed one the generic kernel. */
+#define PQ_SWEEP_RULE_CROSS 0
+#define PQ_SWEEP_RULE_BAND 1
+#define PQ_SWEEP_RULE_CHANNEL 2
+#define PQ_SWEEP_RULE_BREAKOUT 3
+#define PQ_SWEEP_RULE_SCALED_CHANNEL 4
+#define PQ_SWEEP_RULE_CROSS_ZONES 5
+#define PQ_SWEEP_RULE_CROSS_STRENGTH 6
+typedef struct { int32_t rule, a, b, c; double k0, k1; } pq_sweep_rule;
+pq_status pq_backtest_sweep_rules(pq_ctx *, const pq_batch *, const double *price, const double *const *lines, int32_t n_lines,
+                                  const pq_sweep_rule *rules /* device */, int64_t n_rules,
+                                  const double *benchmark, int64_t bench_series_stride /* 0: one [len] series shared by all */,
+                                  const pq_bt_params *bt, double *summary /* [n_series][n_rules][8] */);
 
 /* ---- cross-sectional factor evaluation, Factor.ic / rank_ic / rolling_ic (README.md:1429-1430,
  * :1480-1482, :1626-1634; README-only, decision D-12 in oracle/backtest.c).  factor / fwd_return: [n_series][stride];

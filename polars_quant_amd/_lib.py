@@ -159,6 +159,8 @@ def lib() -> C.CDLL:
                                              C.c_int64, vp, vp, vp, vp, vp]
         L.pq_backtest_sweep.restype = C.c_int32
         L.pq_backtest_sweep.argtypes = [vp, C.POINTER(Batch), vp, C.POINTER(vp), C.c_int32, vp, C.c_int64, vp, C.c_int64, C.POINTER(BtParams), vp]
+        L.pq_backtest_sweep_rules.restype = C.c_int32
+        L.pq_backtest_sweep_rules.argtypes = L.pq_backtest_sweep.argtypes
         L.pq_sweep_row_tile.restype = C.c_int32
         L.pq_sweep_row_tile.argtypes = [C.c_int32]
         L.pq_recommended_stride.restype = C.c_int64

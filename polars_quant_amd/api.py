@@ -1369,16 +1369,12 @@ def sweep_params(rules) -> np.ndarray:
     return out
 
 
-def backtest_sweep(price, lines, params, benchmark=None, out=None, offsets=None, **kw):
-    """D-25: every parameter set of `params` (sweep_params) over every symbol in ONE launch -> device summary [P, N, 8], a permuted
-    view of the kernel's [N, P, 8].  price [N, T]; lines: a list of [N, T] candidate indicator columns or one [L, N, T] array;
-    benchmark: None, one [T] series shared by all symbols, or [N, T]; out: a contiguous device [N, P, 8] float64 tensor to write into;
-    offsets: ragged groups of long columns (see call()) are not supported by the sweep and raise."""
+def _backtest_sweep(who, entry, tab, price, lines, benchmark, out, offsets, kw):
+    """pq_backtest_sweep and pq_backtest_sweep_rules take the same arguments: `entry` is the one to call, `tab` its 32-byte table"""
     prm = BtParams(**{**BT_DEFAULTS, **kw})
-    tab = sweep_params(params)
     cols = list(lines) if isinstance(lines, (list, tuple)) else [lines[j] for j in range(_shape(lines)[0])]
     if not 1 <= len(cols) <= SWEEP_MAX_LINES:
-        raise PqError(f"backtest_sweep: the number of lines must be in 1..{SWEEP_MAX_LINES}, not {len(cols)}")
+        raise PqError(f"{who}: the number of lines must be in 1..{SWEEP_MAX_LINES}, not {len(cols)}")
     mats = _same_layout([_to_device(price)[0]] + [_to_device(c)[0] for c in cols])
     p = mats[0]
     dev = p.device
@@ -1396,18 +1392,57 @@ def backtest_sweep(price, lines, params, benchmark=None, out=None, offsets=None,
         elif bm.shape == (n, T):
             bstride = bm.stride(0)
         else:
-            raise PqError(f"backtest_sweep: `benchmark` has shape {tuple(bm.shape)}, expected {(T,)} or {(n, T)}")
+            raise PqError(f"{who}: `benchmark` has shape {tuple(bm.shape)}, expected {(T,)} or {(n, T)}")
     if out is None:
         out = torch.empty((n, P, 8), dtype=torch.float64, device=dev)
     elif tuple(out.shape) != (n, P, 8) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != dev:
         raise ValueError(f"out must be a contiguous float64 tensor of shape {(n, P, 8)} on {dev}")
     if n and P:
-        dtab = torch.from_numpy(tab.view(np.uint8).reshape(P, SWEEP_PARAM_DTYPE.itemsize)).to(dev)
+        dtab = torch.from_numpy(tab.view(np.uint8).reshape(P, tab.dtype.itemsize)).to(dev)
         vp = C.c_void_p
         ptrs = (vp * len(cols))(*[m.data_ptr() for m in mats[1:]])
         with torch.cuda.device(dev):
-            check(lib().pq_backtest_sweep(ctx(dev.index), C.byref(b), vp(p.data_ptr()), ptrs, C.c_int32(len(cols)), vp(dtab.data_ptr()),
-                                          C.c_int64(P), vp(bm.data_ptr()) if bm is not None else None, C.c_int64(bstride),
-                                          C.byref(prm), vp(out.data_ptr())))
+            check(getattr(lib(), entry)(ctx(dev.index), C.byref(b), vp(p.data_ptr()), ptrs, C.c_int32(len(cols)), vp(dtab.data_ptr()),
+                                        C.c_int64(P), vp(bm.data_ptr()) if bm is not None else None, C.c_int64(bstride),
+                                        C.byref(prm), vp(out.data_ptr())))
     del keep
     return out.permute(1, 0, 2)
+
+
+def backtest_sweep(price, lines, params, benchmark=None, out=None, offsets=None, **kw):
+    """D-25: every parameter set of `params` (sweep_params) over every symbol in ONE launch -> device summary [P, N, 8], a permuted
+    view of the kernel's [N, P, 8].  price [N, T]; lines: a list of [N, T] candidate indicator columns or one [L, N, T] array;
+    benchmark: None, one [T] series shared by all symbols, or [N, T]; out: a contiguous device [N, P, 8] float64 tensor to write into;
+    offsets: ragged groups of long columns (see call()) are not supported by the sweep and raise."""
+    return _backtest_sweep("backtest_sweep", "pq_backtest_sweep", sweep_params(params), price, lines, benchmark, out, offsets, kw)
+
+
+# pq_sweep_rule (include/pq_hip.h): pq_sweep_param with a third column index c (-1: the price) -- the rules of backtest_sweep_rules:
+# 0 cross, 1 band, 2 channel (reversion), 3 breakout, 4 channel around lines[a] * k0 / k1, 5 cross in zones, 6 cross with strength
+SWEEP_RULE_DTYPE = np.dtype([("rule", "<i4"), ("a", "<i4"), ("b", "<i4"), ("c", "<i4"), ("k0", "<f8"), ("k1", "<f8")])
+(SWEEP_RULE_CROSS, SWEEP_RULE_BAND, SWEEP_RULE_CHANNEL, SWEEP_RULE_BREAKOUT, SWEEP_RULE_SCALED_CHANNEL, SWEEP_RULE_CROSS_ZONES,
+ SWEEP_RULE_CROSS_STRENGTH) = range(7)
+
+
+def sweep_rules(rules) -> np.ndarray:
+    """a SWEEP_RULE_DTYPE array from one, or from a dict of equally long rule / a / b / c / k0 / k1 columns (missing ones are 0)"""
+    if isinstance(rules, np.ndarray) and rules.dtype == SWEEP_RULE_DTYPE:
+        return np.ascontiguousarray(rules.reshape(-1))
+    if not isinstance(rules, dict) or "rule" not in rules or "a" not in rules:
+        raise ValueError("rules must be a SWEEP_RULE_DTYPE array or a dict with at least the columns 'rule' and 'a'")
+    unknown = set(rules) - set(SWEEP_RULE_DTYPE.names)
+    if unknown:
+        raise ValueError(f"unknown rule columns {sorted(unknown)}")
+    out = np.zeros(len(np.atleast_1d(rules["rule"])), dtype=SWEEP_RULE_DTYPE)
+    for k, v in rules.items():
+        v = np.atleast_1d(np.asarray(v))
+        if v.shape != out.shape:
+            raise ValueError(f"rule column {k!r} has shape {v.shape}, expected {out.shape}")
+        out[k] = v
+    return out
+
+
+def backtest_sweep_rules(price, lines, rules, benchmark=None, out=None, **kw):
+    """backtest_sweep with the seven rules of pq_backtest_sweep_rules: `rules` is a sweep_rules table whose column c names a third
+    column (a line, or -1 for `price`) -> device summary [P, N, 8].  The other arguments are backtest_sweep's."""
+    return _backtest_sweep("backtest_sweep_rules", "pq_backtest_sweep_rules", sweep_rules(rules), price, lines, benchmark, out, None, kw)

@@ -1,10 +1,18 @@
 // sweep.hip -- ParameterSweep (decision D-25 in DESIGN.md): one launch backtests a grid of strategy parameter sets over every symbol.
 // The parameter set is the parallel axis: one lane is one parameter set, one wavefront is one symbol x 64 consecutive parameter sets,
-// the (up to four) wavefronts of a workgroup share the symbol.  A parameter set names a rule over candidate indicator columns ("lines"):
+// the (up to four) wavefronts of a workgroup share the symbol.  A parameter set names a rule over candidate indicator columns ("lines");
+// col[c] is lines[c], or the price where c = -1:
 //   rule 0  cross(lines[a], lines[b])   (oracle/backtest.c:263-270)      rule 1  band(lines[a], k0, k1)   (oracle/backtest.c:271-278)
+//   rule 2  channel, reversion: col[c] against lo = lines[a], hi = lines[b]   (pq_channel_signals mode 0, oracle/backtest.c:279-294)
+//   rule 3  channel, breakout: col[c] against row t - 1 of lo and hi          (pq_channel_signals mode 1)
+//   rule 4  rule 2 with lo = lines[a] k0, hi = lines[a] k1                    (pq_scale_band + pq_channel_signals mode 0)
+//   rule 5  cross(lines[a], lines[b]), buys while col[c] < k0, sells while col[c] > k1   (pq_cross_signals + pq_gate_signals mode 0)
+//   rule 6  cross(lines[a], lines[b]), both while col[c] > k0                            (pq_cross_signals + pq_gate_signals mode 1)
 // and the lane runs the reference's scan (vectorized.rs:124-194) and summary (metrics.rs:7-152) on the signals without ever writing a
-// signal, position, cash or equity value to memory.  The price and the benchmark return of a row are the same for the whole workgroup;
-// only the two line values differ per lane, and they come from LDS: the symbol's rows of every line (plus the price row and the
+// signal, position, cash or equity value to memory.  A table with one rule throughout runs the kernel instantiated for that rule, which
+// keeps only the LDS reads and row t - 1 registers of that rule; a mixed table runs the generic instantiation (RULE = -1), whose lanes
+// dispatch on their own rule.  The price and the benchmark return of a row are the same for the whole workgroup;
+// only the (up to three) column values differ per lane, and they come from LDS: the symbol's rows of every line (plus the price row and the
 // benchmark-return row) are staged in tiles of R rows, R sized from the number of lines, double buffered -- the loads of the next tile
 // are issued into registers before the current tile is walked and stored to the other buffer after it, so they are in flight during
 // the walk.  The LDS pitch of a line is R itself, which is odd: lanes of one 32-lane group that read different lines at the same row
@@ -42,7 +50,7 @@ int sw_waves(int n_lines, int R, int64_t n_params) {
 struct SwArgs {
     const double *price;          // [n_series][stride]
     const double *const *lines;   // device table of n_lines columns, each [n_series][stride]
-    const pq_sweep_param *params; // device, [n_params]
+    const pq_sweep_rule *params;  // device, [n_params]
     const double *bench;          // nullable; series s at bench + s * bench_stride
     double *summary;              // [n_series][n_params][8]
     pq_bt_params prm;
@@ -51,11 +59,22 @@ struct SwArgs {
     uint32_t magic; // (e * magic) >> 20 == e / R for e < SW_TILE
 };
 
+static_assert(sizeof(pq_sweep_rule) == 32 && sizeof(pq_sweep_param) == 32, "one table layout for both entry points");
+constexpr int SW_GENERIC = -1; // the instantiation whose lanes dispatch on their own rule
+// what a rule reads besides lines[a] (SW_GENERIC: both): RULE is a template argument, so an instantiation carries only its own reads
+// and registers
+constexpr bool sw_uses_b(int rule) { return rule != PQ_SWEEP_RULE_BAND && rule != PQ_SWEEP_RULE_SCALED_CHANNEL; }
+constexpr bool sw_uses_c(int rule) { return rule != PQ_SWEEP_RULE_CROSS && rule != PQ_SWEEP_RULE_BAND; }
+
+struct SwRule { // a lane's parameter set: the LDS offsets of its columns (an unused one repeats ia)
+    int ia, ib, ic, rule;
+    double k0, k1;
+};
 struct SwLane { // the scan's state (vectorized.rs:124-194) and the rule's row t - 1
-    double pa, pb, pos, avail, entry_cost, prev_eq;
+    double pa, pb, pc, pos, avail, entry_cost, prev_eq;
     int32_t trades, wins;
     __device__ void reset(double capital) {
-        pa = pb = __longlong_as_double(0x7FF8000000000000LL); // row 0 never signals: a NaN compares false
+        pa = pb = pc = __longlong_as_double(0x7FF8000000000000LL); // row 0 never signals: a NaN (not the NULL) compares false
         pos = 0.0; avail = capital; entry_cost = 0.0; prev_eq = capital; trades = 0; wins = 0;
     }
 };
@@ -111,16 +130,54 @@ __device__ __forceinline__ void sw_store(const SwArgs &g, int64_t t0, const doub
     }
 }
 
-// n rows of one tile for one lane.  The rule is two comparisons on the lane's two line values (a NULL is a NaN: it compares false);
-// a buy or a sell is rare, so the event arithmetic stays behind the branch.
-template <int PASS, bool BENCH>
-__device__ __forceinline__ void sw_walk(const double *tile, int n, int ia, int ib, int ipx, int ibr, bool band, double k0, double k1,
-                                        const pq_bt_params &prm, SwLane &st, SwAcc &acc) {
+// the lane's rule on row t (xa, xb, xc) and row t - 1 (st.pa, st.pb, st.pc).  Cross, band and the gates are comparisons a NaN fails, and
+// a NULL is a NaN.  A channel side is refused when the OTHER side's column is NULL but not when it is a non-NULL NaN (ChannelSigOp,
+// ops_backtest.h), so rules 2-4 test for the NULL itself.
+template <int RULE>
+__device__ __forceinline__ void sw_signal(const SwRule &q, double xa, double xb, double xc, SwLane &st, bool &buy, bool &sell) {
+    const int rule = RULE == SW_GENERIC ? q.rule : RULE;
+    double na = xa, nb = xb; // what row t leaves behind as row t - 1
+    switch (rule) {
+    case PQ_SWEEP_RULE_BAND:
+        buy = st.pa < q.k0 && xa >= q.k0;
+        sell = st.pa > q.k1 && xa <= q.k1;
+        break;
+    case PQ_SWEEP_RULE_SCALED_CHANNEL: { // ScaleBandOp (strategy.hip): one rounded multiply each, NULL where the base is
+        const bool null = pq_isnull(xa);
+        na = null ? xa : xa * q.k0;
+        nb = null ? xa : xa * q.k1;
+    }
+        [[fallthrough]]; // then the channel on lo = na, hi = nb
+    case PQ_SWEEP_RULE_CHANNEL: {
+        const bool ok = !pq_isnull(xc) && !pq_isnull(st.pc) && !pq_isnull(na) && !pq_isnull(nb) && !pq_isnull(st.pa) && !pq_isnull(st.pb);
+        buy = ok && xc < na && st.pc >= st.pa;
+        sell = ok && xc > nb && st.pc <= st.pb;
+    } break;
+    case PQ_SWEEP_RULE_BREAKOUT: {
+        const bool ok = !pq_isnull(xc) && !pq_isnull(st.pa) && !pq_isnull(st.pb);
+        buy = ok && xc > st.pb;
+        sell = ok && xc < st.pa;
+    } break;
+    default: { // cross, alone or behind a gate on col[c] of row t
+        buy = st.pa <= st.pb && xa > xb;
+        sell = st.pa >= st.pb && xa < xb;
+        if (rule == PQ_SWEEP_RULE_CROSS_ZONES) { buy = buy && xc < q.k0; sell = sell && xc > q.k1; }
+        if (rule == PQ_SWEEP_RULE_CROSS_STRENGTH) { const bool gate = xc > q.k0; buy = buy && gate; sell = sell && gate; }
+    } break;
+    }
+    st.pa = na; st.pb = nb; st.pc = xc;
+}
+
+// n rows of one tile for one lane.  A buy or a sell is rare, so the event arithmetic stays behind the branch.
+template <int RULE, int PASS, bool BENCH>
+__device__ __forceinline__ void sw_walk(const double *tile, int n, const SwRule &q, int ipx, int ibr, const pq_bt_params &prm, SwLane &st,
+                                        SwAcc &acc) {
     for (int c = 0; c < n; c++) {
-        const double xa = tile[ia + c], xb = tile[ib + c], px = tile[ipx + c];
-        const bool buy = band ? (st.pa < k0 && xa >= k0) : (st.pa <= st.pb && xa > xb);
-        const bool sell = band ? (st.pa > k1 && xa <= k1) : (st.pa >= st.pb && xa < xb);
-        st.pa = xa; st.pb = xb;
+        const double xa = tile[q.ia + c], px = tile[ipx + c];
+        const double xb = sw_uses_b(RULE) ? tile[q.ib + c] : xa;
+        const double xc = sw_uses_c(RULE) ? tile[q.ic + c] : xa;
+        bool buy, sell;
+        sw_signal<RULE>(q, xa, xb, xc, st, buy, sell);
         const bool do_buy = buy && st.pos == 0.0, do_sell = sell && st.pos > 0.0;
         if (px > 0.0 && (do_buy || do_sell)) { // a NaN (or NULL) or non-positive price leaves the state untouched (:141-144)
             if (do_buy) {                      // :146-161
@@ -168,9 +225,9 @@ __device__ __forceinline__ void sw_walk(const double *tile, int n, int ia, int i
 }
 
 // one walk over all rows; `again`: the other walk follows, so the tile after the last one is tile 0
-template <int PASS, bool BENCH>
-__device__ __forceinline__ void sw_pass(const SwArgs &g, int64_t s, double *lds, int &cur, bool wave_live, bool again, int ia, int ib,
-                                        bool band, double k0, double k1, SwLane &st, SwAcc &acc) {
+template <int RULE, int PASS, bool BENCH>
+__device__ __forceinline__ void sw_pass(const SwArgs &g, int64_t s, double *lds, int &cur, bool wave_live, bool again, const SwRule &q,
+                                        SwLane &st, SwAcc &acc) {
     const int R = g.R, tile_elems = (g.n_lines + (BENCH ? 2 : 1)) * R;
     const int ipx = g.n_lines * R, ibr = (g.n_lines + 1) * R;
     for (int64_t t0 = 0; t0 < g.len; t0 += R) {
@@ -179,14 +236,15 @@ __device__ __forceinline__ void sw_pass(const SwArgs &g, int64_t s, double *lds,
         double pre[SW_PRE], bprev = 0.0;
         if (more) sw_fetch<BENCH>(g, s, tn, pre, bprev); // in flight during the walk
         const int n = (int)(last ? g.len - t0 : R);
-        if (wave_live) sw_walk<PASS, BENCH>(lds + cur * tile_elems, n, ia, ib, ipx, ibr, band, k0, k1, g.prm, st, acc);
+        if (wave_live) sw_walk<RULE, PASS, BENCH>(lds + cur * tile_elems, n, q, ipx, ibr, g.prm, st, acc);
         if (more) sw_store<BENCH>(g, tn, pre, bprev, lds + (cur ^ 1) * tile_elems);
         __syncthreads(); // the next tile is complete, and nobody reads this one any more
         cur ^= 1;
     }
 }
 
-template <bool BENCH>
+// RULE: the one rule of the whole table, or SW_GENERIC
+template <int RULE, bool BENCH>
 __global__ __launch_bounds__(SW_BLOCK) void sweep_kernel(SwArgs g) {
     extern __shared__ double sw_lds[];
     const int tid = (int)threadIdx.x;
@@ -195,15 +253,14 @@ __global__ __launch_bounds__(SW_BLOCK) void sweep_kernel(SwArgs g) {
     const int64_t p = p0 + tid;
     const bool live = p < g.n_params;
     const bool wave_live = p0 + (tid & ~63) < g.n_params; // a wavefront without a parameter set only helps with the staging
-    int ia = 0, ib = 0;
-    bool band = false;
-    double k0 = 0.0, k1 = 0.0;
-    if (live) { // a and b were checked against n_lines on the host before the launch
-        const pq_sweep_param q = g.params[p];
-        band = q.rule == 1;
-        ia = q.a * g.R;
-        ib = band ? ia : q.b * g.R;
-        k0 = q.k0; k1 = q.k1;
+    SwRule q{0, 0, 0, RULE == SW_GENERIC ? PQ_SWEEP_RULE_CROSS : RULE, 0.0, 0.0};
+    if (live) { // the rule and the columns it uses were checked against n_lines on the host before the launch
+        const pq_sweep_rule in = g.params[p];
+        if (RULE == SW_GENERIC) q.rule = in.rule;
+        q.ia = in.a * g.R;
+        q.ib = (RULE == SW_GENERIC ? sw_uses_b(in.rule) : sw_uses_b(RULE)) ? in.b * g.R : q.ia;
+        q.ic = (RULE == SW_GENERIC ? sw_uses_c(in.rule) : sw_uses_c(RULE)) ? (in.c < 0 ? g.n_lines : in.c) * g.R : q.ia; // -1: the price row
+        q.k0 = in.k0; q.k1 = in.k1;
     }
     const double capital = g.prm.initial_capital;
     SwLane st;
@@ -217,14 +274,14 @@ __global__ __launch_bounds__(SW_BLOCK) void sweep_kernel(SwArgs g) {
         sw_store<BENCH>(g, 0, pre, bprev, sw_lds);
         __syncthreads();
     }
-    sw_pass<1, BENCH>(g, s, sw_lds, cur, wave_live, true, ia, ib, band, k0, k1, st, acc);
+    sw_pass<RULE, 1, BENCH>(g, s, sw_lds, cur, wave_live, true, q, st, acc);
     const double T = (double)g.len;
     const double last_eq = st.prev_eq;
     const int32_t trades = st.trades, wins = st.wins;
     acc.mean = acc.ret_sum / T;  // metrics.rs:60
     acc.bmean = acc.bsum / T;
     st.reset(capital);
-    sw_pass<2, BENCH>(g, s, sw_lds, cur, wave_live, false, ia, ib, band, k0, k1, st, acc);
+    sw_pass<RULE, 2, BENCH>(g, s, sw_lds, cur, wave_live, false, q, st, acc);
     if (!live) return;
     const double DAYS = 252.0, RF = 0.03;
     const double total_return = (last_eq - capital) / capital;                                                  // :52
@@ -247,6 +304,77 @@ __global__ __launch_bounds__(SW_BLOCK) void sweep_kernel(SwArgs g) {
     sm[0] = ann; sm[1] = acc.max_dd; sm[2] = alpha; sm[3] = beta; sm[4] = sharpe;
     sm[5] = fmax(total_return, 0.0); sm[6] = win_rate; sm[7] = (double)trades;                                  // :142-149
 }
+using SwKernel = void (*)(SwArgs);
+template <bool BENCH>
+SwKernel sw_kernel_for(int rule) {
+    switch (rule) {
+    case PQ_SWEEP_RULE_CROSS: return sweep_kernel<PQ_SWEEP_RULE_CROSS, BENCH>;
+    case PQ_SWEEP_RULE_BAND: return sweep_kernel<PQ_SWEEP_RULE_BAND, BENCH>;
+    case PQ_SWEEP_RULE_CHANNEL: return sweep_kernel<PQ_SWEEP_RULE_CHANNEL, BENCH>;
+    case PQ_SWEEP_RULE_BREAKOUT: return sweep_kernel<PQ_SWEEP_RULE_BREAKOUT, BENCH>;
+    case PQ_SWEEP_RULE_SCALED_CHANNEL: return sweep_kernel<PQ_SWEEP_RULE_SCALED_CHANNEL, BENCH>;
+    case PQ_SWEEP_RULE_CROSS_ZONES: return sweep_kernel<PQ_SWEEP_RULE_CROSS_ZONES, BENCH>;
+    case PQ_SWEEP_RULE_CROSS_STRENGTH: return sweep_kernel<PQ_SWEEP_RULE_CROSS_STRENGTH, BENCH>;
+    default: return sweep_kernel<SW_GENERIC, BENCH>;
+    }
+}
+
+// both entry points: `who` names the caller in the messages, max_rule is the last rule it accepts
+pq_status sw_run(const char *who, int max_rule, pq_ctx *ctx, const pq_batch *b, const double *price, const double *const *lines,
+                 int32_t n_lines, const pq_sweep_rule *rules, int64_t n_rules, const double *benchmark, int64_t bench_series_stride,
+                 const pq_bt_params *bt, double *summary) {
+    PQ_TRY(pq_check(ctx, b));
+    if (ctx->rec) { pq_set_error("%s cannot be recorded into a suite", who); return PQ_ERR_UNSUPPORTED; }
+    if (b->offsets) { pq_set_error("%s: ragged batches are not supported", who); return PQ_ERR_UNSUPPORTED; }
+    if (n_rules < 0) { pq_set_error("%s: negative n_params", who); return PQ_ERR_ARG; }
+    const int R = sw_row_tile(n_lines);
+    if (R == 0) { pq_set_error("%s: n_lines must be in [1, %d], not %d", who, PQ_SWEEP_MAX_LINES, (int)n_lines); return PQ_ERR_ARG; }
+    if (!bt) { pq_set_error("%s: null parameters", who); return PQ_ERR_ARG; }
+    if (n_rules == 0 || b->n_series == 0) return PQ_OK;
+    if (!(rules && summary && (b->len == 0 || (price && lines)))) { pq_set_error("%s: null pointer", who); return PQ_ERR_ARG; }
+    for (int j = 0; j < n_lines && b->len > 0; j++)
+        if (!lines[j]) { pq_set_error("%s: null line pointer", who); return PQ_ERR_ARG; }
+    if (benchmark && bench_series_stride != 0 && bench_series_stride < b->len) { pq_set_error("%s: bench_series_stride must be 0 or >= len", who); return PQ_ERR_ARG; }
+    const int waves = sw_waves(n_lines, R, n_rules);
+    const int64_t pblocks = (n_rules + 64 * waves - 1) / (64 * waves);
+    if (!(b->len <= 0x7fffffffLL && n_rules <= 0x7fffffffLL && pblocks * b->n_series <= 0x7fffffffLL)) { pq_set_error("%s: batch or grid too large", who); return PQ_ERR_ARG; }
+    // the table is checked on the host before anything is launched: the kernel indexes LDS with a, b and c
+    std::vector<pq_sweep_rule> host((size_t)n_rules);
+    PQ_HIP_TRY(hipMemcpyAsync(host.data(), rules, sizeof(pq_sweep_rule) * (size_t)n_rules, hipMemcpyDeviceToHost, ctx->stream));
+    PQ_HIP_TRY(hipStreamSynchronize(ctx->stream));
+    int one_rule = host[0].rule; // the rule of every set, or SW_GENERIC
+    for (int64_t i = 0; i < n_rules; i++) {
+        const pq_sweep_rule &q = host[(size_t)i];
+        if (q.rule < 0 || q.rule > max_rule) { pq_set_error("%s: parameter set %lld: unknown rule %d (the rules are 0 .. %d)", who, (long long)i, (int)q.rule, max_rule); return PQ_ERR_ARG; }
+        if (q.a < 0 || q.a >= n_lines || (sw_uses_b(q.rule) && (q.b < 0 || q.b >= n_lines))) {
+            pq_set_error("%s: parameter set %lld: line a=%d b=%d outside [0, %d)", who, (long long)i, (int)q.a, (int)q.b, (int)n_lines);
+            return PQ_ERR_ARG;
+        }
+        if (sw_uses_c(q.rule) && (q.c < -1 || q.c >= n_lines)) {
+            pq_set_error("%s: parameter set %lld: column c=%d outside [-1, %d) (-1 is the price)", who, (long long)i, (int)q.c, (int)n_lines);
+            return PQ_ERR_ARG;
+        }
+        if (q.rule != one_rule) one_rule = SW_GENERIC;
+    }
+    if (b->len == 0) { // calculate_summary on no rows: all zeros (metrics.rs:17-19)
+        PQ_HIP_TRY(hipMemsetAsync(summary, 0, sizeof(double) * PQ_SUMMARY_COLS * (size_t)b->n_series * (size_t)n_rules, ctx->stream));
+        return PQ_OK;
+    }
+    PQ_TRY(pq_ws_reserve(ctx, sizeof(double *) * (size_t)n_lines));
+    PQ_HIP_TRY(hipMemcpyAsync(ctx->ws, lines, sizeof(double *) * (size_t)n_lines, hipMemcpyHostToDevice, ctx->stream));
+    PQ_HIP_TRY(hipStreamSynchronize(ctx->stream)); // the caller's table may go away after the call
+    SwArgs g{};
+    g.price = price; g.lines = (const double *const *)ctx->ws; g.params = rules; g.bench = benchmark; g.summary = summary; g.prm = *bt;
+    g.len = b->len; g.stride = b->stride; g.bench_stride = bench_series_stride; g.n_params = n_rules;
+    g.n_lines = n_lines; g.R = R; g.pblocks = (int32_t)pblocks;
+    g.magic = ((1u << 20) + (uint32_t)R - 1u) / (uint32_t)R;
+    const size_t lds = sizeof(double) * 2 * (size_t)(n_lines + 2) * (size_t)R; // <= 2 * SW_TILE doubles = 64 KB
+    const dim3 grid((unsigned)(pblocks * b->n_series));
+    const SwKernel kernel = benchmark ? sw_kernel_for<true>(one_rule) : sw_kernel_for<false>(one_rule);
+    hipLaunchKernelGGL(kernel, grid, dim3(64 * waves), lds, ctx->stream, g);
+    PQ_HIP_TRY(hipGetLastError());
+    return PQ_OK;
+}
 } // namespace
 
 extern "C" {
@@ -256,50 +384,16 @@ int32_t pq_sweep_row_tile(int32_t n_lines) { return sw_row_tile(n_lines); }
 pq_status pq_backtest_sweep(pq_ctx *ctx, const pq_batch *b, const double *price, const double *const *lines, int32_t n_lines,
                             const pq_sweep_param *params, int64_t n_params, const double *benchmark, int64_t bench_series_stride,
                             const pq_bt_params *bt, double *summary) {
-    PQ_TRY(pq_check(ctx, b));
-    if (ctx->rec) { pq_set_error("pq_backtest_sweep cannot be recorded into a suite"); return PQ_ERR_UNSUPPORTED; }
-    PQ_NO_RAGGED(b, "pq_backtest_sweep");
-    PQ_REQUIRE(n_params >= 0, "pq_backtest_sweep: negative n_params");
-    const int R = sw_row_tile(n_lines);
-    if (R == 0) { pq_set_error("pq_backtest_sweep: n_lines must be in [1, %d], not %d", PQ_SWEEP_MAX_LINES, (int)n_lines); return PQ_ERR_ARG; }
-    PQ_REQUIRE(bt, "pq_backtest_sweep: null parameters");
-    if (n_params == 0 || b->n_series == 0) return PQ_OK;
-    PQ_REQUIRE(params && summary && (b->len == 0 || (price && lines)), "pq_backtest_sweep: null pointer");
-    for (int j = 0; j < n_lines && b->len > 0; j++) PQ_REQUIRE(lines[j], "pq_backtest_sweep: null line pointer");
-    PQ_REQUIRE(!benchmark || bench_series_stride == 0 || bench_series_stride >= b->len, "pq_backtest_sweep: bench_series_stride must be 0 or >= len");
-    const int waves = sw_waves(n_lines, R, n_params);
-    const int64_t pblocks = (n_params + 64 * waves - 1) / (64 * waves);
-    PQ_REQUIRE(b->len <= 0x7fffffffLL && n_params <= 0x7fffffffLL && pblocks * b->n_series <= 0x7fffffffLL, "pq_backtest_sweep: batch or grid too large");
-    // the table is checked on the host before anything is launched: the kernel indexes LDS with a and b
-    std::vector<pq_sweep_param> host((size_t)n_params);
-    PQ_HIP_TRY(hipMemcpyAsync(host.data(), params, sizeof(pq_sweep_param) * (size_t)n_params, hipMemcpyDeviceToHost, ctx->stream));
-    PQ_HIP_TRY(hipStreamSynchronize(ctx->stream));
-    for (int64_t i = 0; i < n_params; i++) {
-        const pq_sweep_param &q = host[(size_t)i];
-        if (q.rule != 0 && q.rule != 1) { pq_set_error("pq_backtest_sweep: parameter set %lld: unknown rule %d (0 cross, 1 band)", (long long)i, (int)q.rule); return PQ_ERR_ARG; }
-        if (q.a < 0 || q.a >= n_lines || (q.rule == 0 && (q.b < 0 || q.b >= n_lines))) {
-            pq_set_error("pq_backtest_sweep: parameter set %lld: line a=%d b=%d outside [0, %d)", (long long)i, (int)q.a, (int)q.b, (int)n_lines);
-            return PQ_ERR_ARG;
-        }
-    }
-    if (b->len == 0) { // calculate_summary on no rows: all zeros (metrics.rs:17-19)
-        PQ_HIP_TRY(hipMemsetAsync(summary, 0, sizeof(double) * PQ_SUMMARY_COLS * (size_t)b->n_series * (size_t)n_params, ctx->stream));
-        return PQ_OK;
-    }
-    PQ_TRY(pq_ws_reserve(ctx, sizeof(double *) * (size_t)n_lines));
-    PQ_HIP_TRY(hipMemcpyAsync(ctx->ws, lines, sizeof(double *) * (size_t)n_lines, hipMemcpyHostToDevice, ctx->stream));
-    PQ_HIP_TRY(hipStreamSynchronize(ctx->stream)); // the caller's table may go away after the call
-    SwArgs g{};
-    g.price = price; g.lines = (const double *const *)ctx->ws; g.params = params; g.bench = benchmark; g.summary = summary; g.prm = *bt;
-    g.len = b->len; g.stride = b->stride; g.bench_stride = bench_series_stride; g.n_params = n_params;
-    g.n_lines = n_lines; g.R = R; g.pblocks = (int32_t)pblocks;
-    g.magic = ((1u << 20) + (uint32_t)R - 1u) / (uint32_t)R;
-    const size_t lds = sizeof(double) * 2 * (size_t)(n_lines + 2) * (size_t)R; // <= 2 * SW_TILE doubles = 64 KB
-    const dim3 grid((unsigned)(pblocks * b->n_series));
-    if (benchmark) hipLaunchKernelGGL(sweep_kernel<true>, grid, dim3(64 * waves), lds, ctx->stream, g);
-    else hipLaunchKernelGGL(sweep_kernel<false>, grid, dim3(64 * waves), lds, ctx->stream, g);
-    PQ_HIP_TRY(hipGetLastError());
-    return PQ_OK;
+    // the same 32 bytes; rules 0 and 1 never look at _pad / c
+    return sw_run("pq_backtest_sweep", PQ_SWEEP_RULE_BAND, ctx, b, price, lines, n_lines, reinterpret_cast<const pq_sweep_rule *>(params), n_params,
+                  benchmark, bench_series_stride, bt, summary);
+}
+
+pq_status pq_backtest_sweep_rules(pq_ctx *ctx, const pq_batch *b, const double *price, const double *const *lines, int32_t n_lines,
+                                  const pq_sweep_rule *rules, int64_t n_rules, const double *benchmark, int64_t bench_series_stride,
+                                  const pq_bt_params *bt, double *summary) {
+    return sw_run("pq_backtest_sweep_rules", PQ_SWEEP_RULE_CROSS_STRENGTH, ctx, b, price, lines, n_lines, rules, n_rules, benchmark,
+                  bench_series_stride, bt, summary);
 }
 
 } // extern "C"

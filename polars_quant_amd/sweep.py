@@ -6,7 +6,12 @@ existing indicator call and hands the lines and a table of parameter sets -- rul
 band(lines[a], k0, k1), the rules of `Strategy.ma` / `.macd` / `.rsi` -- to pq_backtest_sweep, whose lanes are the parameter sets.  The
 result is the [P, N, 8] summary (SUMMARY_KEYS order) and nothing else: no signal or equity column exists.
 
-The grid builders (ma_grid, macd_grid, rsi_grid) are pure host code; like strategy.py this module holds no arithmetic of its own.
+`bband`, `stoch`, `cci`, `adx`, `breakout`, `reversion` and `grid` go through pq_backtest_sweep_rules, whose table has a third column
+index c (-1: the price) and the rules 2 channel, 3 breakout, 4 channel around a scaled base line, 5 cross in zones, 6 cross with
+strength (include/pq_hip.h).  Not covered: `ma`'s trend / slope / distance filters, `volume`, `gap`, `pattern`, `trend`.
+
+The grid builders (ma_grid, macd_grid, rsi_grid, bband_grid, ...) are pure host code; like strategy.py this module holds no arithmetic
+of its own.
 """
 from __future__ import annotations
 
@@ -17,6 +22,8 @@ from ._spec import BT_DEFAULTS, SUMMARY_KEYS
 from .strategy import _MA
 
 RULE_CROSS, RULE_BAND = 0, 1
+RULE_CHANNEL, RULE_BREAKOUT, RULE_SCALED_CHANNEL, RULE_CROSS_ZONES, RULE_CROSS_STRENGTH = 2, 3, 4, 5, 6
+PRICE = -1   # column c of a rule: the price column itself
 
 
 def _ints(xs, what):
@@ -71,6 +78,110 @@ def rsi_grid(periods, oversold, overbought):
     params = {"period": np.array([s[1] for s in sets], dtype=np.int64), "oversold": np.array([s[2] for s in sets]),
               "overbought": np.array([s[3] for s in sets])}
     return ps, rules, params
+
+
+def _floats(xs):
+    return [float(x) for x in np.atleast_1d(np.asarray(xs, dtype=np.float64))]
+
+
+def _rule_table(rule, a, b=None, c=None, k0=None, k1=None):
+    tab = np.zeros(len(a), dtype=_api.SWEEP_RULE_DTYPE)
+    tab["rule"] = rule
+    tab["a"] = a
+    tab["b"] = a if b is None else b
+    tab["c"] = PRICE if c is None else c
+    if k0 is not None:
+        tab["k0"] = k0
+    if k1 is not None:
+        tab["k1"] = k1
+    return tab
+
+
+def _band_grid(periods, lower, upper):
+    """one line per distinct period (in the order given), period x lower x upper sets -> (periods, SWEEP_RULE_DTYPE table, the sets)"""
+    ps = list(dict.fromkeys(_ints(periods, "periods")))
+    sets = [(j, p, l, h) for j, p in enumerate(ps) for l in lower for h in upper]
+    tab = _rule_table(RULE_BAND, [s[0] for s in sets], c=0, k0=[s[2] for s in sets], k1=[s[3] for s in sets])
+    return ps, tab, sets
+
+
+def bband_grid(periods, nbdevs):
+    """-> (pairs, rules, params): the P = #periods x #nbdevs pairs (period, nbdev), period-major; set i owns lines 2 i (the lower band)
+    and 2 i + 1 (the upper band) of bbands(x, period, nbdev, nbdev) and trades the price against them (rule 2, c = -1)"""
+    pairs = [(p, d) for p in dict.fromkeys(_ints(periods, "periods")) for d in dict.fromkeys(_floats(nbdevs))]
+    i = np.arange(len(pairs))
+    rules = _rule_table(RULE_CHANNEL, 2 * i, 2 * i + 1)
+    params = {"period": np.array([p for p, _ in pairs], dtype=np.int64), "nbdev": np.array([d for _, d in pairs], dtype=np.float64)}
+    return pairs, rules, params
+
+
+def stoch_grid(fastk_periods, slowk_periods, slowd_periods, oversold, overbought):
+    """-> (triples, rules, params): the distinct (fastk, slowk, slowd) triples -- triple j owns lines 2 j (%K) and 2 j + 1 (%D) -- and the
+    P = #triples x #oversold x #overbought sets, fastk outermost: %K crossing %D, gated by the zones of %K (rule 5, c = a)"""
+    fk, sk, sd = (list(dict.fromkeys(_ints(x, w))) for x, w in ((fastk_periods, "fastk_periods"), (slowk_periods, "slowk_periods"),
+                                                                 (slowd_periods, "slowd_periods")))
+    triples = [(f, k, d) for f in fk for k in sk for d in sd]
+    sets = [(j, t, l, h) for j, t in enumerate(triples) for l in _floats(oversold) for h in _floats(overbought)]
+    k = np.array([2 * s[0] for s in sets], dtype=np.int64)
+    rules = _rule_table(RULE_CROSS_ZONES, k, k + 1, k, [s[2] for s in sets], [s[3] for s in sets])
+    params = {name: np.array([s[1][j] for s in sets], dtype=np.int64) for j, name in enumerate(("fastk_period", "slowk_period", "slowd_period"))}
+    params["oversold"], params["overbought"] = np.array([s[2] for s in sets]), np.array([s[3] for s in sets])
+    return triples, rules, params
+
+
+def cci_grid(periods, oversold, overbought):
+    """-> (periods, rules, params): like rsi_grid, one CCI line per distinct period"""
+    ps, rules, sets = _band_grid(periods, _floats(oversold), _floats(overbought))
+    params = {"period": np.array([s[1] for s in sets], dtype=np.int64), "oversold": np.array([s[2] for s in sets]),
+              "overbought": np.array([s[3] for s in sets])}
+    return ps, rules, params
+
+
+def adx_grid(periods, thresholds):
+    """-> (periods, rules, params): period j owns lines 3 j (plus_dm), 3 j + 1 (minus_dm) and 3 j + 2 (adx); the P = #periods x
+    #thresholds sets, period-major: plus_dm crossing minus_dm while adx > threshold (rule 6)"""
+    ps = list(dict.fromkeys(_ints(periods, "periods")))
+    sets = [(j, p, th) for j, p in enumerate(ps) for th in _floats(thresholds)]
+    k = np.array([3 * s[0] for s in sets], dtype=np.int64)
+    rules = _rule_table(RULE_CROSS_STRENGTH, k, k + 1, k + 2, [s[2] for s in sets])
+    params = {"period": np.array([s[1] for s in sets], dtype=np.int64), "threshold": np.array([s[2] for s in sets])}
+    return ps, rules, params
+
+
+def breakout_grid(periods, close_is_price=True):
+    """-> (periods, rules, params): period j owns lines 2 j (rolling_min(low)) and 2 j + 1 (rolling_max(high)); the close breaks out of
+    the previous row's channel (rule 3).  The close is the price column (c = -1) or, with close_is_price=False, one more line after
+    the channels"""
+    ps = list(dict.fromkeys(_ints(periods, "periods")))
+    j = np.arange(len(ps))
+    rules = _rule_table(RULE_BREAKOUT, 2 * j, 2 * j + 1, PRICE if close_is_price else 2 * len(ps))
+    return ps, rules, {"period": np.array(ps, dtype=np.int64)}
+
+
+def reversion_grid(periods, thresholds):
+    """-> (periods, rules, params): one z-score line per distinct period; the P = #periods x #thresholds sets, period-major, are the
+    band (-threshold, +threshold)"""
+    ths = _floats(thresholds)
+    ps = list(dict.fromkeys(_ints(periods, "periods")))
+    sets = [(j, p, th) for j, p in enumerate(ps) for th in ths]
+    rules = _rule_table(RULE_BAND, [s[0] for s in sets], c=0, k0=[-s[2] for s in sets], k1=[s[2] for s in sets])
+    params = {"period": np.array([s[1] for s in sets], dtype=np.int64), "threshold": np.array([s[2] for s in sets])}
+    return ps, rules, params
+
+
+def grid_grid(base_periods, grid_pcts):
+    """-> (periods, rules, params): one SMA base line per distinct period; the P = #periods x #grid_pcts sets, period-major, trade the
+    price against base x (1 - pct %) and base x (1 + pct %) (rule 4, c = -1); the factors are `Strategy.grid`'s expressions"""
+    ps = list(dict.fromkeys(_ints(base_periods, "base_periods")))
+    sets = [(j, p, pct) for j, p in enumerate(ps) for pct in _floats(grid_pcts)]
+    rules = _rule_table(RULE_SCALED_CHANNEL, [s[0] for s in sets], k0=[1.0 - s[2] / 100.0 for s in sets], k1=[1.0 + s[2] / 100.0 for s in sets])
+    params = {"base_period": np.array([s[1] for s in sets], dtype=np.int64), "grid_pct": np.array([s[2] for s in sets])}
+    return ps, rules, params
+
+
+def _fits(n_lines, what):
+    if n_lines > _api.SWEEP_MAX_LINES:
+        raise ValueError(f"{what}: the grid needs {n_lines} lines, a sweep takes {_api.SWEEP_MAX_LINES} at the most")
 
 
 class SweepResult:
@@ -142,3 +253,82 @@ class ParameterSweep:
         x = self.df[price_col]
         lines = [_api.call("rsi", x, timeperiod=p)[0] for p in ps]
         return self.run(lines, rules, params, price_col)
+
+    # ---- the rules with a third column (pq_backtest_sweep_rules) ---------------------------------------------------------------------
+    def run_rules(self, lines, rules, params=None, price_col="close"):
+        """caller-built lines and rules (api.sweep_rules: rule / a / b / c / k0 / k1, c = -1 for the price) -> SweepResult"""
+        tab = _api.sweep_rules(rules)
+        if params is None:
+            params = {k: tab[k].copy() for k in tab.dtype.names}
+        summ = _api.backtest_sweep_rules(self.df[price_col], lines, tab, benchmark=self.benchmark, **self.costs)
+        return SweepResult(params, summ)
+
+    def bband(self, periods, nbdevs, price_col="close"):
+        """the grid of `Strategy.bband`: the price against the Bollinger bands of every (period, nbdev)"""
+        pairs, rules, params = bband_grid(periods, nbdevs)
+        _fits(2 * len(pairs), "bband")
+        x = self.df[price_col]
+        lines = []
+        for p, d in pairs:
+            up, _mid, lo = _api.call("bbands", x, timeperiod=p, nbdevup=d, nbdevdn=d)
+            lines += [lo, up]
+        return self.run_rules(lines, rules, params, price_col)
+
+    def stoch(self, fastk_periods, slowk_periods, slowd_periods, oversold, overbought, price_col="close"):
+        """the grid of `Strategy.stoch`: %K and %D once per period triple, every (oversold, overbought) zone pair on them"""
+        triples, rules, params = stoch_grid(fastk_periods, slowk_periods, slowd_periods, oversold, overbought)
+        _fits(2 * len(triples), "stoch")
+        lines = []
+        for f, k, d in triples:
+            lines += list(_api.call("stoch", self.df["high"], self.df["low"], self.df["close"], fastk_period=f, slowk_period=k, slowd_period=d))
+        return self.run_rules(lines, rules, params, price_col)
+
+    def cci(self, periods, oversold, overbought, price_col="close"):
+        """the grid of `Strategy.cci` bands: one line per period"""
+        ps, rules, params = cci_grid(periods, oversold, overbought)
+        _fits(len(ps), "cci")
+        lines = [_api.call("cci", self.df["high"], self.df["low"], self.df["close"], timeperiod=p)[0] for p in ps]
+        return self.run_rules(lines, rules, params, price_col)
+
+    def adx(self, periods, thresholds, price_col="close"):
+        """the grid of `Strategy.adx`: plus_dm, minus_dm and adx once per period, every threshold on them"""
+        ps, rules, params = adx_grid(periods, thresholds)
+        _fits(3 * len(ps), "adx")
+        h, l, c = self.df["high"], self.df["low"], self.df["close"]
+        lines = []
+        for p in ps:
+            lines += [_api.call("plus_dm", h, l, timeperiod=p)[0], _api.call("minus_dm", h, l, timeperiod=p)[0],
+                      _api.call("adx", h, l, c, timeperiod=p)[0]]
+        return self.run_rules(lines, rules, params, price_col)
+
+    def breakout(self, periods, price_col="close"):
+        """the grid of `Strategy.breakout`: the Donchian channel of every period; the signal is taken on the close whatever the price
+        column of the backtest is"""
+        close_is_price = price_col == "close"
+        ps, rules, params = breakout_grid(periods, close_is_price)
+        _fits(2 * len(ps) + (0 if close_is_price else 1), "breakout")
+        lines = []
+        for p in ps:
+            lines += [_api.call("rolling_min", self.df["low"], window=p)[0], _api.call("rolling_max", self.df["high"], window=p)[0]]
+        if not close_is_price:
+            lines.append(self.df["close"])
+        return self.run_rules(lines, rules, params, price_col)
+
+    def reversion(self, periods, thresholds, price_col="close"):
+        """the grid of `Strategy.reversion`: one z-score line per period, every threshold on it"""
+        ps, rules, params = reversion_grid(periods, thresholds)
+        _fits(len(ps), "reversion")
+        x = self.df[price_col]
+        lines = []
+        for p in ps:
+            up, mid, _lo = _api.call("bbands", x, timeperiod=p, nbdevup=1.0, nbdevdn=1.0)
+            lines.append(_api.zscore(x, up, mid))
+        return self.run_rules(lines, rules, params, price_col)
+
+    def grid(self, base_periods, grid_pcts, price_col="close"):
+        """the grid of `Strategy.grid`: one SMA base line per period, every percentage around it"""
+        ps, rules, params = grid_grid(base_periods, grid_pcts)
+        _fits(len(ps), "grid")
+        x = self.df[price_col]
+        lines = [_api.call("sma", x, timeperiod=p)[0] for p in ps]
+        return self.run_rules(lines, rules, params, price_col)
