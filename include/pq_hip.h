@@ -528,6 +528,29 @@ pq_status pq_backtest_sweep_rules(pq_ctx *, const pq_batch *, const double *pric
                                   const pq_sweep_rule *rules /* device */, int64_t n_rules,
                                   const double *benchmark, int64_t bench_series_stride /* 0: one [len] series shared by all */,
                                   const pq_bt_params *bt, double *summary /* [n_series][n_rules][8] */);
+/* ---- walk-forward windows (decision D-26 in DESIGN.md).  pq_backtest_sweep_windows: pq_backtest_sweep_rules with one more grid axis, the
+ * window -- a HOST table of n_windows row ranges [t0, t1) of the same columns, which may overlap or repeat.  summary is
+ * [n_windows][n_series][n_rules][8], and summary[w] is bit for bit what pq_backtest_sweep_rules writes for the rows [t0, t1) alone: the
+ * scan starts flat with initial_capital at t0, row t0 never signals (row t0 - 1 of a line is never read, under rule 3 as well), the
+ * number of rows in the summary is t1 - t0, the benchmark return of row t0 is taken against row t0 and alpha spans benchmark[t0] ..
+ * benchmark[t1 - 1].  The lines are NOT restarted: a window of a causal indicator computed over the whole history is a warmed-up
+ * indicator.  t0 == t1: that window's cells are 0 (metrics.rs:17-19).  PQ_ERR_ARG (naming the window): t0 < 0, t1 > len, t0 > t1;
+ * also n_windows < 0 and a grid beyond 2^31 - 1 blocks.  n_windows = 0 writes nothing.  Everything else -- the table check, limits, ragged
+ * batches, recording -- is pq_backtest_sweep_rules's; the window table is copied into the context workspace behind the line pointers.
+ * pq_sweep_select: per fold f and symbol s the parameter set with the largest (maximize != 0) or smallest summary[train[f]][s][.][metric_col]
+ * -- a NaN ranks last, the lowest index wins a tie, an all-NaN column gives 0 -- as chosen [n_folds][n_series], and that set's eight
+ * values in the train window (in_sample) and in the test window (out_sample), both [n_folds][n_series][8].  train / test: HOST tables
+ * of window indices.  PQ_ERR_ARG: metric_col outside [0, 8), an index outside [0, n_windows), n_params < 1 with n_folds n_series > 0. */
+typedef struct { int64_t t0, t1; } pq_sweep_window; /* rows [t0, t1) */
+pq_status pq_backtest_sweep_windows(pq_ctx *, const pq_batch *, const double *price, const double *const *lines, int32_t n_lines,
+                                    const pq_sweep_rule *rules /* device */, int64_t n_rules,
+                                    const pq_sweep_window *windows /* HOST */, int64_t n_windows,
+                                    const double *benchmark, int64_t bench_series_stride /* 0: one [len] series shared by all */,
+                                    const pq_bt_params *bt, double *summary /* [n_windows][n_series][n_rules][8] */);
+pq_status pq_sweep_select(pq_ctx *, const double *summary /* [n_windows][n_series][n_params][8] */, int64_t n_windows, int64_t n_series,
+                          int64_t n_params, const int32_t *train /* HOST [n_folds] */, const int32_t *test /* HOST [n_folds] */,
+                          int64_t n_folds, int32_t metric_col, int32_t maximize, int32_t *chosen /* [n_folds][n_series] */,
+                          double *in_sample /* [n_folds][n_series][8] */, double *out_sample /* [n_folds][n_series][8] */);
 
 /* ---- cross-sectional factor evaluation, Factor.ic / rank_ic / rolling_ic (README.md:1429-1430,
  * :1480-1482, :1626-1634; README-only, decision D-12 in oracle/backtest.c).  factor / fwd_return: [n_series][stride];

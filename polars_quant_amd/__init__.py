@@ -13,7 +13,7 @@ from .linear import linear
 from .returns import returns
 from .sequential import OrderContext, OrderTape, SequentialBacktester
 from .strategy import Strategy
-from .sweep import ParameterSweep, SweepResult
+from .sweep import ParameterSweep, SweepResult, WalkForwardResult, walk_forward_windows
 from .talib import *  # noqa: F401,F403
 
 __version__ = "0.1.0"

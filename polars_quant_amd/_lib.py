@@ -161,6 +161,11 @@ def lib() -> C.CDLL:
         L.pq_backtest_sweep.argtypes = [vp, C.POINTER(Batch), vp, C.POINTER(vp), C.c_int32, vp, C.c_int64, vp, C.c_int64, C.POINTER(BtParams), vp]
         L.pq_backtest_sweep_rules.restype = C.c_int32
         L.pq_backtest_sweep_rules.argtypes = L.pq_backtest_sweep.argtypes
+        L.pq_backtest_sweep_windows.restype = C.c_int32
+        L.pq_backtest_sweep_windows.argtypes = [vp, C.POINTER(Batch), vp, C.POINTER(vp), C.c_int32, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64,
+                                                C.POINTER(BtParams), vp]
+        L.pq_sweep_select.restype = C.c_int32
+        L.pq_sweep_select.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp]
         L.pq_sweep_row_tile.restype = C.c_int32
         L.pq_sweep_row_tile.argtypes = [C.c_int32]
         L.pq_recommended_stride.restype = C.c_int64

@@ -1369,8 +1369,19 @@ def sweep_params(rules) -> np.ndarray:
     return out
 
 
-def _backtest_sweep(who, entry, tab, price, lines, benchmark, out, offsets, kw):
-    """pq_backtest_sweep and pq_backtest_sweep_rules take the same arguments: `entry` is the one to call, `tab` its 32-byte table"""
+def sweep_windows(windows) -> np.ndarray:
+    """a contiguous int64 [W, 2] table of row ranges [t0, t1) (pq_sweep_window) from any integer array of that shape"""
+    w = np.asarray(windows)
+    if w.size == 0:
+        w = np.zeros((0, 2), dtype=np.int64)
+    if w.ndim != 2 or w.shape[1] != 2 or w.dtype.kind not in "iu":
+        raise ValueError(f"windows must be an integer [W, 2] array of row ranges [t0, t1), not {w.dtype} {w.shape}")
+    return np.ascontiguousarray(w, dtype=np.int64)
+
+
+def _backtest_sweep(who, entry, tab, price, lines, benchmark, out, offsets, kw, windows=None):
+    """pq_backtest_sweep and pq_backtest_sweep_rules take the same arguments: `entry` is the one to call, `tab` its 32-byte table.
+    windows (D-26): a sweep_windows table, which goes to pq_backtest_sweep_windows instead (either table is the same 32 bytes)"""
     prm = BtParams(**{**BT_DEFAULTS, **kw})
     cols = list(lines) if isinstance(lines, (list, tuple)) else [lines[j] for j in range(_shape(lines)[0])]
     if not 1 <= len(cols) <= SWEEP_MAX_LINES:
@@ -1393,28 +1404,40 @@ def _backtest_sweep(who, entry, tab, price, lines, benchmark, out, offsets, kw):
             bstride = bm.stride(0)
         else:
             raise PqError(f"{who}: `benchmark` has shape {tuple(bm.shape)}, expected {(T,)} or {(n, T)}")
+    win = None if windows is None else sweep_windows(windows)
+    shape = (n, P, 8) if win is None else (len(win), n, P, 8)
     if out is None:
-        out = torch.empty((n, P, 8), dtype=torch.float64, device=dev)
-    elif tuple(out.shape) != (n, P, 8) or out.dtype != torch.float64 or not out.is_contiguous() or out.device != dev:
-        raise ValueError(f"out must be a contiguous float64 tensor of shape {(n, P, 8)} on {dev}")
-    if n and P:
+        out = torch.empty(shape, dtype=torch.float64, device=dev)
+    elif tuple(out.shape) != shape or out.dtype != torch.float64 or not out.is_contiguous() or out.device != dev:
+        raise ValueError(f"out must be a contiguous float64 tensor of shape {shape} on {dev}")
+    if n and P and (win is None or len(win)):
         dtab = torch.from_numpy(tab.view(np.uint8).reshape(P, tab.dtype.itemsize)).to(dev)
         vp = C.c_void_p
         ptrs = (vp * len(cols))(*[m.data_ptr() for m in mats[1:]])
+        head = (ctx(dev.index), C.byref(b), vp(p.data_ptr()), ptrs, C.c_int32(len(cols)), vp(dtab.data_ptr()), C.c_int64(P))
+        tail = (vp(bm.data_ptr()) if bm is not None else None, C.c_int64(bstride), C.byref(prm), vp(out.data_ptr()))
         with torch.cuda.device(dev):
-            check(getattr(lib(), entry)(ctx(dev.index), C.byref(b), vp(p.data_ptr()), ptrs, C.c_int32(len(cols)), vp(dtab.data_ptr()),
-                                        C.c_int64(P), vp(bm.data_ptr()) if bm is not None else None, C.c_int64(bstride),
-                                        C.byref(prm), vp(out.data_ptr())))
+            if win is None:
+                check(getattr(lib(), entry)(*head, *tail))
+            else:
+                check(lib().pq_backtest_sweep_windows(*head, vp(win.ctypes.data), C.c_int64(len(win)), *tail))
     del keep
-    return out.permute(1, 0, 2)
+    return out.permute(1, 0, 2) if win is None else out.permute(0, 2, 1, 3)
 
 
-def backtest_sweep(price, lines, params, benchmark=None, out=None, offsets=None, **kw):
+def backtest_sweep(price, lines, params, benchmark=None, out=None, offsets=None, windows=None, **kw):
     """D-25: every parameter set of `params` (sweep_params) over every symbol in ONE launch -> device summary [P, N, 8], a permuted
     view of the kernel's [N, P, 8].  price [N, T]; lines: a list of [N, T] candidate indicator columns or one [L, N, T] array;
     benchmark: None, one [T] series shared by all symbols, or [N, T]; out: a contiguous device [N, P, 8] float64 tensor to write into;
-    offsets: ragged groups of long columns (see call()) are not supported by the sweep and raise."""
-    return _backtest_sweep("backtest_sweep", "pq_backtest_sweep", sweep_params(params), price, lines, benchmark, out, offsets, kw)
+    offsets: ragged groups of long columns (see call()) are not supported by the sweep and raise.
+    windows (D-26): an integer [W, 2] array of row ranges [t0, t1) -> device [W, P, N, 8], a permuted view of the kernel's
+    [W, N, P, 8] (the shape of `out`), still one launch; entry w is bit for bit the sweep of the rows [t0, t1) alone.  The windowed
+    entry point knows all seven rules, so a rule beyond 1 is refused here, in Python, with a PqError whose text differs from the one
+    pq_backtest_sweep itself gives for the same mistake without `windows`."""
+    tab = sweep_params(params)
+    if windows is not None and len(tab) and not (tab["rule"] <= 1).all():      # pq_backtest_sweep_windows knows all seven rules
+        raise PqError("backtest_sweep: unknown rule (the rules are 0 and 1; backtest_sweep_rules has the others)")
+    return _backtest_sweep("backtest_sweep", "pq_backtest_sweep", tab, price, lines, benchmark, out, offsets, kw, windows)
 
 
 # pq_sweep_rule (include/pq_hip.h): pq_sweep_param with a third column index c (-1: the price) -- the rules of backtest_sweep_rules:
@@ -1442,7 +1465,37 @@ def sweep_rules(rules) -> np.ndarray:
     return out
 
 
-def backtest_sweep_rules(price, lines, rules, benchmark=None, out=None, **kw):
+def backtest_sweep_rules(price, lines, rules, benchmark=None, out=None, windows=None, **kw):
     """backtest_sweep with the seven rules of pq_backtest_sweep_rules: `rules` is a sweep_rules table whose column c names a third
-    column (a line, or -1 for `price`) -> device summary [P, N, 8].  The other arguments are backtest_sweep's."""
-    return _backtest_sweep("backtest_sweep_rules", "pq_backtest_sweep_rules", sweep_rules(rules), price, lines, benchmark, out, None, kw)
+    column (a line, or -1 for `price`) -> device summary [P, N, 8], or [W, P, N, 8] with `windows`.  The other arguments are
+    backtest_sweep's."""
+    return _backtest_sweep("backtest_sweep_rules", "pq_backtest_sweep_rules", sweep_rules(rules), price, lines, benchmark, out, None, kw, windows)
+
+
+def sweep_select(summary, train, test, metric, maximize=True):
+    """D-26, pq_sweep_select: summary: the device [W, P, N, 8] result of a windowed sweep (the permuted view of a contiguous
+    [W, N, P, 8]); train / test: F window indices each; metric: a SUMMARY_KEYS name or column index.  Per fold and symbol the set with
+    the largest (smallest) metric in the train window -- a NaN ranks last, the lowest index wins a tie, all NaN gives 0 -- ->
+    (chosen [F, N] int32, in_sample [F, N, 8], out_sample [F, N, 8]): the chosen set's summary in the train and in the test window."""
+    if not isinstance(summary, torch.Tensor) or summary.dim() != 4 or summary.shape[3] != 8 or summary.dtype != torch.float64 or not summary.is_cuda:
+        raise ValueError("summary must be a device float64 [W, P, N, 8] tensor")
+    base = summary.permute(0, 2, 1, 3)
+    if not base.is_contiguous():
+        base = base.contiguous()
+    W, n, P, _ = base.shape
+    col = SUMMARY_KEYS.index(metric) if isinstance(metric, str) and metric in SUMMARY_KEYS else metric
+    if isinstance(col, str):
+        raise KeyError(f"metric must be one of {SUMMARY_KEYS}")
+    tr, te = (np.ascontiguousarray(np.atleast_1d(np.asarray(x)), dtype=np.int32) for x in (train, test))
+    if tr.ndim != 1 or tr.shape != te.shape:
+        raise ValueError(f"train and test must be equally long lists of window indices, not {tr.shape} and {te.shape}")
+    F = len(tr)
+    dev = base.device
+    chosen = torch.empty((F, n), dtype=torch.int32, device=dev)
+    ins, outs = (torch.empty((F, n, 8), dtype=torch.float64, device=dev) for _ in range(2))
+    vp = C.c_void_p
+    with torch.cuda.device(dev):
+        check(lib().pq_sweep_select(ctx(dev.index), vp(base.data_ptr()), C.c_int64(W), C.c_int64(n), C.c_int64(P), vp(tr.ctypes.data),
+                                    vp(te.ctypes.data), C.c_int64(F), C.c_int32(int(col)), C.c_int32(1 if maximize else 0),
+                                    vp(chosen.data_ptr()), vp(ins.data_ptr()), vp(outs.data_ptr())))
+    return chosen, ins, outs

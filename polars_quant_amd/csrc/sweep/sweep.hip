@@ -21,6 +21,7 @@
 // the same deterministic state machine both times (walk 1: sum of returns, peak, drawdown, trades, wins; walk 2: the squared deviations
 // and the covariance in the same row order).  A one-pass sum of squares would cancel.  Only pow differs from the host.
 #include "../pq_dev.h"
+#include "../wave_util.h"
 #include <vector>
 
 namespace {
@@ -102,18 +103,20 @@ __device__ __forceinline__ SwSrc sw_src(const SwArgs &g, int64_t s, int e) {
     return r;
 }
 
-// global memory -> registers: rows [t0, t0 + R) of every staged column.  A thread holds at most one benchmark element (R < 64),
-// whose predecessor row comes along in bprev (metrics.rs:91-98: the return of row 0 is taken against row 0 itself).
+// global memory -> registers: rows [t0, t0 + R) of every staged column, of the rows [lo, hi) that the walk covers (the whole series, or
+// one window of it).  A thread holds at most one benchmark element (R < 64), whose predecessor row comes along in bprev
+// (metrics.rs:91-98: the return of the first row is taken against that row itself).
 template <bool BENCH>
-__device__ __forceinline__ void sw_fetch(const SwArgs &g, int64_t s, int64_t t0, double (&pre)[SW_PRE], double &bprev) {
+__device__ __forceinline__ void sw_fetch(const SwArgs &g, int64_t s, int64_t t0, int64_t lo, int64_t hi, double (&pre)[SW_PRE],
+                                         double &bprev) {
 #pragma unroll
     for (int k = 0; k < SW_PRE; k++) {
         const SwSrc src = sw_src<BENCH>(g, s, k * (int)blockDim.x + (int)threadIdx.x);
         const int64_t t = t0 + src.c;
         pre[k] = 0.0; // an element beyond the tile or the series is stored at the most, never walked
-        if (src.kind < 0 || t >= g.len) continue;
+        if (src.kind < 0 || t >= hi) continue;
         pre[k] = src.p[t];
-        if (BENCH && src.kind == 1) bprev = src.p[t > 0 ? t - 1 : 0];
+        if (BENCH && src.kind == 1) bprev = src.p[t > lo ? t - 1 : lo];
     }
 }
 // registers -> LDS (element e at tile[e]: the pitch of a row is R)
@@ -224,18 +227,18 @@ __device__ __forceinline__ void sw_walk(const double *tile, int n, const SwRule 
     }
 }
 
-// one walk over all rows; `again`: the other walk follows, so the tile after the last one is tile 0
+// one walk over the rows [lo, hi); `again`: the other walk follows, so the tile after the last one is the first one
 template <int RULE, int PASS, bool BENCH>
-__device__ __forceinline__ void sw_pass(const SwArgs &g, int64_t s, double *lds, int &cur, bool wave_live, bool again, const SwRule &q,
-                                        SwLane &st, SwAcc &acc) {
+__device__ __forceinline__ void sw_pass(const SwArgs &g, int64_t s, int64_t lo, int64_t hi, double *lds, int &cur, bool wave_live, bool again,
+                                        const SwRule &q, SwLane &st, SwAcc &acc) {
     const int R = g.R, tile_elems = (g.n_lines + (BENCH ? 2 : 1)) * R;
     const int ipx = g.n_lines * R, ibr = (g.n_lines + 1) * R;
-    for (int64_t t0 = 0; t0 < g.len; t0 += R) {
-        const bool last = t0 + R >= g.len, more = !last || again;
-        const int64_t tn = last ? 0 : t0 + R;
+    for (int64_t t0 = lo; t0 < hi; t0 += R) {
+        const bool last = t0 + R >= hi, more = !last || again;
+        const int64_t tn = last ? lo : t0 + R;
         double pre[SW_PRE], bprev = 0.0;
-        if (more) sw_fetch<BENCH>(g, s, tn, pre, bprev); // in flight during the walk
-        const int n = (int)(last ? g.len - t0 : R);
+        if (more) sw_fetch<BENCH>(g, s, tn, lo, hi, pre, bprev); // in flight during the walk
+        const int n = (int)(last ? hi - t0 : R);
         if (wave_live) sw_walk<RULE, PASS, BENCH>(lds + cur * tile_elems, n, q, ipx, ibr, g.prm, st, acc);
         if (more) sw_store<BENCH>(g, tn, pre, bprev, lds + (cur ^ 1) * tile_elems);
         __syncthreads(); // the next tile is complete, and nobody reads this one any more
@@ -243,7 +246,9 @@ __device__ __forceinline__ void sw_pass(const SwArgs &g, int64_t s, double *lds,
     }
 }
 
-// RULE: the one rule of the whole table, or SW_GENERIC
+// RULE: the one rule of the whole table, or SW_GENERIC.  sweep_windows_kernel below holds a second copy of this body with a window's
+// lo / hi for 0 / len: a change to the lane set-up, the passes or the summary arithmetic here must be made there as well (the
+// bit-for-bit tests of tests/test_sweep_windows_gpu.py compare the two).
 template <int RULE, bool BENCH>
 __global__ __launch_bounds__(SW_BLOCK) void sweep_kernel(SwArgs g) {
     extern __shared__ double sw_lds[];
@@ -270,18 +275,18 @@ __global__ __launch_bounds__(SW_BLOCK) void sweep_kernel(SwArgs g) {
     int cur = 0;
     {
         double pre[SW_PRE], bprev = 0.0;
-        sw_fetch<BENCH>(g, s, 0, pre, bprev);
+        sw_fetch<BENCH>(g, s, 0, 0, g.len, pre, bprev);
         sw_store<BENCH>(g, 0, pre, bprev, sw_lds);
         __syncthreads();
     }
-    sw_pass<RULE, 1, BENCH>(g, s, sw_lds, cur, wave_live, true, q, st, acc);
+    sw_pass<RULE, 1, BENCH>(g, s, 0, g.len, sw_lds, cur, wave_live, true, q, st, acc);
     const double T = (double)g.len;
     const double last_eq = st.prev_eq;
     const int32_t trades = st.trades, wins = st.wins;
     acc.mean = acc.ret_sum / T;  // metrics.rs:60
     acc.bmean = acc.bsum / T;
     st.reset(capital);
-    sw_pass<RULE, 2, BENCH>(g, s, sw_lds, cur, wave_live, false, q, st, acc);
+    sw_pass<RULE, 2, BENCH>(g, s, 0, g.len, sw_lds, cur, wave_live, false, q, st, acc);
     if (!live) return;
     const double DAYS = 252.0, RF = 0.03;
     const double total_return = (last_eq - capital) / capital;                                                  // :52
@@ -304,6 +309,134 @@ __global__ __launch_bounds__(SW_BLOCK) void sweep_kernel(SwArgs g) {
     sm[0] = ann; sm[1] = acc.max_dd; sm[2] = alpha; sm[3] = beta; sm[4] = sharpe;
     sm[5] = fmax(total_return, 0.0); sm[6] = win_rate; sm[7] = (double)trades;                                  // :142-149
 }
+
+// D-26: the sweep with one more grid axis, the window.  Block ((w N + s) pblocks + pb) -- window-major, the order of the loop of sweeps
+// it replaces: with the windows of one symbol as neighbours, ((s W + w) pblocks + pb), the same launch took 57.7 ms against 37.3 ms
+// (config 3, 32 windows, one run each) -- runs rows
+// [t0_w, t1_w) exactly as sweep_kernel runs a series of that length: the
+// lane state and the rule's row t - 1 start afresh at t0 (row t0 never signals, row t0 - 1 is never read), T = t1 - t0, the benchmark
+// return of row t0 is taken against row t0, alpha spans bm[t0] .. bm[t1 - 1].  summary is [W][N][P][8]; an empty window's cells are 0
+// (metrics.rs:17-19).  The body below is sweep_kernel's with lo / hi for 0 / len, kept as a second copy: sweep_kernel written through
+// a shared body with lo = 0 is allocated ~25 more VGPRs by the compiler, and its figures are pinned (tests/test_sweep_rules_ref.py).
+struct SwWinArgs {
+    SwArgs g;
+    const pq_sweep_window *windows; // device, [n_windows]; checked against len on the host
+    int64_t n_series;
+};
+template <int RULE, bool BENCH>
+__global__ __launch_bounds__(SW_BLOCK) void sweep_windows_kernel(SwWinArgs a) {
+    extern __shared__ double sw_lds[];
+    const SwArgs &g = a.g;
+    const unsigned sw = blockIdx.x / (unsigned)g.pblocks;
+    const int64_t p0 = (int64_t)(blockIdx.x % (unsigned)g.pblocks) * blockDim.x;
+    const int64_t w = (int64_t)(sw / (unsigned)a.n_series), s = (int64_t)(sw % (unsigned)a.n_series);
+    const pq_sweep_window win = a.windows[w]; // uniform over the workgroup
+    double *sm_rows = g.summary + (w * a.n_series + s) * g.n_params * PQ_SUMMARY_COLS;
+    const int tid = (int)threadIdx.x;
+    const int64_t p = p0 + tid;
+    const bool live = p < g.n_params;
+    if (win.t0 >= win.t1) {
+        if (live)
+#pragma unroll
+            for (int k = 0; k < PQ_SUMMARY_COLS; k++) sm_rows[p * PQ_SUMMARY_COLS + k] = 0.0;
+        return;
+    }
+    const int64_t lo = win.t0, hi = win.t1;
+    const bool wave_live = p0 + (tid & ~63) < g.n_params; // a wavefront without a parameter set only helps with the staging
+    SwRule q{0, 0, 0, RULE == SW_GENERIC ? PQ_SWEEP_RULE_CROSS : RULE, 0.0, 0.0};
+    if (live) { // the rule and the columns it uses were checked against n_lines on the host before the launch
+        const pq_sweep_rule in = g.params[p];
+        if (RULE == SW_GENERIC) q.rule = in.rule;
+        q.ia = in.a * g.R;
+        q.ib = (RULE == SW_GENERIC ? sw_uses_b(in.rule) : sw_uses_b(RULE)) ? in.b * g.R : q.ia;
+        q.ic = (RULE == SW_GENERIC ? sw_uses_c(in.rule) : sw_uses_c(RULE)) ? (in.c < 0 ? g.n_lines : in.c) * g.R : q.ia; // -1: the price row
+        q.k0 = in.k0; q.k1 = in.k1;
+    }
+    const double capital = g.prm.initial_capital;
+    SwLane st;
+    SwAcc acc{};
+    st.reset(capital);
+    acc.max_eq = capital;
+    int cur = 0;
+    {
+        double pre[SW_PRE], bprev = 0.0;
+        sw_fetch<BENCH>(g, s, lo, lo, hi, pre, bprev);
+        sw_store<BENCH>(g, lo, pre, bprev, sw_lds);
+        __syncthreads();
+    }
+    sw_pass<RULE, 1, BENCH>(g, s, lo, hi, sw_lds, cur, wave_live, true, q, st, acc);
+    const double T = (double)(hi - lo);
+    const double last_eq = st.prev_eq;
+    const int32_t trades = st.trades, wins = st.wins;
+    acc.mean = acc.ret_sum / T;  // metrics.rs:60
+    acc.bmean = acc.bsum / T;
+    st.reset(capital);
+    sw_pass<RULE, 2, BENCH>(g, s, lo, hi, sw_lds, cur, wave_live, false, q, st, acc);
+    if (!live) return;
+    const double DAYS = 252.0, RF = 0.03;
+    const double total_return = (last_eq - capital) / capital;                                                  // :52
+    const double ann = (total_return > -1.0) ? pow(1.0 + total_return, DAYS / T) - 1.0 : -1.0;                  // :54-58
+    const double dof = fmax(T - 1.0, 1.0);                                                                      // :61
+    const double vol = sqrt(acc.vs / dof) * sqrt(DAYS);                                                         // :69
+    const double sharpe = (vol > 0.0) ? (ann - RF) / vol : 0.0;                                                 // :71-75
+    const double win_rate = (trades > 0) ? (double)wins / (double)trades : 0.0;
+    double alpha = 0.0, beta = 0.0;
+    if (BENCH) {                                                                                                // :86-140
+        const double *bm = g.bench + s * g.bench_stride;
+        const double bvar = acc.bv / dof, cov = acc.cv / dof;
+        if (bvar > 0.0) beta = cov / bvar;
+        const double b0 = bm[lo], b1 = bm[hi - 1];
+        const double btr = (b0 > 0.0) ? (b1 - b0) / b0 : 0.0;
+        const double bann = (btr > -1.0) ? pow(1.0 + btr, DAYS / T) - 1.0 : -1.0;
+        alpha = ann - (RF + beta * (bann - RF));
+    }
+    double *sm = sm_rows + p * PQ_SUMMARY_COLS; // a wavefront's 64 rows are one contiguous 4 KB piece
+    sm[0] = ann; sm[1] = acc.max_dd; sm[2] = alpha; sm[3] = beta; sm[4] = sharpe;
+    sm[5] = fmax(total_return, 0.0); sm[6] = win_rate; sm[7] = (double)trades;                                  // :142-149
+}
+
+// D-26, selection: one wavefront per (fold f, symbol s).  Lanes stride over the parameter sets of summary[train[f]][s] and keep their
+// best metric value with a strict comparison (a NaN ranks as the worst value), the wave reduces on (value, index) -- the lower index
+// wins a tie, so an all-NaN column gives 0, like SweepResult.best() -- and the chosen set's eight values are copied from the train and
+// the test window.
+struct SwSelArgs {
+    const double *summary; // [W][N][P][8]
+    const int32_t *train, *test; // device, [F]
+    int32_t *chosen;
+    double *in_sample, *out_sample;
+    int64_t n_series, n_params;
+    int32_t col, maximize;
+};
+__global__ __launch_bounds__(64) void sweep_select_kernel(SwSelArgs a) {
+    const int lane = (int)threadIdx.x;
+    const int64_t f = (int64_t)(blockIdx.x / (unsigned)a.n_series), s = (int64_t)(blockIdx.x % (unsigned)a.n_series);
+    const double *tr = a.summary + ((int64_t)a.train[f] * a.n_series + s) * a.n_params * PQ_SUMMARY_COLS;
+    const double *te = a.summary + ((int64_t)a.test[f] * a.n_series + s) * a.n_params * PQ_SUMMARY_COLS;
+    const bool mx = a.maximize != 0;
+    const double worst = mx ? -__builtin_huge_val() : __builtin_huge_val();
+    const int NONE = 0x7fffffff; // a lane without a parameter set loses every tie
+    auto key = [&](int64_t p) { const double v = tr[p * PQ_SUMMARY_COLS + a.col]; return v != v ? worst : v; };
+    double bv = worst;
+    int bi = NONE;
+    if (lane < a.n_params) { // the lane's first set, then only a strictly better one
+        bv = key(lane);
+        bi = lane;
+        for (int64_t p = lane + 64; p < a.n_params; p += 64) {
+            const double v = key(p);
+            if (mx ? v > bv : v < bv) { bv = v; bi = (int)p; }
+        }
+    }
+#define SW_BEST(CTRL, RM) { const double tv = btw_dpp<CTRL, RM>(worst, bv); const int ti = btw_dpp<CTRL, RM>(NONE, bi);   \
+                            if ((mx ? tv > bv : tv < bv) || (tv == bv && ti < bi)) { bv = tv; bi = ti; } }
+    BTW_SCAN_STEPS(SW_BEST) // an inclusive scan: lane 63 holds the best of the wave
+#undef SW_BEST
+    const int64_t best = __builtin_amdgcn_readlane(bi, 63);
+    const int64_t cell = f * a.n_series + s;
+    if (lane == 0) a.chosen[cell] = (int32_t)best;
+    if (lane < PQ_SUMMARY_COLS) a.in_sample[cell * PQ_SUMMARY_COLS + lane] = tr[best * PQ_SUMMARY_COLS + lane];
+    else if (lane < 2 * PQ_SUMMARY_COLS) a.out_sample[cell * PQ_SUMMARY_COLS + lane - PQ_SUMMARY_COLS] = te[best * PQ_SUMMARY_COLS + lane - PQ_SUMMARY_COLS];
+}
+
 using SwKernel = void (*)(SwArgs);
 template <bool BENCH>
 SwKernel sw_kernel_for(int rule) {
@@ -319,10 +452,27 @@ SwKernel sw_kernel_for(int rule) {
     }
 }
 
-// both entry points: `who` names the caller in the messages, max_rule is the last rule it accepts
+using SwWinKernel = void (*)(SwWinArgs);
+template <bool BENCH>
+SwWinKernel sw_win_kernel_for(int rule) {
+    switch (rule) {
+    case PQ_SWEEP_RULE_CROSS: return sweep_windows_kernel<PQ_SWEEP_RULE_CROSS, BENCH>;
+    case PQ_SWEEP_RULE_BAND: return sweep_windows_kernel<PQ_SWEEP_RULE_BAND, BENCH>;
+    case PQ_SWEEP_RULE_CHANNEL: return sweep_windows_kernel<PQ_SWEEP_RULE_CHANNEL, BENCH>;
+    case PQ_SWEEP_RULE_BREAKOUT: return sweep_windows_kernel<PQ_SWEEP_RULE_BREAKOUT, BENCH>;
+    case PQ_SWEEP_RULE_SCALED_CHANNEL: return sweep_windows_kernel<PQ_SWEEP_RULE_SCALED_CHANNEL, BENCH>;
+    case PQ_SWEEP_RULE_CROSS_ZONES: return sweep_windows_kernel<PQ_SWEEP_RULE_CROSS_ZONES, BENCH>;
+    case PQ_SWEEP_RULE_CROSS_STRENGTH: return sweep_windows_kernel<PQ_SWEEP_RULE_CROSS_STRENGTH, BENCH>;
+    default: return sweep_windows_kernel<SW_GENERIC, BENCH>;
+    }
+}
+
+// every entry point: `who` names the caller in the messages, max_rule is the last rule it accepts.  windowed: `windows` is a HOST table
+// of n_windows row ranges and summary is [n_windows][n_series][n_rules][8]; otherwise the one range is the whole series
 pq_status sw_run(const char *who, int max_rule, pq_ctx *ctx, const pq_batch *b, const double *price, const double *const *lines,
                  int32_t n_lines, const pq_sweep_rule *rules, int64_t n_rules, const double *benchmark, int64_t bench_series_stride,
-                 const pq_bt_params *bt, double *summary) {
+                 const pq_bt_params *bt, double *summary, bool windowed = false, const pq_sweep_window *windows = nullptr,
+                 int64_t n_windows = 1) {
     PQ_TRY(pq_check(ctx, b));
     if (ctx->rec) { pq_set_error("%s cannot be recorded into a suite", who); return PQ_ERR_UNSUPPORTED; }
     if (b->offsets) { pq_set_error("%s: ragged batches are not supported", who); return PQ_ERR_UNSUPPORTED; }
@@ -330,6 +480,7 @@ pq_status sw_run(const char *who, int max_rule, pq_ctx *ctx, const pq_batch *b, 
     const int R = sw_row_tile(n_lines);
     if (R == 0) { pq_set_error("%s: n_lines must be in [1, %d], not %d", who, PQ_SWEEP_MAX_LINES, (int)n_lines); return PQ_ERR_ARG; }
     if (!bt) { pq_set_error("%s: null parameters", who); return PQ_ERR_ARG; }
+    if (n_windows < 0) { pq_set_error("%s: negative n_windows", who); return PQ_ERR_ARG; }
     if (n_rules == 0 || b->n_series == 0) return PQ_OK;
     if (!(rules && summary && (b->len == 0 || (price && lines)))) { pq_set_error("%s: null pointer", who); return PQ_ERR_ARG; }
     for (int j = 0; j < n_lines && b->len > 0; j++)
@@ -338,6 +489,20 @@ pq_status sw_run(const char *who, int max_rule, pq_ctx *ctx, const pq_batch *b, 
     const int waves = sw_waves(n_lines, R, n_rules);
     const int64_t pblocks = (n_rules + 64 * waves - 1) / (64 * waves);
     if (!(b->len <= 0x7fffffffLL && n_rules <= 0x7fffffffLL && pblocks * b->n_series <= 0x7fffffffLL)) { pq_set_error("%s: batch or grid too large", who); return PQ_ERR_ARG; }
+    if (windowed) { // the size of the grid first: the table is read only once it is known to be of a sane length
+        if (n_windows > 0x7fffffffLL / (pblocks * b->n_series)) {
+            pq_set_error("%s: %lld windows make a grid of more than 2^31 - 1 blocks", who, (long long)n_windows);
+            return PQ_ERR_ARG;
+        }
+        if (n_windows > 0 && !windows) { pq_set_error("%s: null window table", who); return PQ_ERR_ARG; }
+        for (int64_t w = 0; w < n_windows; w++)
+            if (windows[w].t0 < 0 || windows[w].t1 > b->len || windows[w].t0 > windows[w].t1) {
+                pq_set_error("%s: window %lld: rows [%lld, %lld) are not a range inside [0, %lld)", who, (long long)w, (long long)windows[w].t0,
+                             (long long)windows[w].t1, (long long)b->len);
+                return PQ_ERR_ARG;
+            }
+        if (n_windows == 0) return PQ_OK;
+    }
     // the table is checked on the host before anything is launched: the kernel indexes LDS with a, b and c
     std::vector<pq_sweep_rule> host((size_t)n_rules);
     PQ_HIP_TRY(hipMemcpyAsync(host.data(), rules, sizeof(pq_sweep_rule) * (size_t)n_rules, hipMemcpyDeviceToHost, ctx->stream));
@@ -356,19 +521,29 @@ pq_status sw_run(const char *who, int max_rule, pq_ctx *ctx, const pq_batch *b, 
         }
         if (q.rule != one_rule) one_rule = SW_GENERIC;
     }
-    if (b->len == 0) { // calculate_summary on no rows: all zeros (metrics.rs:17-19)
-        PQ_HIP_TRY(hipMemsetAsync(summary, 0, sizeof(double) * PQ_SUMMARY_COLS * (size_t)b->n_series * (size_t)n_rules, ctx->stream));
+    if (b->len == 0) { // calculate_summary on no rows: all zeros (metrics.rs:17-19); n_windows is 1 where the call is not windowed
+        PQ_HIP_TRY(hipMemsetAsync(summary, 0, sizeof(double) * PQ_SUMMARY_COLS * (size_t)n_windows * (size_t)b->n_series * (size_t)n_rules, ctx->stream));
         return PQ_OK;
     }
-    PQ_TRY(pq_ws_reserve(ctx, sizeof(double *) * (size_t)n_lines));
-    PQ_HIP_TRY(hipMemcpyAsync(ctx->ws, lines, sizeof(double *) * (size_t)n_lines, hipMemcpyHostToDevice, ctx->stream));
-    PQ_HIP_TRY(hipStreamSynchronize(ctx->stream)); // the caller's table may go away after the call
+    const size_t line_bytes = sizeof(double *) * (size_t)n_lines; // the window table lies behind the line pointers
+    PQ_TRY(pq_ws_reserve(ctx, line_bytes + (windowed ? sizeof(pq_sweep_window) * (size_t)n_windows : 0)));
+    PQ_HIP_TRY(hipMemcpyAsync(ctx->ws, lines, line_bytes, hipMemcpyHostToDevice, ctx->stream));
+    pq_sweep_window *dwin = reinterpret_cast<pq_sweep_window *>(static_cast<unsigned char *>(ctx->ws) + line_bytes);
+    if (windowed) PQ_HIP_TRY(hipMemcpyAsync(dwin, windows, sizeof(pq_sweep_window) * (size_t)n_windows, hipMemcpyHostToDevice, ctx->stream));
+    PQ_HIP_TRY(hipStreamSynchronize(ctx->stream)); // the caller's tables may go away after the call
     SwArgs g{};
     g.price = price; g.lines = (const double *const *)ctx->ws; g.params = rules; g.bench = benchmark; g.summary = summary; g.prm = *bt;
     g.len = b->len; g.stride = b->stride; g.bench_stride = bench_series_stride; g.n_params = n_rules;
     g.n_lines = n_lines; g.R = R; g.pblocks = (int32_t)pblocks;
     g.magic = ((1u << 20) + (uint32_t)R - 1u) / (uint32_t)R;
     const size_t lds = sizeof(double) * 2 * (size_t)(n_lines + 2) * (size_t)R; // <= 2 * SW_TILE doubles = 64 KB
+    if (windowed) {
+        SwWinArgs a{g, dwin, b->n_series};
+        const SwWinKernel kernel = benchmark ? sw_win_kernel_for<true>(one_rule) : sw_win_kernel_for<false>(one_rule);
+        hipLaunchKernelGGL(kernel, dim3((unsigned)(pblocks * b->n_series * n_windows)), dim3(64 * waves), lds, ctx->stream, a);
+        PQ_HIP_TRY(hipGetLastError());
+        return PQ_OK;
+    }
     const dim3 grid((unsigned)(pblocks * b->n_series));
     const SwKernel kernel = benchmark ? sw_kernel_for<true>(one_rule) : sw_kernel_for<false>(one_rule);
     hipLaunchKernelGGL(kernel, grid, dim3(64 * waves), lds, ctx->stream, g);
@@ -394,6 +569,42 @@ pq_status pq_backtest_sweep_rules(pq_ctx *ctx, const pq_batch *b, const double *
                                   const pq_bt_params *bt, double *summary) {
     return sw_run("pq_backtest_sweep_rules", PQ_SWEEP_RULE_CROSS_STRENGTH, ctx, b, price, lines, n_lines, rules, n_rules, benchmark,
                   bench_series_stride, bt, summary);
+}
+
+pq_status pq_backtest_sweep_windows(pq_ctx *ctx, const pq_batch *b, const double *price, const double *const *lines, int32_t n_lines,
+                                    const pq_sweep_rule *rules, int64_t n_rules, const pq_sweep_window *windows, int64_t n_windows,
+                                    const double *benchmark, int64_t bench_series_stride, const pq_bt_params *bt, double *summary) {
+    return sw_run("pq_backtest_sweep_windows", PQ_SWEEP_RULE_CROSS_STRENGTH, ctx, b, price, lines, n_lines, rules, n_rules, benchmark,
+                  bench_series_stride, bt, summary, true, windows, n_windows);
+}
+
+pq_status pq_sweep_select(pq_ctx *ctx, const double *summary, int64_t n_windows, int64_t n_series, int64_t n_params, const int32_t *train,
+                          const int32_t *test, int64_t n_folds, int32_t metric_col, int32_t maximize, int32_t *chosen, double *in_sample,
+                          double *out_sample) {
+    const char *who = "pq_sweep_select";
+    if (!ctx) { pq_set_error("%s: null context", who); return PQ_ERR_ARG; }
+    if (ctx->rec) { pq_set_error("%s cannot be recorded into a suite", who); return PQ_ERR_UNSUPPORTED; }
+    if (n_windows < 0 || n_series < 0 || n_params < 0 || n_folds < 0) { pq_set_error("%s: negative size", who); return PQ_ERR_ARG; }
+    if (metric_col < 0 || metric_col >= PQ_SUMMARY_COLS) { pq_set_error("%s: metric_col %d outside [0, %d)", who, (int)metric_col, PQ_SUMMARY_COLS); return PQ_ERR_ARG; }
+    if (n_folds > 0 && !(train && test)) { pq_set_error("%s: null fold table", who); return PQ_ERR_ARG; }
+    for (int64_t f = 0; f < n_folds; f++)
+        if (train[f] < 0 || train[f] >= n_windows || test[f] < 0 || test[f] >= n_windows) {
+            pq_set_error("%s: fold %lld: train window %d or test window %d outside [0, %lld)", who, (long long)f, (int)train[f], (int)test[f], (long long)n_windows);
+            return PQ_ERR_ARG;
+        }
+    if (n_folds == 0 || n_series == 0) return PQ_OK;
+    if (n_params < 1) { pq_set_error("%s: no parameter set to choose from", who); return PQ_ERR_ARG; }
+    if (!(summary && chosen && in_sample && out_sample)) { pq_set_error("%s: null pointer", who); return PQ_ERR_ARG; }
+    if (n_params > 0x7fffffffLL || n_series > 0x7fffffffLL || n_folds > 0x7fffffffLL / n_series) { pq_set_error("%s: grid too large", who); return PQ_ERR_ARG; }
+    PQ_TRY(pq_ws_reserve(ctx, 2 * sizeof(int32_t) * (size_t)n_folds));
+    int32_t *dfold = static_cast<int32_t *>(ctx->ws);
+    PQ_HIP_TRY(hipMemcpyAsync(dfold, train, sizeof(int32_t) * (size_t)n_folds, hipMemcpyHostToDevice, ctx->stream));
+    PQ_HIP_TRY(hipMemcpyAsync(dfold + n_folds, test, sizeof(int32_t) * (size_t)n_folds, hipMemcpyHostToDevice, ctx->stream));
+    PQ_HIP_TRY(hipStreamSynchronize(ctx->stream)); // the caller's tables may go away after the call
+    SwSelArgs a{summary, dfold, dfold + n_folds, chosen, in_sample, out_sample, n_series, n_params, metric_col, maximize};
+    hipLaunchKernelGGL(sweep_select_kernel, dim3((unsigned)(n_folds * n_series)), dim3(64), 0, ctx->stream, a);
+    PQ_HIP_TRY(hipGetLastError());
+    return PQ_OK;
 }
 
 } // extern "C"
