@@ -3,9 +3,15 @@ cross (pq_cross_signals), the oversold / overbought zones (pq_gate_signals) -- f
   eager   four C-ABI calls, one launch (or more) each
   suite   the same four calls recorded once (pq_suite_begin / end) and replayed: the signal columns stay on the device between the
           indicator job, the rule kernels and the wave-per-symbol backtest, and the launches are a recorded plan
-Prints one JSON object (profiles/r03_bench_strategy.json)."""
+Eager against recorded, column by column: the signal columns, position, cash, equity and summary columns 1, 5, 6, 7 (max_drawdown,
+max_profit, win_rate, total_trades) are compared BIT FOR BIT ("exact_columns_identical"); summary columns 0, 2, 3, 4 (annualized
+return, alpha, beta, sharpe: ordered sums) get their largest relative difference -- a recorded backtest runs the one-wave kernel, an
+eager one the four-wave kernel, and the two add the daily returns in different orders (tests/test_strategy_rules_gpu.py).  The last
+field repeats the comparison with the eager backtest forced to one wave (PQ_BT_WAVES=1): the same kernel on both sides.
+Prints one JSON object (profiles/r07_bench_strategy.json)."""
 import ctypes as C
 import json
+import os
 import sys
 
 sys.path.insert(0, ".")
@@ -50,19 +56,50 @@ def t_event(fn, reps=20):
     return e0.elapsed_time(e1) / reps
 
 
+SUMMARY_KEYS = ("annualized_return", "max_drawdown", "alpha", "beta", "sharpe_ratio", "max_profit", "win_rate", "total_trades")
+EXACT, SUMS = (1, 5, 6, 7), (0, 2, 3, 4)
+NAMED = (("slowk", k_), ("slowd", d_), ("cross_buy", b0), ("cross_sell", s0), ("buy", b1), ("sell", s1), ("position", pos), ("cash", cash), ("equity", eq))
+
+
+def snapshot():
+    torch.cuda.synchronize()
+    return {nm: t[:, :T].clone() for nm, t in NAMED}, summ.clone()
+
+
+def same_bits(a, r):
+    return torch.equal(a.view(torch.int64), r.view(torch.int64)) if a.dtype == torch.float64 else torch.equal(a, r)
+
+
+def compare(ref, got):
+    """-> (names of the columns that differ in some bit, exact columns identical, largest relative difference of the sum columns)"""
+    differing = [nm for nm in ref[0] if not same_bits(got[0][nm], ref[0][nm])]
+    differing += [f"summary.{SUMMARY_KEYS[k]}" for k in range(8) if not same_bits(got[1][:, k].contiguous(), ref[1][:, k].contiguous())]
+    exact = not any(nm in differing for nm in list(ref[0]) + [f"summary.{SUMMARY_KEYS[k]}" for k in EXACT])
+    a, r = got[1][:, list(SUMS)], ref[1][:, list(SUMS)]
+    ok = torch.isfinite(a) & torch.isfinite(r) & (r != 0)
+    rel = float(((a - r).abs() / r.abs())[ok].max()) if bool(ok.any()) else 0.0
+    return differing, exact, rel
+
+
 eager_ms = t_event(calls)
-torch.cuda.synchronize()
-ref = [t.clone() for t in (pos, cash, eq, summ, b1, s1)]
+ref = snapshot()
+os.environ["PQ_BT_WAVES"] = "1"          # the eager backtest as the one-wave kernel: what a recording runs
+calls()
+ref_one_wave = snapshot()
+del os.environ["PQ_BT_WAVES"]
 check(L.pq_suite_begin(h, C.byref(b)))
 calls()
 suite = C.c_void_p()
 check(L.pq_suite_end(h, C.byref(suite)))
-for t in (pos, cash, eq, summ):
-    t.fill_(-1.0)
+for _, t in NAMED:
+    t.fill_(-1.0 if t.dtype == torch.float64 else 7)
+summ.fill_(-1.0)
 suite_ms = t_event(lambda: check(L.pq_suite_run(h, suite)))
-torch.cuda.synchronize()
-same = all(torch.equal(a.view(torch.int64) if a.dtype == torch.float64 else a, r.view(torch.int64) if r.dtype == torch.float64 else r)
-           for a, r in zip((pos[:, :T], cash[:, :T], eq[:, :T], summ, b1[:, :T], s1[:, :T]), (ref[0][:, :T], ref[1][:, :T], ref[2][:, :T], ref[3], ref[4][:, :T], ref[5][:, :T])))
+got = snapshot()
 check(L.pq_suite_destroy(h, suite))
+differing, exact, rel = compare(ref, got)
+differing1, _, _ = compare(ref_one_wave, got)
 print(json.dumps({"workload": f"Strategy.stoch -> VectorizedBacktester, {N} x {T}", "eager_ms": eager_ms, "recorded_suite_ms": suite_ms,
-                  "identical_results": bool(same), "trades_total": float(summ[:, 7].sum())}, indent=1))
+                  "identical_results": not differing, "exact_columns_identical": exact, "differing_columns": differing,
+                  "summary_sum_columns_max_rel_diff": rel, "identical_to_one_wave_eager": not differing1,
+                  "differing_columns_one_wave_eager": differing1, "trades_total": float(summ[:, 7].sum())}, indent=1))
