@@ -430,6 +430,16 @@ static pq_status upload_col(pq_ctx *ctx, const Layout &L, const void *host, size
 // not alias: other bytes, other hash, a miss.  Shared by the host threads Polars calls from (a mutex; an entry is published after its
 // creator's stream has been drained, is never freed while a call uses it, least recently used entries go when PQ_PLUGIN_CACHE_MB --
 // default 2 048, 0 = no cache -- is exceeded).
+// Under concurrent callers (tests/test_concurrency_gpu.py):
+//  * "upload `close` once" holds for a WARM cache only.  There is no in-flight entry: threads that miss on the same column at the same
+//    time each upload it and each publish their copy (inputs_done pushes duplicates; a later caller hits the first of them, the others
+//    age out by LRU).  Observed with 16 first callers of one 40 000-row column: 16, 15 and 3 misses in three runs (EXPERIMENTS.md).  Results are
+//    right and the counters consistent (bytes = the sum over ALL entries); what is lost is the upload and the device memory of the copies.
+//  * every plugin context is created on the NULL stream (plugin_ctx: pq_ctx_create(0, nullptr, ...)), so one thread's pq_ctx_sync waits
+//    for every other thread's work as well: the calls overlap on the host (hash, gather, page faults), not on the device.  (VERDICT.md
+//    weakness 7 -- "every context but the first is on a created stream" -- describes an older state of this file.)
+//  * an evicted or cleared entry is freed through the context of the thread that evicts or clears, whichever thread uploaded it.  That
+//    is safe because in_use == 0 and the shared NULL stream is drained by pq_free first.
 struct CacheEntry {
     const void *addr; int64_t n, groups, glen, pitch; uint64_t hash;
     void *d; size_t bytes; int in_use; uint64_t tick;
