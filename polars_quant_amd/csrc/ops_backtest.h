@@ -1,8 +1,22 @@
 // ops_backtest.h -- per-symbol backtest scan + summary (device body shared by backtest.hip and the suite job grid)
 #pragma once
 #include "pq_cores.h"
+#include "bt_core.h"
 
 __device__ __forceinline__ double z0b(double x) { return pq_isnull(x) ? 0.0 : x; }
+
+// One row of the pool for a lane that walks every row (vectorized.rs:130-177): the row's equity.  A NULL is a NaN (:70-78), and a NaN or
+// non-positive price leaves the state untouched (:141-144).
+__device__ __forceinline__ double bt_pool_row(BtPool &pl, double px, bool buy, bool sell, const pq_bt_params &prm, int64_t &trades, int64_t &wins) {
+    if (pq_isnull(px)) px = __longlong_as_double(0x7FF8000000000000LL);
+    bool opened = false, won = false;
+    if (!(isnan(px) || px <= 0.0)) {
+        if (buy && pl.pos == 0.0) opened = bt_buy(pl, px, prm);
+        else if (sell && pl.pos > 0.0) won = bt_sell(pl, px, prm);
+    }
+    trades += opened; wins += won;
+    return pl.equity(px);
+}
 
 struct BtArgs {
     const double *price;
@@ -26,11 +40,10 @@ __device__ __forceinline__ void backtest_body(const BtArgs &a, const Dims &d, in
     double prev_m = pq_null(), prev_s = pq_null();
     if (MACD_SIGNALS) { ef.init(a.fast, T); es.init(a.slow, T); eg.init(a.sig, T); }
 
-    double pos = 0.0, avail = prm.initial_capital, peak = prm.initial_capital, entry_cost = 0.0;
+    BtPool pl;
+    BtRun run;
+    pl.reset(prm.initial_capital); run.reset(prm.initial_capital);
     int64_t trades = 0, wins = 0;
-    // summary pass 1 state (metrics.rs:21-49)
-    double max_dd = 0.0, max_eq = prm.initial_capital, prev_eq = prm.initial_capital, ret_sum = 0.0;
-    double last_eq = prm.initial_capital;
 
     for (int64_t i = 0; i < T; i++) {
         double px = price[i];
@@ -48,103 +61,14 @@ __device__ __forceinline__ void backtest_body(const BtArgs &a, const Dims &d, in
             buy = a.buy[base + i] != 0;
             sell = a.sell[base + i] != 0;
         }
-        double eq;
-        if (pq_isnull(px)) px = __longlong_as_double(0x7FF8000000000000LL); // null -> NaN (vectorized.rs:70-78)
-        if (isnan(px) || px <= 0.0) { // vectorized.rs:141-144: state untouched
-            eq = avail + pos * px;
-        } else {
-            if (buy && pos == 0.0) { // :146-161
-                double exec = px + prm.buy_slippage;
-                double cur_eq = avail + pos * px;
-                double deploy = cur_eq * prm.position_size;
-                double qty = floor(deploy / exec);
-                if (qty > 0.0) {
-                    double cost = qty * exec;
-                    double fee = fmax(cost * prm.buy_commission_rate, prm.min_commission);
-                    pos += qty;
-                    avail -= cost + fee;
-                    entry_cost = pos * px;
-                    trades += 1;
-                }
-            } else if (sell && pos > 0.0) { // :162-175
-                double exec = px - prm.sell_slippage;
-                double revenue = pos * exec;
-                double fee = fmax(revenue * prm.sell_commission_rate, prm.min_commission);
-                double net = revenue - fee;
-                if (net > entry_cost) wins += 1;
-                avail += net;
-                pos = 0.0;
-            }
-            eq = avail + pos * px;
-            if (eq > peak) peak = eq;
-        }
-        if (a.position) a.position[base + i] = pos;
-        if (a.cash) a.cash[base + i] = avail;
+        const double eq = bt_pool_row(pl, px, buy, sell, prm, trades, wins);
+        if (a.position) a.position[base + i] = pl.pos;
+        if (a.cash) a.cash[base + i] = pl.avail;
         a.equity[base + i] = eq;
-        // metrics.rs:26-49
-        if (eq > max_eq) max_eq = eq;
-        double dd = (max_eq > 0.0) ? (max_eq - eq) / max_eq : 0.0;
-        if (dd > max_dd) max_dd = dd;
-        double r = (prev_eq > 0.0) ? (eq - prev_eq) / prev_eq : 0.0;
-        ret_sum += r;
-        prev_eq = eq;
-        last_eq = eq;
+        run.add(eq);
     }
     if (SIGNALS_ONLY || a.summary == nullptr) return;
-    double *sm = a.summary + s * PQ_SUMMARY_COLS;
-    if (T == 0) { for (int k = 0; k < 8; k++) sm[k] = 0.0; return; }
-    const double DAYS = 252.0, RF = 0.03;
-    double total_return = (last_eq - prm.initial_capital) / prm.initial_capital;
-    double ann = (total_return > -1.0) ? pow(1.0 + total_return, DAYS / (double)T) - 1.0 : -1.0;
-    double mean = ret_sum / (double)T;
-    double dof = fmax((double)T - 1.0, 1.0);
-    // pass 2: variance of daily returns, recomputed from the lane's own equity rows
-    const double *eqr = a.equity + base;
-    double vs = 0.0, pe = prm.initial_capital;
-    for (int64_t i = 0; i < T; i++) {
-        double e = eqr[i];
-        double r = (pe > 0.0) ? (e - pe) / pe : 0.0;
-        double dlt = r - mean;
-        vs += dlt * dlt;
-        pe = e;
-    }
-    double var = vs / dof;
-    double vol = sqrt(var) * sqrt(DAYS);
-    double sharpe = (vol > 0.0) ? (ann - RF) / vol : 0.0;
-    double win_rate = (trades > 0) ? (double)wins / (double)trades : 0.0;
-    double alpha = 0.0, beta = 0.0;
-    if (a.bench) { // metrics.rs:86-140
-        const double *bm = a.bench + base;
-        double pb = bm[0], bs = 0.0;
-        for (int64_t i = 0; i < T; i++) { double bv = bm[i]; bs += (pb > 0.0) ? (bv - pb) / pb : 0.0; pb = bv; }
-        double bmean = bs / (double)T;
-        double bvar = 0.0, cov = 0.0;
-        pb = bm[0];
-        for (int64_t i = 0; i < T; i++) {
-            double bv = bm[i];
-            double br = (pb > 0.0) ? (bv - pb) / pb : 0.0;
-            double dlt = br - bmean;
-            bvar += dlt * dlt;
-            pb = bv;
-        }
-        bvar /= dof;
-        pb = bm[0]; pe = prm.initial_capital;
-        for (int64_t i = 0; i < T; i++) {
-            double bv = bm[i], e = eqr[i];
-            double br = (pb > 0.0) ? (bv - pb) / pb : 0.0;
-            double r = (pe > 0.0) ? (e - pe) / pe : 0.0;
-            cov += (r - mean) * (br - bmean);
-            pb = bv; pe = e;
-        }
-        cov /= dof;
-        if (bvar > 0.0) beta = cov / bvar;
-        double b0 = bm[0], b1 = bm[T - 1];
-        double btr = (b0 > 0.0) ? (b1 - b0) / b0 : 0.0;
-        double bann = (btr > -1.0) ? pow(1.0 + btr, DAYS / (double)T) - 1.0 : -1.0;
-        alpha = ann - (RF + beta * (bann - RF));
-    }
-    sm[0] = ann; sm[1] = max_dd; sm[2] = alpha; sm[3] = beta; sm[4] = sharpe;
-    sm[5] = fmax(total_return, 0.0); sm[6] = win_rate; sm[7] = (double)trades;
+    bt_summary_finish(a.equity + base, a.bench ? a.bench + base : nullptr, T, prm.initial_capital, run, trades, wins, a.summary + s * PQ_SUMMARY_COLS);
 }
 
 
@@ -159,14 +83,15 @@ struct BtMacdOp {
     int64_t fast, slow, sig;
     double *summary; // [n][8], nullable
     EmaCore ef, es, eg;
-    double prev_m, prev_s, pos, avail, peak, entry_cost, max_dd, max_eq, prev_eq, ret_sum, last_eq;
+    double prev_m, prev_s;
+    BtPool pl;
+    BtRun run;
     int64_t trades, wins;
     __device__ void init(const Row<1> &r) {
         ef.init(fast, r.len); es.init(slow, r.len); eg.init(sig, r.len);
         prev_m = pq_null(); prev_s = pq_null();
-        pos = 0.0; avail = prm.initial_capital; peak = prm.initial_capital; entry_cost = 0.0;
+        pl.reset(prm.initial_capital); run.reset(prm.initial_capital);
         trades = 0; wins = 0;
-        max_dd = 0.0; max_eq = prm.initial_capital; prev_eq = prm.initial_capital; ret_sum = 0.0; last_eq = prm.initial_capital;
     }
     __device__ void step(const Row<1> &, int64_t i, const double (&x)[1], double (&y)[3]) {
         double px = x[0];
@@ -196,139 +121,25 @@ struct BtMacdOp {
     }
     // vectorized.rs:130-194 for one row + the running parts of calculate_summary (metrics.rs:26-49)
     __device__ __forceinline__ void trade_row(double px, bool buy, bool sell, double (&y)[3]) {
-        double eq;
-        if (pq_isnull(px)) px = __longlong_as_double(0x7FF8000000000000LL); // null -> NaN (vectorized.rs:70-78)
-        if (isnan(px) || px <= 0.0) { // vectorized.rs:141-144: state untouched
-            eq = avail + pos * px;
-        } else {
-            if (buy && pos == 0.0) { // :146-161
-                double exec = px + prm.buy_slippage;
-                double cur_eq = avail + pos * px;
-                double deploy = cur_eq * prm.position_size;
-                double qty = floor(deploy / exec);
-                if (qty > 0.0) {
-                    double cost = qty * exec;
-                    double fee = fmax(cost * prm.buy_commission_rate, prm.min_commission);
-                    pos += qty;
-                    avail -= cost + fee;
-                    entry_cost = pos * px;
-                    trades += 1;
-                }
-            } else if (sell && pos > 0.0) { // :162-175
-                double exec = px - prm.sell_slippage;
-                double revenue = pos * exec;
-                double fee = fmax(revenue * prm.sell_commission_rate, prm.min_commission);
-                double net = revenue - fee;
-                if (net > entry_cost) wins += 1;
-                avail += net;
-                pos = 0.0;
-            }
-            eq = avail + pos * px;
-            if (eq > peak) peak = eq;
-        }
-        y[0] = pos; y[1] = avail; y[2] = eq;
-        if (eq > max_eq) max_eq = eq; // metrics.rs:26-49
-        double dd = (max_eq > 0.0) ? (max_eq - eq) / max_eq : 0.0;
-        if (dd > max_dd) max_dd = dd;
-        double r = (prev_eq > 0.0) ? (eq - prev_eq) / prev_eq : 0.0;
-        ret_sum += r;
-        prev_eq = eq;
-        last_eq = eq;
+        const double eq = bt_pool_row(pl, px, buy, sell, prm, trades, wins);
+        y[0] = pl.pos; y[1] = pl.avail; y[2] = eq;
+        run.add(eq);
     }
     __host__ __device__ void *finish_writes() const { return summary; } // what finish() writes besides the op's columns
     // called once per live lane after every row of the series has been stored
     __device__ void finish(double *const *outp, const Dims &d, int64_t s) {
         if (summary == nullptr) return;
-        const int64_t T = dims_len(d, s);
-        double *sm = summary + s * PQ_SUMMARY_COLS;
-        if (T == 0) { for (int k = 0; k < 8; k++) sm[k] = 0.0; return; }
-        const double DAYS = 252.0, RF = 0.03;
-        double total_return = (last_eq - prm.initial_capital) / prm.initial_capital;
-        double ann = (total_return > -1.0) ? pow(1.0 + total_return, DAYS / (double)T) - 1.0 : -1.0;
-        double mean = ret_sum / (double)T;
-        double dof = fmax((double)T - 1.0, 1.0);
-        const double *eqr = outp[2] + dims_base(d, s);
-        double vs = 0.0, pe = prm.initial_capital;
-        for (int64_t i = 0; i < T; i++) {
-            double e = eqr[i];
-            double r = (pe > 0.0) ? (e - pe) / pe : 0.0;
-            double dlt = r - mean;
-            vs += dlt * dlt;
-            pe = e;
-        }
-        double var = vs / dof;
-        double vol = sqrt(var) * sqrt(DAYS);
-        double sharpe = (vol > 0.0) ? (ann - RF) / vol : 0.0;
-        double win_rate = (trades > 0) ? (double)wins / (double)trades : 0.0;
-        sm[0] = ann; sm[1] = max_dd; sm[2] = 0.0; sm[3] = 0.0; sm[4] = sharpe;
-        sm[5] = fmax(total_return, 0.0); sm[6] = win_rate; sm[7] = (double)trades;
+        bt_summary_finish(outp[2] + dims_base(d, s), nullptr, dims_len(d, s), prm.initial_capital, run, trades, wins, summary + s * PQ_SUMMARY_COLS);
     }
 };
 
 // calculate_summary (metrics.rs:7-152) from a stored equity row; `bench`: this lane's benchmark rows or nullptr.
 __device__ __forceinline__ void bt_summary_from_row(const double *eqr, int64_t T, double initial_capital, int64_t trades,
                                                     int64_t wins, const double *bm, double *sm) {
-    if (T == 0) { for (int k = 0; k < 8; k++) sm[k] = 0.0; return; }
-    const double DAYS = 252.0, RF = 0.03;
-    double max_dd = 0.0, max_eq = initial_capital, pe = initial_capital, ret_sum = 0.0;
-    for (int64_t i = 0; i < T; i++) { // metrics.rs:26-49
-        double e = eqr[i];
-        if (e > max_eq) max_eq = e;
-        double dd = (max_eq > 0.0) ? (max_eq - e) / max_eq : 0.0;
-        if (dd > max_dd) max_dd = dd;
-        ret_sum += (pe > 0.0) ? (e - pe) / pe : 0.0;
-        pe = e;
-    }
-    const double last_eq = eqr[T - 1];
-    double total_return = (last_eq - initial_capital) / initial_capital;
-    double ann = (total_return > -1.0) ? pow(1.0 + total_return, DAYS / (double)T) - 1.0 : -1.0;
-    double mean = ret_sum / (double)T;
-    double dof = fmax((double)T - 1.0, 1.0);
-    double vs = 0.0;
-    pe = initial_capital;
-    for (int64_t i = 0; i < T; i++) {
-        double e = eqr[i];
-        double r = (pe > 0.0) ? (e - pe) / pe : 0.0;
-        double dlt = r - mean;
-        vs += dlt * dlt;
-        pe = e;
-    }
-    double var = vs / dof;
-    double vol = sqrt(var) * sqrt(DAYS);
-    double sharpe = (vol > 0.0) ? (ann - RF) / vol : 0.0;
-    double win_rate = (trades > 0) ? (double)wins / (double)trades : 0.0;
-    double alpha = 0.0, beta = 0.0;
-    if (bm) { // metrics.rs:86-140
-        double pb = bm[0], bs = 0.0;
-        for (int64_t i = 0; i < T; i++) { double bv = bm[i]; bs += (pb > 0.0) ? (bv - pb) / pb : 0.0; pb = bv; }
-        double bmean = bs / (double)T;
-        double bvar = 0.0, cov = 0.0;
-        pb = bm[0];
-        for (int64_t i = 0; i < T; i++) {
-            double bv = bm[i];
-            double br = (pb > 0.0) ? (bv - pb) / pb : 0.0;
-            double dlt = br - bmean;
-            bvar += dlt * dlt;
-            pb = bv;
-        }
-        bvar /= dof;
-        pb = bm[0]; pe = initial_capital;
-        for (int64_t i = 0; i < T; i++) {
-            double bv = bm[i], e = eqr[i];
-            double br = (pb > 0.0) ? (bv - pb) / pb : 0.0;
-            double r = (pe > 0.0) ? (e - pe) / pe : 0.0;
-            cov += (r - mean) * (br - bmean);
-            pb = bv; pe = e;
-        }
-        cov /= dof;
-        if (bvar > 0.0) beta = cov / bvar;
-        double b0 = bm[0], b1 = bm[T - 1];
-        double btr = (b0 > 0.0) ? (b1 - b0) / b0 : 0.0;
-        double bann = (btr > -1.0) ? pow(1.0 + btr, DAYS / (double)T) - 1.0 : -1.0;
-        alpha = ann - (RF + beta * (bann - RF));
-    }
-    sm[0] = ann; sm[1] = max_dd; sm[2] = alpha; sm[3] = beta; sm[4] = sharpe;
-    sm[5] = fmax(total_return, 0.0); sm[6] = win_rate; sm[7] = (double)trades;
+    BtRun run;
+    run.reset(initial_capital);
+    for (int64_t i = 0; i < T; i++) run.add(eqr[i]);
+    bt_summary_finish(eqr, bm, T, initial_capital, run, trades, wins, sm);
 }
 
 // SURVEY 8(f) rank 1 / decision D-10 (oracle/backtest.c pqo_backtest_leveraged): leveraged per-symbol pool.
@@ -343,69 +154,84 @@ struct LevArgs {
     double *summary;
     pq_lev_params prm;
 };
+struct LevState {
+    double cash, debt, shares, last_px, e_outlay, e_price;
+    int64_t e_day, trades, wins;
+    __device__ __forceinline__ void reset(double capital) {
+        cash = capital; debt = 0.0; shares = 0.0; last_px = 0.0; e_outlay = 0.0; e_price = 0.0;
+        e_day = 0; trades = 0; wins = 0;
+    }
+};
+// One row of the leveraged pool (D-10): interest, margin call or sale, else the lot search and the purchase; y = cash - debt, the stock
+// value, their sum.  A closed trade goes to the record arrays at rb + its index (where the caller asked for records).
+__device__ __forceinline__ void lev_row(LevState &st, const LevArgs &a, int64_t rb, double p, bool buy, bool sell, int64_t t, double (&y)[3]) {
+    const pq_lev_params &prm = a.prm;
+    if (pq_isnull(p)) p = __longlong_as_double(0x7FF8000000000000LL);
+    const bool valid = !(isnan(p) || p <= 0.0);
+    if (st.debt > 0.0) st.debt += st.debt * (prm.interest_rate / 252.0); // D-10 step 1: the daily rate is formed first
+    if (valid) {
+        st.last_px = p;
+        int do_sell = 0;
+        if (st.shares > 0.0) {
+            if (st.debt > 0.0 && st.cash + st.shares * p - st.debt < prm.margin_call_threshold * (st.shares * p)) do_sell = 2;
+            else if (sell) do_sell = 1;
+        }
+        if (do_sell) {
+            const double exec = p * (1.0 - prm.slippage);
+            const double rev = st.shares * exec;
+            const double fee = fmax(rev * prm.commission_rate, prm.min_commission);
+            const double net = rev - fee;
+            const double gain = net - st.e_outlay;
+            if (st.trades < a.max_trades && a.entry_day) {
+                const int64_t r = rb + st.trades;
+                a.entry_day[r] = (int32_t)st.e_day; a.exit_day[r] = (int32_t)t;
+                a.entry_price[r] = st.e_price; a.exit_price[r] = exec; a.quantity[r] = st.shares;
+                a.pnl[r] = gain; a.pnl_pct[r] = gain / st.e_outlay * 100.0; a.reason[r] = do_sell;
+            }
+            st.trades += 1;
+            if (gain > 0.0) st.wins += 1;
+            st.cash = st.cash + net - st.debt;
+            st.debt = 0.0;
+            st.shares = 0.0;
+        } else if (buy && st.shares == 0.0) {
+            const double exec = p * (1.0 + prm.slippage);
+            const double power = st.cash * prm.position_size * prm.leverage;
+            double lots = floor(power / (exec * 100.0));
+            double cost = 0.0, fee = 0.0;
+            while (lots > 0.0) {
+                cost = lots * 100.0 * exec;
+                fee = fmax(cost * prm.commission_rate, prm.min_commission);
+                if (cost + fee <= st.cash * prm.leverage) break;
+                lots -= 1.0;
+            }
+            if (lots > 0.0) {
+                const double outlay = cost + fee;
+                st.debt = fmax(outlay - st.cash, 0.0);
+                st.cash = fmax(st.cash - outlay, 0.0);
+                st.shares = lots * 100.0;
+                st.e_outlay = outlay; st.e_price = exec; st.e_day = t;
+            }
+        }
+    }
+    const double sv = st.shares * st.last_px;
+    y[0] = st.cash - st.debt; y[1] = sv; y[2] = (st.cash - st.debt) + sv;
+}
 static __global__ __launch_bounds__(SEQ_BLOCK) void lev_backtest_kernel(LevArgs a, Dims d) {
     const int64_t s = (int64_t)blockIdx.x * SEQ_BLOCK + threadIdx.x;
     if (s >= d.n) return;
     const int64_t base = dims_base(d, s), T = dims_len(d, s);
-    const pq_lev_params prm = a.prm;
-    double cash = prm.initial_capital, debt = 0.0, shares = 0.0, last_px = 0.0, e_outlay = 0.0, e_price = 0.0;
-    int64_t e_day = 0, trades = 0, wins = 0;
+    LevState st;
+    st.reset(a.prm.initial_capital);
     const int64_t rb = s * (int64_t)a.max_trades;
     for (int64_t t = 0; t < T; t++) {
-        double p = a.price[base + t];
-        if (pq_isnull(p)) p = __longlong_as_double(0x7FF8000000000000LL);
-        const bool valid = !(isnan(p) || p <= 0.0);
-        if (debt > 0.0) debt += debt * (prm.interest_rate / 252.0); // D-10 step 1: the daily rate is formed first
-        if (valid) {
-            last_px = p;
-            int do_sell = 0;
-            if (shares > 0.0) {
-                if (debt > 0.0 && cash + shares * p - debt < prm.margin_call_threshold * (shares * p)) do_sell = 2;
-                else if (a.sell[base + t]) do_sell = 1;
-            }
-            if (do_sell) {
-                double exec = p * (1.0 - prm.slippage);
-                double rev = shares * exec;
-                double fee = fmax(rev * prm.commission_rate, prm.min_commission);
-                double net = rev - fee;
-                double gain = net - e_outlay;
-                if (trades < a.max_trades && a.entry_day) {
-                    a.entry_day[rb + trades] = (int32_t)e_day; a.exit_day[rb + trades] = (int32_t)t;
-                    a.entry_price[rb + trades] = e_price; a.exit_price[rb + trades] = exec; a.quantity[rb + trades] = shares;
-                    a.pnl[rb + trades] = gain; a.pnl_pct[rb + trades] = gain / e_outlay * 100.0; a.reason[rb + trades] = do_sell;
-                }
-                trades += 1;
-                if (gain > 0.0) wins += 1;
-                cash = cash + net - debt;
-                debt = 0.0;
-                shares = 0.0;
-            } else if (a.buy[base + t] && shares == 0.0) {
-                double exec = p * (1.0 + prm.slippage);
-                double power = cash * prm.position_size * prm.leverage;
-                double lots = floor(power / (exec * 100.0));
-                double cost = 0.0, fee = 0.0;
-                while (lots > 0.0) {
-                    cost = lots * 100.0 * exec;
-                    fee = fmax(cost * prm.commission_rate, prm.min_commission);
-                    if (cost + fee <= cash * prm.leverage) break;
-                    lots -= 1.0;
-                }
-                if (lots > 0.0) {
-                    double outlay = cost + fee;
-                    debt = fmax(outlay - cash, 0.0);
-                    cash = fmax(cash - outlay, 0.0);
-                    shares = lots * 100.0;
-                    e_outlay = outlay; e_price = exec; e_day = t;
-                }
-            }
-        }
-        double sv = shares * last_px;
-        a.cash_net[base + t] = cash - debt;
-        a.stock_value[base + t] = sv;
-        a.total_value[base + t] = (cash - debt) + sv;
+        double y[3];
+        lev_row(st, a, rb, a.price[base + t], a.buy[base + t] != 0, a.sell[base + t] != 0, t, y);
+        a.cash_net[base + t] = y[0];
+        a.stock_value[base + t] = y[1];
+        a.total_value[base + t] = y[2];
     }
-    if (a.trade_count) a.trade_count[s] = (int32_t)trades;
-    if (a.summary) bt_summary_from_row(a.total_value + base, T, prm.initial_capital, trades, wins, a.bench, a.summary + s * PQ_SUMMARY_COLS);
+    if (a.trade_count) a.trade_count[s] = (int32_t)st.trades;
+    if (a.summary) bt_summary_from_row(a.total_value + base, T, a.prm.initial_capital, st.trades, st.wins, a.bench, a.summary + s * PQ_SUMMARY_COLS);
 }
 
 // The same engine as a tiled SEQ op: the price and the three daily columns move through the coalesced tile path; the
@@ -425,15 +251,13 @@ struct LevOp {
     const uint8_t *brow, *srow;
     int64_t rec0, T;
     unsigned long long bcur, scur, bnext, snext;
-    double cash, debt, shares, last_px, e_outlay, e_price;
-    int64_t e_day, trades, wins;
+    LevState st;
     __device__ void init(const Row<1> &r) {
         const int64_t off = r.in[0] - a.price; // element offset of this lane's series
         brow = a.buy + off; srow = a.sell + off;
         T = r.len;
         rec0 = (off / stride) * (int64_t)a.max_trades; // this series' slice of the trade-record arrays
-        cash = a.prm.initial_capital; debt = 0.0; shares = 0.0; last_px = 0.0; e_outlay = 0.0; e_price = 0.0;
-        e_day = 0; trades = 0; wins = 0;
+        st.reset(a.prm.initial_capital);
         bcur = scur = 0;
         bnext = T >= 8 ? *reinterpret_cast<const unsigned long long *>(brow) : 0;
         snext = T >= 8 ? *reinterpret_cast<const unsigned long long *>(srow) : 0;
@@ -456,62 +280,12 @@ struct LevOp {
             }
         }
         const bool buy = ((bcur >> (8 * j)) & 0xff) != 0, sell = ((scur >> (8 * j)) & 0xff) != 0;
-        const pq_lev_params &prm = a.prm;
-        double p = x[0];
-        if (pq_isnull(p)) p = __longlong_as_double(0x7FF8000000000000LL);
-        const bool valid = !(isnan(p) || p <= 0.0);
-        if (debt > 0.0) debt += debt * (prm.interest_rate / 252.0); // D-10 step 1: the daily rate is formed first
-        if (valid) {
-            last_px = p;
-            int do_sell = 0;
-            if (shares > 0.0) {
-                if (debt > 0.0 && cash + shares * p - debt < prm.margin_call_threshold * (shares * p)) do_sell = 2;
-                else if (sell) do_sell = 1;
-            }
-            if (do_sell) {
-                double exec = p * (1.0 - prm.slippage);
-                double rev = shares * exec;
-                double fee = fmax(rev * prm.commission_rate, prm.min_commission);
-                double net = rev - fee;
-                double gain = net - e_outlay;
-                if (trades < a.max_trades && a.entry_day) {
-                    const int64_t rb = rec0 + trades;
-                    a.entry_day[rb] = (int32_t)e_day; a.exit_day[rb] = (int32_t)t;
-                    a.entry_price[rb] = e_price; a.exit_price[rb] = exec; a.quantity[rb] = shares;
-                    a.pnl[rb] = gain; a.pnl_pct[rb] = gain / e_outlay * 100.0; a.reason[rb] = do_sell;
-                }
-                trades += 1;
-                if (gain > 0.0) wins += 1;
-                cash = cash + net - debt;
-                debt = 0.0;
-                shares = 0.0;
-            } else if (buy && shares == 0.0) {
-                double exec = p * (1.0 + prm.slippage);
-                double power = cash * prm.position_size * prm.leverage;
-                double lots = floor(power / (exec * 100.0));
-                double cost = 0.0, fee = 0.0;
-                while (lots > 0.0) {
-                    cost = lots * 100.0 * exec;
-                    fee = fmax(cost * prm.commission_rate, prm.min_commission);
-                    if (cost + fee <= cash * prm.leverage) break;
-                    lots -= 1.0;
-                }
-                if (lots > 0.0) {
-                    double outlay = cost + fee;
-                    debt = fmax(outlay - cash, 0.0);
-                    cash = fmax(cash - outlay, 0.0);
-                    shares = lots * 100.0;
-                    e_outlay = outlay; e_price = exec; e_day = t;
-                }
-            }
-        }
-        const double sv = shares * last_px;
-        y[0] = cash - debt; y[1] = sv; y[2] = (cash - debt) + sv;
+        lev_row(st, a, rec0, x[0], buy, sell, t, y);
     }
     __host__ __device__ void *finish_writes() const { return a.summary; }
     __device__ void finish(double *const *outp, const Dims &d, int64_t s) {
-        if (a.trade_count) a.trade_count[s] = (int32_t)trades;
-        if (a.summary) bt_summary_from_row(outp[2] + dims_base(d, s), dims_len(d, s), a.prm.initial_capital, trades, wins, a.bench, a.summary + s * PQ_SUMMARY_COLS);
+        if (a.trade_count) a.trade_count[s] = (int32_t)st.trades;
+        if (a.summary) bt_summary_from_row(outp[2] + dims_base(d, s), dims_len(d, s), a.prm.initial_capital, st.trades, st.wins, a.bench, a.summary + s * PQ_SUMMARY_COLS);
     }
 };
 

@@ -82,142 +82,6 @@ __device__ __forceinline__ void btw_bcast_ema(EmaCore &e, int l) { // every lane
     e.sum = btw_readlane(e.sum, l);
 }
 
-// calculate_summary (metrics.rs:7-152) of the equity row that sits in LDS (`px`; overwritten with the daily returns): lane c owns
-// rows [c*C, (c+1)*C).  The running max is an exact prefix max; max_drawdown / max_profit / win_rate / total_trades are exact; the
-// ordered f64 sums (mean, variance, covariance) are summed per chunk and then across the lanes in a fixed order (<= 1e-12).
-// `bm`: the benchmark rows or null -- in LDS with the same geometry, or (bm_linear) a plain series in global memory (the leveraged
-// engine's ONE benchmark shared by all symbols: it stays in L2, so it is not worth a second LDS row per wave).
-__device__ __forceinline__ void btw_summary(const BtwGeom &g, int lane, double *px, const double *bm, double initial_capital, int trades, int wins,
-                                            double *sm, bool bm_linear = false) {
-    const int T = g.T, C = g.C, P = g.P;
-    auto addr = [&](int i) { return g.addr(i); };
-    auto baddr = [&](int i) { return bm_linear ? i : g.addr(i); };
-    struct { double initial_capital; } prm{initial_capital};
-    const bool has_bench = bm != nullptr;
-    // ---- summary (metrics.rs:7-152): lane c owns rows [c*C, (c+1)*C) of the equity row now in LDS
-    const int c = lane, lo = c * C, hi = lo + C < T ? lo + C : T;
-    const int nrow = hi - lo; // <= 0: idle lane
-    double *erow = px + c * P;
-    const double init = prm.initial_capital;
-    const double NEG_INF = __longlong_as_double((long long)0xFFF0000000000000ULL);
-    double lm = NEG_INF;
-    for (int b0 = 0; b0 < nrow; b0 += 8) { // (eight LDS reads in flight, then the compares)
-        double e[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) e[u] = b0 + u < nrow ? erow[b0 + u] : NEG_INF;
-#pragma unroll
-        for (int u = 0; u < 8; u++) if (e[u] > lm) lm = e[u];
-    }
-    double Mx = lm; // inclusive prefix max over the lanes (exact in any order)
-#define BTW_MAX(CTRL, RM) { const double t = btw_dpp<CTRL, RM>(NEG_INF, Mx); if (t > Mx) Mx = t; }
-    BTW_SCAN_STEPS(BTW_MAX)
-#undef BTW_MAX
-    double max_eq = btw_prev_lane(NEG_INF, Mx);
-    if (lane == 0 || !(max_eq > init)) max_eq = init; // the running max starts at initial_capital (metrics.rs:21)
-    double prev = init;
-    if (c > 0 && nrow > 0) prev = px[addr(lo - 1)];
-    const double last_eq = px[addr(T - 1)];
-    double max_dd = 0.0, rs = 0.0;
-    for (int b0 = 0; b0 < nrow; b0 += 4) { // metrics.rs:26-49, four rows at a time: their eight divisions overlap
-        double e[4], mx[4], pv[4];
-#pragma unroll
-        for (int u = 0; u < 4; u++) e[u] = b0 + u < nrow ? erow[b0 + u] : 0.0;
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            if (b0 + u < nrow && e[u] > max_eq) max_eq = e[u];
-            mx[u] = max_eq;
-            pv[u] = prev;
-            if (b0 + u < nrow) prev = e[u];
-        }
-#pragma unroll
-        for (int u = 0; u < 4; u++) {
-            const double dd = (mx[u] > 0.0) ? (mx[u] - e[u]) / mx[u] : 0.0;
-            const double rr = (pv[u] > 0.0) ? (e[u] - pv[u]) / pv[u] : 0.0;
-            if (b0 + u < nrow) {
-                if (dd > max_dd) max_dd = dd;
-                rs += rr;
-                erow[b0 + u] = rr;
-            }
-        }
-    }
-    // wave sums in a fixed order (an inclusive DPP scan, the total read from lane 63): the same value on every lane
-    auto wave_sum3 = [&](double &v0, double &v1, double &v2) {
-#define BTW_SUM3(CTRL, RM) { v0 += btw_dpp<CTRL, RM>(0.0, v0); v1 += btw_dpp<CTRL, RM>(0.0, v1); v2 += btw_dpp<CTRL, RM>(0.0, v2); }
-        BTW_SCAN_STEPS(BTW_SUM3)
-#undef BTW_SUM3
-        v0 = btw_readlane(v0, 63); v1 = btw_readlane(v1, 63); v2 = btw_readlane(v2, 63);
-    };
-    double bs = 0.0, pb0 = 0.0;
-    const double *brow = bm + c * (bm_linear ? C : P);
-    if (has_bench) { // metrics.rs:86-140: the benchmark's daily returns
-        pb0 = (c == 0 || nrow <= 0) ? bm[0] : bm[baddr(lo - 1)];
-        double pb = pb0;
-        for (int b0 = 0; b0 < nrow; b0 += 4) {
-            double bv[4], pv[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) { bv[u] = b0 + u < nrow ? brow[b0 + u] : 0.0; pv[u] = pb; if (b0 + u < nrow) pb = bv[u]; }
-#pragma unroll
-            for (int u = 0; u < 4; u++) { const double br = (pv[u] > 0.0) ? (bv[u] - pv[u]) / pv[u] : 0.0; if (b0 + u < nrow) bs += br; }
-        }
-    }
-    {
-#define BTW_MAXDD(CTRL, RM) { const double t = btw_dpp<CTRL, RM>(0.0, max_dd); if (t > max_dd) max_dd = t; }
-        BTW_SCAN_STEPS(BTW_MAXDD)
-#undef BTW_MAXDD
-        max_dd = btw_readlane(max_dd, 63);
-        double zero = 0.0;
-        wave_sum3(rs, bs, zero);
-    }
-    const double ret_sum = rs;
-    const double DAYS = 252.0, RF = 0.03;
-    const double total_return = (last_eq - init) / init;
-    const double mean = ret_sum / (double)T;
-    const double dof = fmax((double)T - 1.0, 1.0);
-    const double bmean = bs / (double)T;
-    double vs = 0.0, bvs = 0.0, cvs = 0.0;
-    {
-        double pb = pb0;
-        for (int b0 = 0; b0 < nrow; b0 += 4) {
-            double rr[4], bv[4], pv[4];
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                rr[u] = b0 + u < nrow ? erow[b0 + u] : mean;
-                bv[u] = 0.0; pv[u] = pb;
-                if (has_bench) { bv[u] = b0 + u < nrow ? brow[b0 + u] : 0.0; if (b0 + u < nrow) pb = bv[u]; }
-            }
-#pragma unroll
-            for (int u = 0; u < 4; u++) {
-                const double dlt = rr[u] - mean;
-                if (b0 + u < nrow) vs += dlt * dlt;
-                if (has_bench) {
-                    const double br = (pv[u] > 0.0) ? (bv[u] - pv[u]) / pv[u] : 0.0;
-                    const double db = br - bmean;
-                    if (b0 + u < nrow) { bvs += db * db; cvs += dlt * db; }
-                }
-            }
-        }
-    }
-    wave_sum3(vs, bvs, cvs);
-    const double ann = (total_return > -1.0) ? pow(1.0 + total_return, DAYS / (double)T) - 1.0 : -1.0;
-    const double var = vs / dof;
-    const double vol = sqrt(var) * sqrt(DAYS);
-    const double sharpe = (vol > 0.0) ? (ann - RF) / vol : 0.0;
-    const double win_rate = (trades > 0) ? (double)wins / (double)trades : 0.0;
-    double alpha = 0.0, beta = 0.0;
-    if (has_bench) {
-        const double bvar = bvs / dof, cov = cvs / dof;
-        if (bvar > 0.0) beta = cov / bvar;
-        const double b0 = bm[0], b1 = bm[baddr(T - 1)];
-        const double btr = (b0 > 0.0) ? (b1 - b0) / b0 : 0.0;
-        const double bann = (btr > -1.0) ? pow(1.0 + btr, DAYS / (double)T) - 1.0 : -1.0;
-        alpha = ann - (RF + beta * (bann - RF));
-    }
-    if (lane == 0) {
-        sm[0] = ann; sm[1] = max_dd; sm[2] = alpha; sm[3] = beta; sm[4] = sharpe;
-        sm[5] = fmax(total_return, 0.0); sm[6] = win_rate; sm[7] = (double)trades;
-    }
-}
-
 // Per-lane row masks: bit b = row b of the lane's chunk (MACD signals) or of the lane's 64-row block (signals as inputs).  NW = 1
 // covers len <= 4096 (C <= 64); NW = 2 -- chunks of up to 128 rows, two blocks per lane (lane w: blocks w and w + 64) -- len <= 8192.
 template <int NW>
@@ -317,36 +181,41 @@ __device__ __forceinline__ void btw_fill_tiles(const BtWaveArgs &a, const BtwGeo
     }
 }
 
-// calculate_summary over NWV wavefronts: the lanes of the workgroup, in row order, own a QUARTER chunk each (global lane 4 c + q: rows
-// c * C + q * Cq ...), the running maximum and the sums are combined wave by wave through shd[] in a fixed order.  Same exact columns
-// (prefix maximum, max_drawdown, win_rate, total_trades); the ordered sums are summed per quarter chunk, then per wave, then over the
-// waves (<= 1e-12, as in the one-wave form).  Every wave passes the three barriers; only wave 0 writes the row.
+// calculate_summary (metrics.rs:7-152) of the equity row that sits in LDS (`px`; overwritten with the daily returns), by the NWV wavefronts
+// of the symbol's workgroup: the lanes of the workgroup, in row order, own one NWV-th of a chunk each (global lane NWV c + q: rows
+// c * C + q * Cq ...; one wave: lane c owns the chunk [c*C, (c+1)*C)).  The running max is an exact prefix max; max_drawdown / max_profit /
+// win_rate / total_trades are exact; the ordered f64 sums (mean, variance, covariance) are summed per lane, then over the lanes of a wave
+// in a fixed order, then -- NWV > 1 -- wave by wave through shd[] (<= 1e-12; the one-wave and the four-wave order differ, and so may the
+// last bits of these sums).  With NWV > 1 every wave passes the three barriers and only wave 0 writes the row.
+// `bm`: the benchmark rows or null -- in LDS with the same geometry, or (bm_linear, one wave only) a plain series in global memory (the
+// leveraged engine's ONE benchmark shared by all symbols: it stays in L2, so it is not worth a second LDS row per wave).
 template <int NWV>
-__device__ __forceinline__ void btw_summary_mw(const BtwGeom &g, int lane, int wv, double *px, const double *bm, double initial_capital, int trades,
-                                               int wins, double *sm, double *shd) {
-    static_assert(NWV == 2 || NWV == 4, "sub-chunks per chunk: a power of two");
+__device__ __forceinline__ void btw_summary(const BtwGeom &g, int lane, int wv, double *px, const double *bm, double initial_capital, int trades,
+                                            int wins, double *sm, double *shd, bool bm_linear = false) {
+    static_assert(NWV == 1 || NWV == 2 || NWV == 4, "sub-chunks per chunk: a power of two");
     const int T = g.T, C = g.C, P = g.P;
     const int Cq = (C + NWV - 1) / NWV;
     const int gl = wv * 64 + lane, c = gl / NWV, q = gl % NWV;
     const int lo = c * C + q * Cq;
     int hi = lo + Cq;
-    if (hi > (c + 1) * C) hi = (c + 1) * C;
+    if (NWV > 1 && hi > (c + 1) * C) hi = (c + 1) * C;
     if (hi > T) hi = T;
     const int nrow = hi - lo; // <= 0: idle lane
+    auto baddr = [&](int i) { return bm_linear ? i : g.addr(i); };
     double *erow = px + c * P + q * Cq;
     const bool has_bench = bm != nullptr;
-    const double *brow = has_bench ? bm + c * P + q * Cq : nullptr;
+    const double *brow = bm + (bm_linear ? lo : c * P + q * Cq);
     const double init = initial_capital;
     const double NEG_INF = __longlong_as_double((long long)0xFFF0000000000000ULL);
     double lm = NEG_INF;
-    for (int b0 = 0; b0 < nrow; b0 += 8) {
+    for (int b0 = 0; b0 < nrow; b0 += 8) { // (eight LDS reads in flight, then the compares)
         double e[8];
 #pragma unroll
         for (int u = 0; u < 8; u++) e[u] = b0 + u < nrow ? erow[b0 + u] : NEG_INF;
 #pragma unroll
         for (int u = 0; u < 8; u++) if (e[u] > lm) lm = e[u];
     }
-    double Mx = lm; // inclusive prefix max over this wave's lanes
+    double Mx = lm; // inclusive prefix max over this wave's lanes (exact in any order)
 #define BTW_MAX(CTRL, RM) { const double t = btw_dpp<CTRL, RM>(NEG_INF, Mx); if (t > Mx) Mx = t; }
     BTW_SCAN_STEPS(BTW_MAX)
 #undef BTW_MAX
@@ -355,13 +224,15 @@ __device__ __forceinline__ void btw_summary_mw(const BtwGeom &g, int lane, int w
     double prev = init;
     if (gl > 0 && nrow > 0) prev = px[g.addr(lo - 1)];
     const double last_eq = px[g.addr(T - 1)];
-    if (lane == 0) shd[BTW_SH_RED + wv] = btw_readlane(Mx, 63);
-    __syncthreads();
+    if constexpr (NWV > 1) {
+        if (lane == 0) shd[BTW_SH_RED + wv] = btw_readlane(Mx, 63);
+        __syncthreads();
 #pragma unroll
-    for (int w = 0; w < NWV - 1; w++) { const double t = shd[BTW_SH_RED + w]; if (w < wv && t > max_eq) max_eq = t; }
+        for (int w = 0; w < NWV - 1; w++) { const double t = shd[BTW_SH_RED + w]; if (w < wv && t > max_eq) max_eq = t; }
+    }
     if (gl == 0 || !(max_eq > init)) max_eq = init; // the running max starts at initial_capital (metrics.rs:21)
     double max_dd = 0.0, rs = 0.0;
-    for (int b0 = 0; b0 < nrow; b0 += 4) { // metrics.rs:26-49
+    for (int b0 = 0; b0 < nrow; b0 += 4) { // metrics.rs:26-49, four rows at a time: their eight divisions overlap
         double e[4], mx[4], pv[4];
 #pragma unroll
         for (int u = 0; u < 4; u++) e[u] = b0 + u < nrow ? erow[b0 + u] : 0.0;
@@ -375,7 +246,7 @@ __device__ __forceinline__ void btw_summary_mw(const BtwGeom &g, int lane, int w
 #pragma unroll
         for (int u = 0; u < 4; u++) {
             const double dd = (mx[u] > 0.0) ? (mx[u] - e[u]) / mx[u] : 0.0;
-            const double rr = (pv[u] > 0.0) ? (e[u] - pv[u]) / pv[u] : 0.0;
+            const double rr = bt_ret(pv[u], e[u]);
             if (b0 + u < nrow) {
                 if (dd > max_dd) max_dd = dd;
                 rs += rr;
@@ -383,31 +254,36 @@ __device__ __forceinline__ void btw_summary_mw(const BtwGeom &g, int lane, int w
             }
         }
     }
-    auto wave_sum3 = [&](double &v0, double &v1, double &v2) { // the wave's totals, the same value on every lane
+    // wave sums in a fixed order (an inclusive DPP scan, the total read from lane 63): the same value on every lane
+    auto wave_sum3 = [&](double &v0, double &v1, double &v2) {
 #define BTW_SUM3(CTRL, RM) { v0 += btw_dpp<CTRL, RM>(0.0, v0); v1 += btw_dpp<CTRL, RM>(0.0, v1); v2 += btw_dpp<CTRL, RM>(0.0, v2); }
         BTW_SCAN_STEPS(BTW_SUM3)
 #undef BTW_SUM3
         v0 = btw_readlane(v0, 63); v1 = btw_readlane(v1, 63); v2 = btw_readlane(v2, 63);
     };
-    // the workgroup's totals of three values, waves in order (round = a region of shd[] of its own)
-    auto group3 = [&](int round, double &v0, double &v1, double &v2) {
+    // the workgroup's totals of three values, waves in order (round = a region of shd[] of its own); the third is a sum or a maximum
+    auto group3 = [&](int round, bool max2, double &v0, double &v1, double &v2) {
         double *r = shd + BTW_SH_RED + 4 + round * 3 * NWV;
         if (lane == 0) { r[wv] = v0; r[NWV + wv] = v1; r[2 * NWV + wv] = v2; }
         __syncthreads();
         v0 = r[0]; v1 = r[NWV]; v2 = r[2 * NWV];
 #pragma unroll
-        for (int w = 1; w < NWV; w++) { v0 += r[w]; v1 += r[NWV + w]; v2 += r[2 * NWV + w]; }
+        for (int w = 1; w < NWV; w++) {
+            v0 += r[w]; v1 += r[NWV + w];
+            if (!max2) v2 += r[2 * NWV + w];
+            else if (r[2 * NWV + w] > v2) v2 = r[2 * NWV + w];
+        }
     };
     double bs = 0.0, pb0 = 0.0;
     if (has_bench) { // metrics.rs:86-140: the benchmark's daily returns
-        pb0 = (gl == 0 || nrow <= 0) ? bm[0] : bm[g.addr(lo - 1)];
+        pb0 = (gl == 0 || nrow <= 0) ? bm[0] : bm[baddr(lo - 1)];
         double pb = pb0;
         for (int b0 = 0; b0 < nrow; b0 += 4) {
             double bv[4], pv[4];
 #pragma unroll
             for (int u = 0; u < 4; u++) { bv[u] = b0 + u < nrow ? brow[b0 + u] : 0.0; pv[u] = pb; if (b0 + u < nrow) pb = bv[u]; }
 #pragma unroll
-            for (int u = 0; u < 4; u++) { const double br = (pv[u] > 0.0) ? (bv[u] - pv[u]) / pv[u] : 0.0; if (b0 + u < nrow) bs += br; }
+            for (int u = 0; u < 4; u++) { const double br = bt_ret(pv[u], bv[u]); if (b0 + u < nrow) bs += br; }
         }
     }
     {
@@ -417,19 +293,9 @@ __device__ __forceinline__ void btw_summary_mw(const BtwGeom &g, int lane, int w
         max_dd = btw_readlane(max_dd, 63);
         double zero = 0.0;
         wave_sum3(rs, bs, zero);
-        // (the maximum rides in the third slot as a sum would: combined below by comparison instead)
-        double *r = shd + BTW_SH_RED + 4;
-        if (lane == 0) { r[wv] = rs; r[NWV + wv] = bs; r[2 * NWV + wv] = max_dd; }
-        __syncthreads();
-        rs = r[0]; bs = r[NWV]; max_dd = r[2 * NWV];
-#pragma unroll
-        for (int w = 1; w < NWV; w++) { rs += r[w]; bs += r[NWV + w]; if (r[2 * NWV + w] > max_dd) max_dd = r[2 * NWV + w]; }
+        if constexpr (NWV > 1) group3(0, true, rs, bs, max_dd);
     }
-    const double ret_sum = rs;
-    const double DAYS = 252.0, RF = 0.03;
-    const double total_return = (last_eq - init) / init;
-    const double mean = ret_sum / (double)T;
-    const double dof = fmax((double)T - 1.0, 1.0);
+    const double mean = rs / (double)T;
     const double bmean = bs / (double)T;
     double vs = 0.0, bvs = 0.0, cvs = 0.0;
     {
@@ -447,33 +313,25 @@ __device__ __forceinline__ void btw_summary_mw(const BtwGeom &g, int lane, int w
                 const double dlt = rr[u] - mean;
                 if (b0 + u < nrow) vs += dlt * dlt;
                 if (has_bench) {
-                    const double br = (pv[u] > 0.0) ? (bv[u] - pv[u]) / pv[u] : 0.0;
-                    const double db = br - bmean;
+                    const double db = bt_ret(pv[u], bv[u]) - bmean;
                     if (b0 + u < nrow) { bvs += db * db; cvs += dlt * db; }
                 }
             }
         }
     }
     wave_sum3(vs, bvs, cvs);
-    group3(1, vs, bvs, cvs);
-    if (wv != 0) return;
-    const double ann = (total_return > -1.0) ? pow(1.0 + total_return, DAYS / (double)T) - 1.0 : -1.0;
-    const double var = vs / dof;
-    const double vol = sqrt(var) * sqrt(DAYS);
-    const double sharpe = (vol > 0.0) ? (ann - RF) / vol : 0.0;
-    const double win_rate = (trades > 0) ? (double)wins / (double)trades : 0.0;
-    double alpha = 0.0, beta = 0.0;
-    if (has_bench) {
-        const double bvar = bvs / dof, cov = cvs / dof;
-        if (bvar > 0.0) beta = cov / bvar;
-        const double b0 = bm[0], b1 = bm[g.addr(T - 1)];
-        const double btr = (b0 > 0.0) ? (b1 - b0) / b0 : 0.0;
-        const double bann = (btr > -1.0) ? pow(1.0 + btr, DAYS / (double)T) - 1.0 : -1.0;
-        alpha = ann - (RF + beta * (bann - RF));
+    if constexpr (NWV > 1) {
+        group3(1, false, vs, bvs, cvs);
+        if (wv != 0) return;
     }
+    const double b0 = has_bench ? bm[0] : 0.0, b1 = has_bench ? bm[baddr(T - 1)] : 0.0;
+    // every lane closes the row and lane 0 stores it: behind a branch on the lane, the close's dependent chain (pow, the divisions) would
+    // wait for the reductions above instead of overlapping them (+0.4 us per symbol on a lone wave)
+    double row[PQ_SUMMARY_COLS];
+    bt_summary_close((double)T, init, last_eq, max_dd, vs, bvs, cvs, trades, wins, has_bench, b0, b1, row);
     if (lane == 0) {
-        sm[0] = ann; sm[1] = max_dd; sm[2] = alpha; sm[3] = beta; sm[4] = sharpe;
-        sm[5] = fmax(total_return, 0.0); sm[6] = win_rate; sm[7] = (double)trades;
+#pragma unroll
+        for (int k = 0; k < PQ_SUMMARY_COLS; k++) sm[k] = row[k];
     }
 }
 
@@ -490,7 +348,7 @@ __device__ __forceinline__ void btw_helper_wave(const BtWaveArgs &a, const BtwGe
     if (shd[BTW_SH_DENSE] != 0.0) btw_fill_tiles<NW>(a, geo, base, lane, wv, NWV, px, evw, evr, evp);
     __syncthreads(); // B3: the equity row is complete
     if (!a.summary) return;
-    btw_summary_mw<NWV>(geo, lane, wv, px, a.bench ? bm : nullptr, a.prm.initial_capital, 0, 0, a.summary + s * PQ_SUMMARY_COLS, shd);
+    btw_summary<NWV>(geo, lane, wv, px, a.bench ? bm : nullptr, a.prm.initial_capital, 0, 0, a.summary + s * PQ_SUMMARY_COLS, shd);
 }
 
 #ifdef PQ_BTW_PROF // scripts/ab_build.sh only: per-phase device time summed over the waves, stats[4 + k] in 10 ns ticks
@@ -911,7 +769,8 @@ __global__ __launch_bounds__(64 * NWV) void bt_wave_kernel(BtWaveArgs a, Dims d)
     }
     BTW_T(1);
 
-    double pos = 0.0, avail = prm.initial_capital, entry_cost = 0.0;
+    BtPool pl;
+    pl.reset(prm.initial_capital);
     int trades = 0, wins = 0;
     bool flat = true;
     // The serial part of a symbol is the cash recurrence through its ~100 round trips, and an f64 operation that waits for its
@@ -924,7 +783,7 @@ __global__ __launch_bounds__(64 * NWV) void bt_wave_kernel(BtWaveArgs a, Dims d)
     bool bad = false;
     auto buy_fast = [&](double p, double r) { // vectorized.rs:146-161 on a flat pool (pos == +0.0: cash + pos * price == cash)
         const double exec = p + prm.buy_slippage;
-        const double deploy = avail * prm.position_size;
+        const double deploy = pl.avail * prm.position_size;
         const double qa = deploy * r;
         const double qty = floor(qa);
         // decided here only if 1 <= q~ < 2^28 and its fraction lies in (2^-22, 1 - 2^-22) (the admissible error is q~ * 2^-51 <=
@@ -933,32 +792,24 @@ __global__ __launch_bounds__(64 * NWV) void bt_wave_kernel(BtWaveArgs a, Dims d)
         bad |= (hq - 0x3FF00000u) >= (0x41B00000u - 0x3FF00000u) || (hf - 0x3E900000u) >= (0x3FEFFFFEu - 0x3E900000u);
         const double cost = qty * exec;
         const double fee = fmax(cost * prm.buy_commission_rate, prm.min_commission);
-        pos += qty;
-        avail -= cost + fee;
-        entry_cost = pos * p;
+        pl.pos += qty;
+        pl.avail -= cost + fee;
+        pl.entry_cost = pl.pos * p;
         trades += 1;
     };
     auto sell_fast = [&](double p) { // :162-175
         const double exec = p - prm.sell_slippage;
-        const double revenue = pos * exec;
+        const double revenue = pl.pos * exec;
         const double fee = fmax(revenue * prm.sell_commission_rate, prm.min_commission);
         const double net = revenue - fee;
-        wins += net > entry_cost ? 1 : 0;
-        avail += net;
-        pos = 0.0;
+        wins += net > pl.entry_cost ? 1 : 0;
+        pl.avail += net;
+        pl.pos = 0.0;
     };
     // The reference's own operations (an infinite price makes qty NaN there and 0 here: no trade either way).
     auto trade = [&](double p) -> bool { // false: a buy that cannot afford one share, nothing changes
-        if (flat) {
-            const double exec = p + prm.buy_slippage;
-            const double deploy = avail * prm.position_size;
-            const double qty = floor(deploy / exec);
-            if (!(qty > 0.0)) return false;
-            const double cost = qty * exec;
-            const double fee = fmax(cost * prm.buy_commission_rate, prm.min_commission);
-            pos += qty;
-            avail -= cost + fee;
-            entry_cost = pos * p;
+        if (flat) { // pl.pos == +0.0, and an event's price is positive: bt_buy's avail + pos * price is avail itself
+            if (!bt_buy(pl, p, prm)) return false;
             trades += 1;
             flat = false;
         } else {
@@ -1007,13 +858,13 @@ __global__ __launch_bounds__(64 * NWV) void bt_wave_kernel(BtWaveArgs a, Dims d)
                     const int t = __builtin_amdgcn_readfirstlane(t0);
                     const double pb = btw_readlane(ev[g], t), rb = btw_readlane(rv[g], t), psl = btw_readlane(ev[g], t + 1);
                     buy_fast(pb, rb);
-                    if (lane == t) { tpv[g] = pos; tcv[g] = avail; }
+                    if (lane == t) { tpv[g] = pl.pos; tcv[g] = pl.avail; }
                     sell_fast(psl);
-                    if (lane == t + 1) tcv[g] = avail; // the position after a sell is 0.0
+                    if (lane == t + 1) tcv[g] = pl.avail; // the position after a sell is 0.0
                 }
                 if (n & 1) { // last event of the series: the position stays open
                     buy_fast(btw_readlane(ev[g], n - 1), btw_readlane(rv[g], n - 1));
-                    if (lane == n - 1) { tpv[g] = pos; tcv[g] = avail; }
+                    if (lane == n - 1) { tpv[g] = pl.pos; tcv[g] = pl.avail; }
                 }
             }
         }
@@ -1027,7 +878,7 @@ __global__ __launch_bounds__(64 * NWV) void bt_wave_kernel(BtWaveArgs a, Dims d)
         BTW_T(9);
         if (bad) { // wave-uniform: start over in the block form below
             dense = false;
-            pos = 0.0; avail = prm.initial_capital; entry_cost = 0.0; trades = 0; wins = 0; flat = true;
+            pl.reset(prm.initial_capital); trades = 0; wins = 0; flat = true;
         }
     }
     if constexpr (NWV > 1) {
@@ -1172,7 +1023,7 @@ __global__ __launch_bounds__(64 * NWV) void bt_wave_kernel(BtWaveArgs a, Dims d)
         const int i = 64 * j + lane;
         const int ai = addr(i);
         double x = px[ai];
-        double tp = pos, tc = avail; // state after the last event at or before my row
+        double tp = pl.pos, tc = pl.avail; // state after the last event at or before my row
         unsigned long long w = searching ? 0ULL : btw_word(myword, j);
         while (w) {
             const int l = __builtin_ctzll(w);
@@ -1185,13 +1036,13 @@ __global__ __launch_bounds__(64 * NWV) void bt_wave_kernel(BtWaveArgs a, Dims d)
                 break;
             }
             w &= w - 1;
-            if (lane >= l) { tp = pos; tc = avail; }
+            if (lane >= l) { tp = pl.pos; tc = pl.avail; }
         }
         if (searching) {
             const int rend = 64 * (j + 1);
             while (r >= 0 && r < rend) {
                 const int l = r & 63;
-                if (trade(btw_readlane(x, l)) && lane >= l) { tp = pos; tc = avail; }
+                if (trade(btw_readlane(x, l)) && lane >= l) { tp = pl.pos; tc = pl.avail; }
                 r = find();
             }
         }
@@ -1209,8 +1060,7 @@ __global__ __launch_bounds__(64 * NWV) void bt_wave_kernel(BtWaveArgs a, Dims d)
     if constexpr (NWV > 1) __syncthreads(); // B3: the equity row is complete (dense: every wave's tiles; else the block form above)
     if (!a.summary) return;
 
-    if constexpr (NWV > 1) btw_summary_mw<NWV>(geo, lane, 0, px, a.bench ? bm : nullptr, prm.initial_capital, trades, wins, a.summary + s * PQ_SUMMARY_COLS, shd);
-    else btw_summary(geo, lane, px, a.bench ? bm : nullptr, prm.initial_capital, trades, wins, a.summary + s * PQ_SUMMARY_COLS);
+    btw_summary<NWV>(geo, lane, 0, px, a.bench ? bm : nullptr, prm.initial_capital, trades, wins, a.summary + s * PQ_SUMMARY_COLS, shd);
     BTW_T(3);
 }
 
@@ -1352,7 +1202,7 @@ __global__ __launch_bounds__(64) void lev_wave_kernel(LevWaveArgs w, Dims d) {
     }
     btw_lds_fence();
     if (a.trade_count && lane == 0) a.trade_count[s] = trades;
-    if (a.summary) btw_summary(geo, lane, px, a.bench, prm.initial_capital, trades, wins, a.summary + s * PQ_SUMMARY_COLS, true);
+    if (a.summary) btw_summary<1>(geo, lane, 0, px, a.bench, prm.initial_capital, trades, wins, a.summary + s * PQ_SUMMARY_COLS, nullptr, true);
 }
 
 // host side: shape of the wave form for a batch, or false when it does not apply (len > 64 * BTW_MAX_C)

@@ -21,6 +21,7 @@
 // the same deterministic state machine both times (walk 1: sum of returns, peak, drawdown, trades, wins; walk 2: the squared deviations
 // and the covariance in the same row order).  A one-pass sum of squares would cancel.  Only pow differs from the host.
 #include "../pq_dev.h"
+#include "../bt_core.h"
 #include "../wave_util.h"
 #include <vector>
 
@@ -72,11 +73,12 @@ struct SwRule { // a lane's parameter set: the LDS offsets of its columns (an un
     double k0, k1;
 };
 struct SwLane { // the scan's state (vectorized.rs:124-194) and the rule's row t - 1
-    double pa, pb, pc, pos, avail, entry_cost, prev_eq;
+    double pa, pb, pc, prev_eq;
+    BtPool pl;
     int32_t trades, wins;
     __device__ void reset(double capital) {
         pa = pb = pc = __longlong_as_double(0x7FF8000000000000LL); // row 0 never signals: a NaN (not the NULL) compares false
-        pos = 0.0; avail = capital; entry_cost = 0.0; prev_eq = capital; trades = 0; wins = 0;
+        pl.reset(capital); prev_eq = capital; trades = 0; wins = 0;
     }
 };
 struct SwAcc { // calculate_summary's running values (metrics.rs:21-67, :86-116)
@@ -181,35 +183,20 @@ __device__ __forceinline__ void sw_walk(const double *tile, int n, const SwRule 
         const double xc = sw_uses_c(RULE) ? tile[q.ic + c] : xa;
         bool buy, sell;
         sw_signal<RULE>(q, xa, xb, xc, st, buy, sell);
-        const bool do_buy = buy && st.pos == 0.0, do_sell = sell && st.pos > 0.0;
+        const bool do_buy = buy && st.pl.pos == 0.0, do_sell = sell && st.pl.pos > 0.0;
         if (px > 0.0 && (do_buy || do_sell)) { // a NaN (or NULL) or non-positive price leaves the state untouched (:141-144)
-            if (do_buy) {                      // :146-161
-                const double exec = px + prm.buy_slippage;
-                const double cur_eq = st.avail + st.pos * px;
-                const double deploy = cur_eq * prm.position_size;
-                const double qty = floor(deploy / exec);
-                if (qty > 0.0) {
-                    const double cost = qty * exec;
-                    const double fee = fmax(cost * prm.buy_commission_rate, prm.min_commission);
-                    st.pos += qty;
-                    st.avail -= cost + fee;
-                    st.entry_cost = st.pos * px;
-                    if (PASS == 1) st.trades += 1;
-                }
-            } else {                           // :162-175
-                const double exec = px - prm.sell_slippage;
-                const double revenue = st.pos * exec;
-                const double fee = fmax(revenue * prm.sell_commission_rate, prm.min_commission);
-                const double net = revenue - fee;
-                if (PASS == 1 && net > st.entry_cost) st.wins += 1;
-                st.avail += net;
-                st.pos = 0.0;
+            if (do_buy) {
+                const bool opened = bt_buy(st.pl, px, prm);
+                if (PASS == 1 && opened) st.trades += 1;
+            } else {
+                const bool win = bt_sell(st.pl, px, prm);
+                if (PASS == 1 && win) st.wins += 1;
             }
         }
-        const double eq = st.avail + st.pos * px; // :177, and :142 on an untouched row
-        const double r = (st.prev_eq > 0.0) ? (eq - st.prev_eq) / st.prev_eq : 0.0;
+        const double eq = st.pl.equity(px);
+        const double r = bt_ret(st.prev_eq, eq);
         st.prev_eq = eq;
-        if (PASS == 1) { // metrics.rs:26-49
+        if (PASS == 1) { // metrics.rs:26-49 (BtRun::add, with prev_eq among the lane's registers of both walks)
             if (eq > acc.max_eq) acc.max_eq = eq;
             const double dd = (acc.max_eq > 0.0) ? (acc.max_eq - eq) / acc.max_eq : 0.0;
             if (dd > acc.max_dd) acc.max_dd = dd;
@@ -246,18 +233,9 @@ __device__ __forceinline__ void sw_pass(const SwArgs &g, int64_t s, int64_t lo, 
     }
 }
 
-// RULE: the one rule of the whole table, or SW_GENERIC.  sweep_windows_kernel below holds a second copy of this body with a window's
-// lo / hi for 0 / len: a change to the lane set-up, the passes or the summary arithmetic here must be made there as well (the
-// bit-for-bit tests of tests/test_sweep_windows_gpu.py compare the two).
-template <int RULE, bool BENCH>
-__global__ __launch_bounds__(SW_BLOCK) void sweep_kernel(SwArgs g) {
-    extern __shared__ double sw_lds[];
-    const int tid = (int)threadIdx.x;
-    const int64_t s = (int64_t)(blockIdx.x / (unsigned)g.pblocks);
-    const int64_t p0 = (int64_t)(blockIdx.x % (unsigned)g.pblocks) * blockDim.x;
-    const int64_t p = p0 + tid;
-    const bool live = p < g.n_params;
-    const bool wave_live = p0 + (tid & ~63) < g.n_params; // a wavefront without a parameter set only helps with the staging
+// a lane's parameter set p of the table (a lane beyond the table walks a cross of column 0 with itself and writes nothing)
+template <int RULE>
+__device__ __forceinline__ SwRule sw_rule(const SwArgs &g, int64_t p, bool live) {
     SwRule q{0, 0, 0, RULE == SW_GENERIC ? PQ_SWEEP_RULE_CROSS : RULE, 0.0, 0.0};
     if (live) { // the rule and the columns it uses were checked against n_lines on the host before the launch
         const pq_sweep_rule in = g.params[p];
@@ -267,6 +245,30 @@ __global__ __launch_bounds__(SW_BLOCK) void sweep_kernel(SwArgs g) {
         q.ic = (RULE == SW_GENERIC ? sw_uses_c(in.rule) : sw_uses_c(RULE)) ? (in.c < 0 ? g.n_lines : in.c) * g.R : q.ia; // -1: the price row
         q.k0 = in.k0; q.k1 = in.k1;
     }
+    return q;
+}
+// the lane's eight values after both walks over the rows [lo, hi); a wavefront's 64 rows of `sm` are one contiguous 4 KB piece
+template <bool BENCH>
+__device__ __forceinline__ void sw_close(const SwArgs &g, int64_t s, int64_t lo, int64_t hi, double last_eq, int32_t trades, int32_t wins,
+                                         const SwAcc &acc, double *sm) {
+    const double *bm = g.bench + s * g.bench_stride;
+    bt_summary_close((double)(hi - lo), g.prm.initial_capital, last_eq, acc.max_dd, acc.vs, acc.bv, acc.cv, trades, wins, BENCH,
+                     BENCH ? bm[lo] : 0.0, BENCH ? bm[hi - 1] : 0.0, sm);
+}
+
+// RULE: the one rule of the whole table, or SW_GENERIC.  The lane set-up (sw_rule), the two walks (sw_pass) and the close (sw_close) are
+// shared with sweep_windows_kernel below; the two bodies that string them together stay apart (see there), and the bit-for-bit tests of
+// tests/test_sweep_windows_gpu.py compare the two.
+template <int RULE, bool BENCH>
+__global__ __launch_bounds__(SW_BLOCK) void sweep_kernel(SwArgs g) {
+    extern __shared__ double sw_lds[];
+    const int tid = (int)threadIdx.x;
+    const int64_t s = (int64_t)(blockIdx.x / (unsigned)g.pblocks);
+    const int64_t p0 = (int64_t)(blockIdx.x % (unsigned)g.pblocks) * blockDim.x;
+    const int64_t p = p0 + tid;
+    const bool live = p < g.n_params;
+    const bool wave_live = p0 + (tid & ~63) < g.n_params; // a wavefront without a parameter set only helps with the staging
+    const SwRule q = sw_rule<RULE>(g, p, live);
     const double capital = g.prm.initial_capital;
     SwLane st;
     SwAcc acc{};
@@ -288,26 +290,7 @@ __global__ __launch_bounds__(SW_BLOCK) void sweep_kernel(SwArgs g) {
     st.reset(capital);
     sw_pass<RULE, 2, BENCH>(g, s, 0, g.len, sw_lds, cur, wave_live, false, q, st, acc);
     if (!live) return;
-    const double DAYS = 252.0, RF = 0.03;
-    const double total_return = (last_eq - capital) / capital;                                                  // :52
-    const double ann = (total_return > -1.0) ? pow(1.0 + total_return, DAYS / T) - 1.0 : -1.0;                  // :54-58
-    const double dof = fmax(T - 1.0, 1.0);                                                                      // :61
-    const double vol = sqrt(acc.vs / dof) * sqrt(DAYS);                                                         // :69
-    const double sharpe = (vol > 0.0) ? (ann - RF) / vol : 0.0;                                                 // :71-75
-    const double win_rate = (trades > 0) ? (double)wins / (double)trades : 0.0;
-    double alpha = 0.0, beta = 0.0;
-    if (BENCH) {                                                                                                // :86-140
-        const double *bm = g.bench + s * g.bench_stride;
-        const double bvar = acc.bv / dof, cov = acc.cv / dof;
-        if (bvar > 0.0) beta = cov / bvar;
-        const double b0 = bm[0], b1 = bm[g.len - 1];
-        const double btr = (b0 > 0.0) ? (b1 - b0) / b0 : 0.0;
-        const double bann = (btr > -1.0) ? pow(1.0 + btr, DAYS / T) - 1.0 : -1.0;
-        alpha = ann - (RF + beta * (bann - RF));
-    }
-    double *sm = g.summary + (s * g.n_params + p) * PQ_SUMMARY_COLS; // a wavefront's 64 rows are one contiguous 4 KB piece
-    sm[0] = ann; sm[1] = acc.max_dd; sm[2] = alpha; sm[3] = beta; sm[4] = sharpe;
-    sm[5] = fmax(total_return, 0.0); sm[6] = win_rate; sm[7] = (double)trades;                                  // :142-149
+    sw_close<BENCH>(g, s, 0, g.len, last_eq, trades, wins, acc, g.summary + (s * g.n_params + p) * PQ_SUMMARY_COLS);
 }
 
 // D-26: the sweep with one more grid axis, the window.  Block ((w N + s) pblocks + pb) -- window-major, the order of the loop of sweeps
@@ -316,8 +299,8 @@ __global__ __launch_bounds__(SW_BLOCK) void sweep_kernel(SwArgs g) {
 // [t0_w, t1_w) exactly as sweep_kernel runs a series of that length: the
 // lane state and the rule's row t - 1 start afresh at t0 (row t0 never signals, row t0 - 1 is never read), T = t1 - t0, the benchmark
 // return of row t0 is taken against row t0, alpha spans bm[t0] .. bm[t1 - 1].  summary is [W][N][P][8]; an empty window's cells are 0
-// (metrics.rs:17-19).  The body below is sweep_kernel's with lo / hi for 0 / len, kept as a second copy: sweep_kernel written through
-// a shared body with lo = 0 is allocated ~25 more VGPRs by the compiler, and its figures are pinned (tests/test_sweep_rules_ref.py).
+// (metrics.rs:17-19).  Only the grid decode, the first tile and the order of the calls are written twice: sweep_kernel written through
+// one shared body with lo = 0 is allocated ~25 more VGPRs by the compiler, and its figures are pinned (tests/test_sweep_rules_ref.py).
 struct SwWinArgs {
     SwArgs g;
     const pq_sweep_window *windows; // device, [n_windows]; checked against len on the host
@@ -336,22 +319,12 @@ __global__ __launch_bounds__(SW_BLOCK) void sweep_windows_kernel(SwWinArgs a) {
     const int64_t p = p0 + tid;
     const bool live = p < g.n_params;
     if (win.t0 >= win.t1) {
-        if (live)
-#pragma unroll
-            for (int k = 0; k < PQ_SUMMARY_COLS; k++) sm_rows[p * PQ_SUMMARY_COLS + k] = 0.0;
+        if (live) bt_summary_zero(sm_rows + p * PQ_SUMMARY_COLS);
         return;
     }
     const int64_t lo = win.t0, hi = win.t1;
     const bool wave_live = p0 + (tid & ~63) < g.n_params; // a wavefront without a parameter set only helps with the staging
-    SwRule q{0, 0, 0, RULE == SW_GENERIC ? PQ_SWEEP_RULE_CROSS : RULE, 0.0, 0.0};
-    if (live) { // the rule and the columns it uses were checked against n_lines on the host before the launch
-        const pq_sweep_rule in = g.params[p];
-        if (RULE == SW_GENERIC) q.rule = in.rule;
-        q.ia = in.a * g.R;
-        q.ib = (RULE == SW_GENERIC ? sw_uses_b(in.rule) : sw_uses_b(RULE)) ? in.b * g.R : q.ia;
-        q.ic = (RULE == SW_GENERIC ? sw_uses_c(in.rule) : sw_uses_c(RULE)) ? (in.c < 0 ? g.n_lines : in.c) * g.R : q.ia; // -1: the price row
-        q.k0 = in.k0; q.k1 = in.k1;
-    }
+    const SwRule q = sw_rule<RULE>(g, p, live);
     const double capital = g.prm.initial_capital;
     SwLane st;
     SwAcc acc{};
@@ -373,26 +346,7 @@ __global__ __launch_bounds__(SW_BLOCK) void sweep_windows_kernel(SwWinArgs a) {
     st.reset(capital);
     sw_pass<RULE, 2, BENCH>(g, s, lo, hi, sw_lds, cur, wave_live, false, q, st, acc);
     if (!live) return;
-    const double DAYS = 252.0, RF = 0.03;
-    const double total_return = (last_eq - capital) / capital;                                                  // :52
-    const double ann = (total_return > -1.0) ? pow(1.0 + total_return, DAYS / T) - 1.0 : -1.0;                  // :54-58
-    const double dof = fmax(T - 1.0, 1.0);                                                                      // :61
-    const double vol = sqrt(acc.vs / dof) * sqrt(DAYS);                                                         // :69
-    const double sharpe = (vol > 0.0) ? (ann - RF) / vol : 0.0;                                                 // :71-75
-    const double win_rate = (trades > 0) ? (double)wins / (double)trades : 0.0;
-    double alpha = 0.0, beta = 0.0;
-    if (BENCH) {                                                                                                // :86-140
-        const double *bm = g.bench + s * g.bench_stride;
-        const double bvar = acc.bv / dof, cov = acc.cv / dof;
-        if (bvar > 0.0) beta = cov / bvar;
-        const double b0 = bm[lo], b1 = bm[hi - 1];
-        const double btr = (b0 > 0.0) ? (b1 - b0) / b0 : 0.0;
-        const double bann = (btr > -1.0) ? pow(1.0 + btr, DAYS / T) - 1.0 : -1.0;
-        alpha = ann - (RF + beta * (bann - RF));
-    }
-    double *sm = sm_rows + p * PQ_SUMMARY_COLS; // a wavefront's 64 rows are one contiguous 4 KB piece
-    sm[0] = ann; sm[1] = acc.max_dd; sm[2] = alpha; sm[3] = beta; sm[4] = sharpe;
-    sm[5] = fmax(total_return, 0.0); sm[6] = win_rate; sm[7] = (double)trades;                                  // :142-149
+    sw_close<BENCH>(g, s, lo, hi, last_eq, trades, wins, acc, sm_rows + p * PQ_SUMMARY_COLS);
 }
 
 // D-26, selection: one wavefront per (fold f, symbol s).  Lanes stride over the parameter sets of summary[train[f]][s] and keep their
