@@ -48,6 +48,118 @@ class SeqParams(C.Structure):
                                           "sell_commission_rate", "minimum_commission_fee")]
 
 
+# One line per entry point of include/pq_hip.h that _spec does not describe: name (without pq_), the kind of the return value, the kinds
+# of the parameters.  B / V / W / Q: const pq_batch / pq_bt_params / pq_lev_params / pq_seq_params *, s: const char *, p: any other
+# pointer, i: int32_t / pq_status, l: int64_t, u: uint32_t, d: double, z: size_t.  tests/test_abi_signatures.py holds every line (and the
+# derived ones) against the header.
+_KINDS = {"p": C.c_void_p, "B": C.POINTER(Batch), "V": C.POINTER(BtParams), "W": C.POINTER(LevParams), "Q": C.POINTER(SeqParams),
+          "s": C.c_char_p, "i": C.c_int32, "l": C.c_int64, "u": C.c_uint32, "d": C.c_double, "z": C.c_size_t}
+_SIGNATURES = """
+recommended_stride     l l
+layout_check           i Bpi
+abi_version            i
+last_error             s
+device_count           i p
+ctx_create             i ipp
+ctx_destroy            i p
+ctx_set_stream         i pp
+ctx_sync               i p
+malloc                 i pzp
+free                   i pp
+host_register          i pz
+host_unregister        i p
+memcpy_h2d             i pppz
+memcpy_d2h             i pppz
+memcpy_h2d_pitched     i ppzpzzz
+memcpy_d2h_pitched     i ppzpzzz
+nulls_from_arrow       i pppll
+validity_to_arrow      i pplpp
+count_nulls            i pBpp
+ema_all                i pBplpppp
+atr_all                i pBppplpp
+dm_pair                i pBpplpp
+ad_all                 i pBppppllpp
+macd_pair              i pBpllllpppppp
+dm_system_all          i pBppplppppppp
+sma_ma                 i pBplpp
+cmo_rsi                i pBplpp
+volume_all             i pBpppplllpppp
+sar_pair               i pBppddddddddddpp
+stoch_all              i pBppplllllllpppp
+apo_ppo                i pBplllpp
+aroon_all              i pBpplppp
+dmi_all                i pBppplppppp
+ht_all                 i pBppppppp
+pattern_name           s i
+pattern_id             i s
+cdl                    i pBippppdp
+cdl_all                i pBpppppp
+backtest_vectorized    i pBppppVpppp
+backtest_macd_cross    i pBplllVpppp
+macd_cross_signals     i pBplllpp
+backtest_wave_stats    i ppi
+wt_stats               i ppi
+ragged_rehouse_stats   i ppi
+comm_unique_id         i p
+comm_init              i piip
+comm_destroy           i p
+shard_range            i liipp
+gather_summaries       i pplp
+gather_summaries_begin i pplpi
+gather_summaries_end   i pi
+comm_sync              i p
+cross_signals          i pBpppp
+band_signals           i pBpddpp
+channel_signals        i pBpppipp
+gate_signals           i pBppiddpppp
+zscore                 i pBpppp
+scale_band             i pBpddpp
+volume_surge_signals   i pBpppdpp
+gap_signals            i pBpppddpp
+pattern_any_signals    i pBpipipp
+ma_stack_signals       i pBpipp
+backtest_leveraged     i pBppppWpppipppppppppp
+portfolio_metrics      i pBpdpp
+backtest_report        i pBpdpWippppppppp
+report_portfolio       i plppdp
+backtest_sequential    i pllipppplpQlppppp
+backtest_sweep         i pBppiplplVp
+sweep_row_tile         i i
+backtest_sweep_rules   i pBppiplplVp
+backtest_sweep_windows i pBppiplplplVp
+sweep_select           i pplllppliippp
+factor_ic              i pBppipp
+rolling_ic             i ppllpp
+factor_quantiles       i pBppipppppp
+factor_long_short      i pBppddpppppp
+factor_coverage        i pBpp
+ic_stats               i pplp
+factor_clean           i pBpidppiip
+xsec_regress           i pBpippppppp
+ts_regress             i pBpiupppppp
+corr_t_test            i ppplpp
+linear                 i pBpipppppppp
+factor_orthogonalize   i pBpiip
+ic_decay               i pBppiippp
+ic_subgroup            i pBpppliippp
+series_split_summary   i pplip
+factor_rank            i pBpiip
+factor_minmax          i pBpp
+factor_weighted        i pBppplip
+factor_binary          i pBppip
+factor_rolling         i pBpillp
+suite_begin            i pB
+suite_end              i pp
+suite_abort            i p
+suite_run              i pp
+suite_destroy          i pp
+suite_info             i pppp
+suite_set_timing       i pi
+suite_grid_stats       i pippppp
+suite_grid_variant     i pip
+suite_span_stats       i pipp
+"""
+
 _lib = None
 
 
@@ -59,146 +171,14 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} not found: the MI355X HIP library is not built. "
                 "Run `make -C polars_quant_amd/csrc` (hipcc --offload-arch=gfx950). There is no CPU fallback.")
         L = C.CDLL(str(LIB_PATH))
-        L.pq_last_error.restype = C.c_char_p
-        L.pq_pattern_name.restype = C.c_char_p
-        L.pq_pattern_name.argtypes = [C.c_int32]
-        L.pq_pattern_id.argtypes = [C.c_char_p]
-        vp = C.c_void_p
-        for name, (cols, params, outs, _fam) in {**SPEC, **EXTRA}.items():
+        sigs = [line.split() for line in _SIGNATURES.strip().splitlines()]
+        # an indicator: (ctx, batch, input columns, parameters, output columns) -> pq_status, from its _spec entry
+        sigs += [(name, "i", "pB" + "p" * len(cols) + "".join("l" if k == I else "d" for _, k, _ in params) + "p" * len(outs))
+                 for name, (cols, params, outs, _fam) in {**SPEC, **EXTRA}.items()]
+        for name, ret, *args in sigs:
             fn = getattr(L, "pq_" + name)
-            fn.restype = C.c_int32
-            fn.argtypes = [vp, C.POINTER(Batch)] + [vp] * len(cols) + \
-                          [C.c_int64 if k == I else C.c_double for _, k, _ in params] + [vp] * len(outs)
-        L.pq_dmi_all.restype = C.c_int32
-        L.pq_dmi_all.argtypes = [vp, C.POINTER(Batch), vp, vp, vp, C.c_int64, vp, vp, vp, vp, vp]
-        for nm, args in (("pq_ema_all", [vp, C.c_int64, vp, vp, vp, vp]), ("pq_atr_all", [vp, vp, vp, C.c_int64, vp, vp]),
-                         ("pq_dm_pair", [vp, vp, C.c_int64, vp, vp]), ("pq_ad_all", [vp, vp, vp, vp, C.c_int64, C.c_int64, vp, vp]),
-                         ("pq_macd_pair", [vp, C.c_int64, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, vp, vp, vp]),
-                         ("pq_apo_ppo", [vp, C.c_int64, C.c_int64, C.c_int64, vp, vp]),
-                         ("pq_stoch_all", [vp, vp, vp] + [C.c_int64] * 7 + [vp] * 4),
-                         ("pq_sar_pair", [vp, vp] + [C.c_double] * 10 + [vp, vp]),
-                         ("pq_dm_system_all", [vp, vp, vp, C.c_int64] + [vp] * 7), ("pq_cmo_rsi", [vp, C.c_int64, vp, vp]), ("pq_sma_ma", [vp, C.c_int64, vp, vp]),
-                         ("pq_volume_all", [vp, vp, vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, vp, vp])):
-            getattr(L, nm).restype = C.c_int32
-            getattr(L, nm).argtypes = [vp, C.POINTER(Batch)] + args
-        L.pq_aroon_all.restype = C.c_int32
-        L.pq_aroon_all.argtypes = [vp, C.POINTER(Batch), vp, vp, C.c_int64, vp, vp, vp]
-        L.pq_ht_all.restype = C.c_int32
-        L.pq_ht_all.argtypes = [vp, C.POINTER(Batch), vp, vp, vp, vp, vp, vp, vp]
-        L.pq_cdl.restype = C.c_int32
-        L.pq_cdl.argtypes = [vp, C.POINTER(Batch), C.c_int32, vp, vp, vp, vp, C.c_double, vp]
-        L.pq_cdl_all.restype = C.c_int32
-        L.pq_cdl_all.argtypes = [vp, C.POINTER(Batch), vp, vp, vp, vp, C.POINTER(C.c_double), C.POINTER(vp)]
-        L.pq_backtest_vectorized.restype = C.c_int32
-        L.pq_backtest_vectorized.argtypes = [vp, C.POINTER(Batch), vp, vp, vp, vp, C.POINTER(BtParams), vp, vp, vp, vp]
-        L.pq_backtest_macd_cross.restype = C.c_int32
-        L.pq_backtest_macd_cross.argtypes = [vp, C.POINTER(Batch), vp, C.c_int64, C.c_int64, C.c_int64,
-                                             C.POINTER(BtParams), vp, vp, vp, vp]
-        L.pq_comm_unique_id.restype = C.c_int32
-        L.pq_comm_unique_id.argtypes = [vp]
-        L.pq_comm_init.restype = C.c_int32
-        L.pq_comm_init.argtypes = [vp, C.c_int32, C.c_int32, vp]
-        L.pq_comm_destroy.restype = C.c_int32
-        L.pq_comm_destroy.argtypes = [vp]
-        L.pq_shard_range.restype = C.c_int32
-        L.pq_shard_range.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        L.pq_gather_summaries.restype = C.c_int32
-        L.pq_gather_summaries.argtypes = [vp, vp, C.c_int64, vp]
-        L.pq_gather_summaries_begin.restype = C.c_int32
-        L.pq_gather_summaries_begin.argtypes = [vp, vp, C.c_int64, vp, C.c_int32]
-        L.pq_gather_summaries_end.restype = C.c_int32
-        L.pq_gather_summaries_end.argtypes = [vp, C.c_int32]
-        L.pq_comm_sync.restype = C.c_int32
-        L.pq_comm_sync.argtypes = [vp]
-        L.pq_backtest_wave_stats.restype = C.c_int32
-        L.pq_backtest_wave_stats.argtypes = [vp, C.POINTER(C.c_int64), C.c_int32]
-        L.pq_wt_stats.restype = C.c_int32
-        L.pq_wt_stats.argtypes = [vp, C.POINTER(C.c_int64), C.c_int32]
-        L.pq_ragged_rehouse_stats.restype = C.c_int32
-        L.pq_ragged_rehouse_stats.argtypes = [vp, C.POINTER(C.c_int64), C.c_int32]
-        L.pq_macd_cross_signals.restype = C.c_int32
-        L.pq_macd_cross_signals.argtypes = [vp, C.POINTER(Batch), vp, C.c_int64, C.c_int64, C.c_int64, vp, vp]
-        L.pq_cross_signals.restype = C.c_int32
-        L.pq_cross_signals.argtypes = [vp, C.POINTER(Batch), vp, vp, vp, vp]
-        L.pq_band_signals.restype = C.c_int32
-        L.pq_band_signals.argtypes = [vp, C.POINTER(Batch), vp, C.c_double, C.c_double, vp, vp]
-        L.pq_channel_signals.restype = C.c_int32
-        L.pq_channel_signals.argtypes = [vp, C.POINTER(Batch), vp, vp, vp, C.c_int32, vp, vp]
-        L.pq_gate_signals.restype = C.c_int32
-        L.pq_gate_signals.argtypes = [vp, C.POINTER(Batch), vp, vp, C.c_int32, C.c_double, C.c_double, vp, vp, vp, vp]
-        L.pq_zscore.restype = C.c_int32
-        L.pq_zscore.argtypes = [vp, C.POINTER(Batch), vp, vp, vp, vp]
-        L.pq_scale_band.restype = C.c_int32
-        L.pq_scale_band.argtypes = [vp, C.POINTER(Batch), vp, C.c_double, C.c_double, vp, vp]
-        L.pq_volume_surge_signals.restype = C.c_int32
-        L.pq_volume_surge_signals.argtypes = [vp, C.POINTER(Batch), vp, vp, vp, C.c_double, vp, vp]
-        L.pq_gap_signals.restype = C.c_int32
-        L.pq_gap_signals.argtypes = [vp, C.POINTER(Batch), vp, vp, vp, C.c_double, C.c_double, vp, vp]
-        L.pq_pattern_any_signals.restype = C.c_int32
-        L.pq_pattern_any_signals.argtypes = [vp, C.POINTER(Batch), vp, C.c_int32, vp, C.c_int32, vp, vp]
-        L.pq_ma_stack_signals.restype = C.c_int32
-        L.pq_ma_stack_signals.argtypes = [vp, C.POINTER(Batch), vp, C.c_int32, vp, vp]
-        L.pq_factor_ic.restype = C.c_int32
-        L.pq_factor_ic.argtypes = [vp, C.POINTER(Batch), vp, vp, C.c_int32, vp, vp]
-        L.pq_factor_rolling.restype = C.c_int32
-        L.pq_factor_rolling.argtypes = [vp, C.POINTER(Batch), vp, C.c_int32, C.c_int64, C.c_int64, vp]
-        L.pq_linear.restype = C.c_int32
-        L.pq_linear.argtypes = [vp, C.POINTER(Batch), C.POINTER(vp), C.c_int32] + [vp] * 8
-        L.pq_rolling_ic.restype = C.c_int32
-        L.pq_rolling_ic.argtypes = [vp, vp, C.c_int64, C.c_int64, vp, vp]
-        L.pq_backtest_leveraged.restype = C.c_int32
-        L.pq_backtest_leveraged.argtypes = [vp, C.POINTER(Batch), vp, vp, vp, vp, C.POINTER(LevParams), vp, vp, vp, C.c_int32] + [vp] * 10
-        L.pq_portfolio_metrics.restype = C.c_int32
-        L.pq_portfolio_metrics.argtypes = [vp, C.POINTER(Batch), vp, C.c_double, vp, vp]
-        L.pq_backtest_report.restype = C.c_int32
-        L.pq_backtest_report.argtypes = [vp, C.POINTER(Batch), vp, C.c_double, vp, C.POINTER(LevParams), C.c_int32] + [vp] * 9
-        L.pq_report_portfolio.restype = C.c_int32
-        L.pq_report_portfolio.argtypes = [vp, C.c_int64, vp, vp, C.c_double, vp]
-        L.pq_backtest_sequential.restype = C.c_int32
-        L.pq_backtest_sequential.argtypes = [vp, C.c_int64, C.c_int64, C.c_int32, vp, vp, vp, vp, C.c_int64, vp, C.POINTER(SeqParams),
-                                             C.c_int64, vp, vp, vp, vp, vp]
-        L.pq_backtest_sweep.restype = C.c_int32
-        L.pq_backtest_sweep.argtypes = [vp, C.POINTER(Batch), vp, C.POINTER(vp), C.c_int32, vp, C.c_int64, vp, C.c_int64, C.POINTER(BtParams), vp]
-        L.pq_backtest_sweep_rules.restype = C.c_int32
-        L.pq_backtest_sweep_rules.argtypes = L.pq_backtest_sweep.argtypes
-        L.pq_backtest_sweep_windows.restype = C.c_int32
-        L.pq_backtest_sweep_windows.argtypes = [vp, C.POINTER(Batch), vp, C.POINTER(vp), C.c_int32, vp, C.c_int64, vp, C.c_int64, vp, C.c_int64,
-                                                C.POINTER(BtParams), vp]
-        L.pq_sweep_select.restype = C.c_int32
-        L.pq_sweep_select.argtypes = [vp, vp, C.c_int64, C.c_int64, C.c_int64, vp, vp, C.c_int64, C.c_int32, C.c_int32, vp, vp, vp]
-        L.pq_sweep_row_tile.restype = C.c_int32
-        L.pq_sweep_row_tile.argtypes = [C.c_int32]
-        L.pq_recommended_stride.restype = C.c_int64
-        L.pq_recommended_stride.argtypes = [C.c_int64]
-        L.pq_layout_check.restype = C.c_int32
-        L.pq_layout_check.argtypes = [C.POINTER(Batch), C.POINTER(vp), C.c_int32]
-        L.pq_ctx_create.argtypes = [C.c_int32, vp, C.POINTER(vp)]
-        L.pq_ctx_destroy.argtypes = [vp]
-        L.pq_ctx_set_stream.argtypes = [vp, vp]
-        L.pq_ctx_sync.argtypes = [vp]
-        L.pq_count_nulls.argtypes = [vp, C.POINTER(Batch), vp, C.POINTER(C.c_int64)]
-        L.pq_nulls_from_arrow.argtypes = [vp, vp, vp, C.c_int64, C.c_int64]
-        L.pq_validity_to_arrow.argtypes = [vp, vp, C.c_int64, vp, vp]
-        L.pq_malloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
-        L.pq_free.argtypes = [vp, vp]
-        L.pq_host_register.argtypes = [vp, C.c_size_t]
-        L.pq_host_unregister.argtypes = [vp]
-        L.pq_memcpy_h2d.argtypes = [vp, vp, vp, C.c_size_t]
-        L.pq_memcpy_d2h.argtypes = [vp, vp, vp, C.c_size_t]
-        L.pq_memcpy_h2d_pitched.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_size_t]
-        L.pq_memcpy_d2h_pitched.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_size_t, C.c_size_t]
-        L.pq_device_count.argtypes = [C.POINTER(C.c_int32)]
-        L.pq_suite_begin.argtypes = [vp, C.POINTER(Batch)]
-        L.pq_suite_end.argtypes = [vp, C.POINTER(vp)]
-        L.pq_suite_abort.argtypes = [vp]
-        L.pq_suite_run.argtypes = [vp, vp]
-        L.pq_suite_destroy.argtypes = [vp, vp]
-        L.pq_suite_info.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        L.pq_suite_set_timing.argtypes = [vp, C.c_int32]
-        L.pq_suite_grid_stats.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_int32),
-                                          C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-        L.pq_suite_grid_variant.argtypes = [vp, C.c_int32, C.POINTER(C.c_int32)]
-        L.pq_suite_span_stats.argtypes = [vp, C.c_int32, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+            fn.restype = _KINDS[ret]
+            fn.argtypes = [_KINDS[k] for k in "".join(args)]
         _lib = L
     return _lib
 

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import Batch, BtParams, NullsNotAllowed, PqError, check, lib
+from ._lib import Batch, BtParams, LevParams, NullsNotAllowed, PqError, SeqParams, check, lib
 from ._spec import BT_DEFAULTS, EXTRA, I, NB, PATTERN_NAMES, PATTERN_PEN_DEFAULT, SPEC, SUMMARY_KEYS
 
 NULL = np.array([_lib.NULL_BITS], dtype=np.uint64).view(np.float64)[0]
@@ -34,11 +34,67 @@ def ctx(device: int | None = None):
     key = (dev, stream)
     h = _ctx_cache.get(key)
     if h is None:
-        out = C.c_void_p()
-        check(lib().pq_ctx_create(dev, C.c_void_p(stream) if stream else None, C.byref(out)))
-        h = out
+        h = C.c_void_p()
+        _call("pq_ctx_create", None, dev, stream or None, C.byref(h))
         _ctx_cache[key] = h
     return h
+
+
+def _tensor_ptr(t):
+    return t.data_ptr() if t.numel() else None
+
+
+def _classify(t: type):
+    """how _marshal converts an argument of type t: a function of the argument, or None where it is passed as it is"""
+    if issubclass(t, torch.Tensor):
+        return _tensor_ptr
+    if issubclass(t, C.Structure):          # Batch and the parameter structs: the callee reads the caller's
+        return C.byref
+    if issubclass(t, np.ndarray):
+        return lambda a: a.ctypes.data
+    return None                             # numbers, None, context and suite handles, ctypes arrays and byref()s
+
+
+# _classify by exact type, filled as types are first seen (a dict lookup, not an isinstance chain: torch.Tensor's costs 0.5 us a miss)
+_convert = {t: _classify(t) for t in (int, float, type(None), C.c_void_p, Batch)}
+_Tensor = torch.Tensor
+
+
+def _marshal(args) -> list:
+    """the one rule by which the package hands values to the C ABI: None -> NULL; a tensor -> its data_ptr(), NULL when it has no
+    element; a numpy array -> its address; a Batch or parameter struct -> by reference; anything else (numbers, ctypes arrays and
+    byref()s, handles) as it is, for the entry point's argtypes to convert or refuse"""
+    out = []
+    for a in args:
+        t = type(a)
+        if t is _Tensor:                    # most arguments: _tensor_ptr without the call
+            out.append(a.data_ptr() if a.numel() else None)
+            continue
+        try:
+            conv = _convert[t]
+        except KeyError:
+            conv = _convert[t] = _classify(t)
+        out.append(a if conv is None else conv(a))
+    return out
+
+
+def _call(name: str, dev, *args, checked: bool = True):
+    """every C-ABI call of the package: the entry point `name` on _marshal(args), its status checked (checked=False: for one that
+    returns a value, which is returned as it is).  dev: the device of an entry point that takes a context -- it is made current and
+    the context of its current stream goes in front of args; None for one that takes none, or is handed one in args.  `args` stay
+    referenced until the call has returned.  A value that the declared signature refuses (a float for an int64_t) is a TypeError."""
+    try:
+        if dev is None:
+            r = getattr(lib(), name)(*_marshal(args))
+        else:
+            with torch.cuda.device(dev):
+                r = getattr(lib(), name)(ctx(dev.index), *_marshal(args))
+    except C.ArgumentError as e:
+        raise TypeError(f"{name}: {e}") from None
+    if not checked:
+        return r
+    if r:
+        check(r)
 
 
 class _Kind:
@@ -146,9 +202,13 @@ def _from_device(t: torch.Tensor, kind: int, squeeze: bool, name: str = ""):
     return arr
 
 
-def _batch_of(t: torch.Tensor) -> Batch:
+def _batch(t: torch.Tensor, dense: bool = False, lone_dense: bool = False) -> Batch:
+    """the Batch that describes an [N, T] tensor: its own row pitch; dense: T (the tensor was made contiguous).  A single series has no
+    pitch to keep: it passes its own where that is at least T, and T otherwise or with lone_dense (the library picks its 16-byte or
+    8-byte forms by this value, and each entry point keeps the one it always passed)"""
     n, T = t.shape
-    return Batch(n, T, t.stride(0) if n > 1 else max(T, t.stride(0) if t.stride(0) >= T else T))
+    s = t.stride(0)
+    return Batch(n, T, T if dense or (n <= 1 and (lone_dense or s < T)) else s)
 
 
 def _same_layout(ts):
@@ -169,9 +229,8 @@ def _same_layout(ts):
 
 def count_nulls(t: torch.Tensor) -> int:
     t2, _, _ = _to_device(t)
-    b = _batch_of(t2)
     n = C.c_int64(0)
-    check(lib().pq_count_nulls(ctx(t2.device.index), C.byref(b), C.c_void_p(t2.data_ptr()), C.byref(n)))
+    _call("pq_count_nulls", None, ctx(t2.device.index), _batch(t2), t2, C.byref(n))
     return n.value
 
 
@@ -186,7 +245,7 @@ def ragged_batch(offsets, device):
     longest = int((off[1:] - off[:-1]).max()) if n else 0
     total = int(off[-1])
     dev_off = off.to(device)
-    return Batch(n, longest, total, C.c_void_p(dev_off.data_ptr())), dev_off
+    return Batch(n, longest, total, dev_off.data_ptr()), dev_off
 
 
 def call(name: str, *inputs, check_nulls: bool = False, offsets=None, **params):
@@ -201,47 +260,31 @@ def call(name: str, *inputs, check_nulls: bool = False, offsets=None, **params):
     conv = [_to_device(x) for x in inputs]
     kind, squeeze = conv[0][1], conv[0][2]
     ts = _same_layout([c[0] for c in conv])
+    dev = ts[0].device
     if offsets is not None:
         if not squeeze:
             raise PqError("with offsets the inputs are long columns [rows]")
         ts = [t.contiguous() for t in ts]
-        dev = ts[0].device
-        b, keep = ragged_batch(offsets, dev)
+        b, _off = ragged_batch(offsets, dev)       # (_off: the device offsets the batch points at)
         if b.stride != ts[0].shape[1]:
             raise PqError(f"offsets end at row {b.stride} but the columns have {ts[0].shape[1]} rows")
-        pvals = []
-        for pname, k, default in pspec:
-            v = params.pop(pname, default)
-            pvals.append(C.c_int64(int(v)) if k == I else C.c_double(float(v)))
-        if params:
-            raise TypeError(f"{name}() got unexpected parameters {sorted(params)}")
-        res = [torch.empty((1, b.stride), dtype=torch.float64 if dt == "f8" else torch.int32, device=dev) for _, dt in outs]
-        with torch.cuda.device(dev):
-            if b.n_series and b.stride:
-                check(getattr(lib(), "pq_" + name)(ctx(dev.index), C.byref(b), *[C.c_void_p(t.data_ptr()) for t in ts], *pvals,
-                                                   *[C.c_void_p(r.data_ptr()) for r in res]))
-        del keep
-        return tuple(_from_device(r, kind, True, oname) for r, (oname, _) in zip(res, outs))
-    if fam == NB and (check_nulls or kind in (_Kind.ARROW, _Kind.POLARS)):
-        for t in ts:
-            if count_nulls(t):
-                raise NullsNotAllowed(f"{name}: input contains nulls (the reference's cont_slice() rejects them)")
-    dev = ts[0].device
-    n, T = ts[0].shape
-    b = Batch(n, T, ts[0].stride(0) if n > 1 else T)
+        shape, live = (1, b.stride), b.n_series and b.stride
+    else:
+        if fam == NB and (check_nulls or kind in (_Kind.ARROW, _Kind.POLARS)):
+            for t in ts:
+                if count_nulls(t):
+                    raise NullsNotAllowed(f"{name}: input contains nulls (the reference's cont_slice() rejects them)")
+        b = _batch(ts[0], lone_dense=True)
+        shape, live = tuple(ts[0].shape), b.n_series * b.len > 0   # an empty batch has no device storage to point at
     pvals = []
     for pname, k, default in pspec:
         v = params.pop(pname, default)
-        pvals.append(C.c_int64(int(v)) if k == I else C.c_double(float(v)))
+        pvals.append(int(v) if k == I else float(v))
     if params:
         raise TypeError(f"{name}() got unexpected parameters {sorted(params)}")
-    res = [torch.empty_strided((n, T), (b.stride, 1), dtype=torch.float64 if dt == "f8" else torch.int32, device=dev)
-           for _, dt in outs]
-    with torch.cuda.device(dev):
-        fn = getattr(lib(), "pq_" + name)
-        if n * T > 0:  # an empty batch has no device storage to point at
-            check(fn(ctx(dev.index), C.byref(b), *[C.c_void_p(t.data_ptr()) for t in ts], *pvals,
-                     *[C.c_void_p(r.data_ptr()) for r in res]))
+    res = [torch.empty_strided(shape, (b.stride, 1), dtype=torch.float64 if dt == "f8" else torch.int32, device=dev) for _, dt in outs]
+    if live:
+        _call("pq_" + name, dev, b, *ts, *pvals, *res)
     return tuple(_from_device(r, kind, squeeze, oname) for r, (oname, _) in zip(res, outs))
 
 
@@ -251,28 +294,22 @@ def cdl(name: str, open, high, low, close, penetration: float | None = None, off
     conv = [_to_device(x) for x in (open, high, low, close)]
     kind, squeeze = conv[0][1], conv[0][2]
     ts = _same_layout([c[0] for c in conv])
+    dev = ts[0].device
     if offsets is not None:
         ts = [t.contiguous() for t in ts]
-        dev = ts[0].device
-        b, keep = ragged_batch(offsets, dev)
+        b, _off = ragged_batch(offsets, dev)
         out = torch.zeros((1, b.stride), dtype=torch.int32, device=dev)
-        with torch.cuda.device(dev):
-            if b.n_series and b.stride:
-                check(lib().pq_cdl(ctx(dev.index), C.byref(b), pid, *[C.c_void_p(t.data_ptr()) for t in ts], C.c_double(pen),
-                                   C.c_void_p(out.data_ptr())))
-        del keep
-        return _from_device(out, kind, True, name)
-    if kind in (_Kind.ARROW, _Kind.POLARS):
-        for t in ts:
-            if count_nulls(t):
-                raise NullsNotAllowed(f"{name}: input contains nulls")
-    dev = ts[0].device
-    n, T = ts[0].shape
-    b = Batch(n, T, ts[0].stride(0) if n > 1 else T)
-    out = torch.empty_strided((n, T), (b.stride, 1), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        check(lib().pq_cdl(ctx(dev.index), C.byref(b), pid, *[C.c_void_p(t.data_ptr()) for t in ts], C.c_double(pen),
-                           C.c_void_p(out.data_ptr())))
+        squeeze, live = True, b.n_series and b.stride
+    else:
+        if kind in (_Kind.ARROW, _Kind.POLARS):
+            for t in ts:
+                if count_nulls(t):
+                    raise NullsNotAllowed(f"{name}: input contains nulls")
+        b = _batch(ts[0], lone_dense=True)
+        out = torch.empty_strided(tuple(ts[0].shape), (b.stride, 1), dtype=torch.int32, device=dev)
+        live = True
+    if live:
+        _call("pq_cdl", dev, b, pid, *ts, pen, out)
     return _from_device(out, kind, squeeze, name)
 
 
@@ -282,14 +319,12 @@ def cdl_all(open, high, low, close, penetrations: dict | None = None, names=None
     kind, squeeze = conv[0][1], conv[0][2]
     ts = _same_layout([c[0] for c in conv])
     dev = ts[0].device
-    n, T = ts[0].shape
-    b = Batch(n, T, ts[0].stride(0) if n > 1 else T)
+    b = _batch(ts[0], lone_dense=True)
     want = PATTERN_NAMES if names is None else list(names)
-    outs = {nm: torch.empty_strided((n, T), (b.stride, 1), dtype=torch.int32, device=dev) for nm in want}
+    outs = {nm: torch.empty_strided(tuple(ts[0].shape), (b.stride, 1), dtype=torch.int32, device=dev) for nm in want}
     pens = (C.c_double * 61)(*[(penetrations or {}).get(nm, PATTERN_PEN_DEFAULT[nm]) for nm in PATTERN_NAMES])
     ptrs = (C.c_void_p * 61)(*[outs[nm].data_ptr() if nm in outs else None for nm in PATTERN_NAMES])
-    with torch.cuda.device(dev):
-        check(lib().pq_cdl_all(ctx(dev.index), C.byref(b), *[C.c_void_p(t.data_ptr()) for t in ts], pens, ptrs))
+    _call("pq_cdl_all", dev, b, *ts, pens, ptrs)
     return {nm: _from_device(o, kind, squeeze, nm) for nm, o in outs.items()}
 
 
@@ -303,47 +338,38 @@ def backtest_vectorized(price, buy, sell, benchmark=None, want_curves: bool = Tr
     p = p.contiguous(); bu = bu.contiguous(); se = se.contiguous()
     dev = p.device
     n, T = p.shape
+    bm = None
     if offsets is not None:
-        b, keep = ragged_batch(offsets, dev)
+        b, _off = ragged_batch(offsets, dev)
         bm = _to_device(benchmark)[0].contiguous() if benchmark is not None else None
         for nm, t in (("buy", bu), ("sell", se), ("benchmark", bm)):
             if t is not None and t.shape != p.shape:
                 raise PqError(f"backtest_vectorized: `{nm}` must be a long column like `price`")
-        mk = lambda: torch.empty((1, b.stride), dtype=torch.float64, device=dev)
-        pos, cash, eq = (mk(), mk(), mk()) if want_curves else (None, None, None)
-        summ = torch.empty((b.n_series, 8), dtype=torch.float64, device=dev)
-        vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-        with torch.cuda.device(dev):
-            if b.n_series:
-                check(lib().pq_backtest_vectorized(ctx(dev.index), C.byref(b), vp(p), vp(bu), vp(se), vp(bm), C.byref(prm),
-                                                   vp(pos), vp(cash), vp(eq), vp(summ)))
-        del keep
-        f = lambda t, sq: _from_device(t, _Kind.TORCH if kind == _Kind.TORCH else _Kind.NUMPY, sq) if t is not None else None
-        return f(pos, True), f(cash, True), f(eq, True), f(summ, False)
-    # the kernel indexes every column as base + s * stride: all of them must be [N, T] like the prices
-    for nm, t in (("buy", bu), ("sell", se)):
-        if t.shape == (1, T) and n > 1:
-            raise PqError(f"backtest_vectorized: `{nm}` is one series but `price` has {n}; signals are per series ([N, T])")
-        if t.shape != (n, T):
-            raise PqError(f"backtest_vectorized: `{nm}` has shape {tuple(t.shape)}, expected {(n, T)}")
-    bm = None
-    if benchmark is not None:
-        bm = _to_device(benchmark)[0]
-        if bm.shape == (1, T) and n > 1:
-            bm = bm.expand(n, T)          # one benchmark series shared by all symbols (the reference is single-asset)
-        if bm.shape != (n, T):
-            raise PqError(f"backtest_vectorized: `benchmark` has shape {tuple(bm.shape)}, expected {(T,)} or {(n, T)}")
-        bm = bm.contiguous()
-    b = Batch(n, T, T)
-    mk = lambda: torch.empty((n, T), dtype=torch.float64, device=dev)
+        rows, sq, sq_summ, live = (1, b.stride), True, False, b.n_series
+    else:
+        # the kernel indexes every column as base + s * stride: all of them must be [N, T] like the prices
+        for nm, t in (("buy", bu), ("sell", se)):
+            if t.shape == (1, T) and n > 1:
+                raise PqError(f"backtest_vectorized: `{nm}` is one series but `price` has {n}; signals are per series ([N, T])")
+            if t.shape != (n, T):
+                raise PqError(f"backtest_vectorized: `{nm}` has shape {tuple(t.shape)}, expected {(n, T)}")
+        if benchmark is not None:
+            bm = _to_device(benchmark)[0]
+            if bm.shape == (1, T) and n > 1:
+                bm = bm.expand(n, T)          # one benchmark series shared by all symbols (the reference is single-asset)
+            if bm.shape != (n, T):
+                raise PqError(f"backtest_vectorized: `benchmark` has shape {tuple(bm.shape)}, expected {(T,)} or {(n, T)}")
+            bm = bm.contiguous()
+        b = _batch(p, dense=True)
+        rows, sq, sq_summ, live = (n, T), squeeze, squeeze, True
+    mk = lambda: torch.empty(rows, dtype=torch.float64, device=dev)
     pos, cash, eq = (mk(), mk(), mk()) if want_curves else (None, None, None)
-    summ = torch.empty((n, 8), dtype=torch.float64, device=dev)
-    vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    with torch.cuda.device(dev):
-        check(lib().pq_backtest_vectorized(ctx(dev.index), C.byref(b), vp(p), vp(bu), vp(se), vp(bm), C.byref(prm),
-                                           vp(pos), vp(cash), vp(eq), vp(summ)))
-    f = lambda t: _from_device(t, kind if kind != _Kind.ARROW and kind != _Kind.POLARS else _Kind.NUMPY, squeeze) if t is not None else None
-    return f(pos), f(cash), f(eq), f(summ)
+    summ = torch.empty((b.n_series, 8), dtype=torch.float64, device=dev)
+    if live:
+        _call("pq_backtest_vectorized", dev, b, p, bu, se, bm, prm, pos, cash, eq, summ)
+    k = kind if kind in (_Kind.TORCH, _Kind.NUMPY) else _Kind.NUMPY
+    f = lambda t, s: _from_device(t, k, s) if t is not None else None
+    return f(pos, sq), f(cash, sq), f(eq, sq), f(summ, sq_summ)
 
 
 def backtest_macd_cross(close, fastperiod=12, slowperiod=26, signalperiod=9, want_curves: bool = True, offsets=None, **kw):
@@ -353,52 +379,41 @@ def backtest_macd_cross(close, fastperiod=12, slowperiod=26, signalperiod=9, wan
     p, kind, squeeze = _to_device(close)
     p = p.contiguous()
     dev = p.device
-    n, T = p.shape
-    b = Batch(n, T, T)
-    keep = None
+    b = _batch(p, dense=True)
     if offsets is not None:
-        b, keep = ragged_batch(offsets, dev)
-        n = b.n_series
+        b, _off = ragged_batch(offsets, dev)
     mk = lambda: torch.empty(tuple(p.shape), dtype=torch.float64, device=dev)
     pos, cash, eq = (mk(), mk(), mk()) if want_curves else (None, None, None)
-    summ = torch.empty((n, 8), dtype=torch.float64, device=dev)
-    vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    with torch.cuda.device(dev):
-        if n:
-            check(lib().pq_backtest_macd_cross(ctx(dev.index), C.byref(b), vp(p), fastperiod, slowperiod, signalperiod,
-                                               C.byref(prm), vp(pos), vp(cash), vp(eq), vp(summ)))
-    del keep
+    summ = torch.empty((b.n_series, 8), dtype=torch.float64, device=dev)
+    if b.n_series:
+        _call("pq_backtest_macd_cross", dev, b, p, fastperiod, slowperiod, signalperiod, prm, pos, cash, eq, summ)
     f = lambda t, sq=squeeze: _from_device(t, kind if kind in (_Kind.TORCH, _Kind.NUMPY) else _Kind.NUMPY, sq) if t is not None else None
     return f(pos), f(cash), f(eq), f(summ, squeeze and offsets is None)
+
+
+def _stats(name: str, k: int, reset: bool, device):
+    """the k int64 counters of a pq_*_stats entry point since the last reset -> tuple; synchronises the stream"""
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    out = (C.c_int64 * k)()
+    _call(name, dev, out, 1 if reset else 0)
+    return tuple(int(v) for v in out)
 
 
 def backtest_wave_stats(reset: bool = False, device=None):
     """(symbols run by the wave-per-symbol backtest, speculative chunks that failed the bit test, chunk re-runs) since the last
     reset -- pq_backtest_wave_stats (csrc/ops_backtest_wave.h).  Synchronises the stream."""
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    out = (C.c_int64 * 3)()
-    with torch.cuda.device(dev):
-        check(lib().pq_backtest_wave_stats(ctx(dev.index), out, 1 if reset else 0))
-    return tuple(int(v) for v in out)
+    return _stats("pq_backtest_wave_stats", 3, reset, device)
 
 
 def ragged_rehouse_stats(reset: bool = False, device=None) -> int:
     """launches on a ragged batch that took the re-housed tiled path (pq_ragged_rehouse_stats) since the last reset"""
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    out = C.c_int64(0)
-    with torch.cuda.device(dev):
-        check(lib().pq_ragged_rehouse_stats(ctx(dev.index), C.byref(out), 1 if reset else 0))
-    return int(out.value)
+    return _stats("pq_ragged_rehouse_stats", 1, reset, device)[0]
 
 
 def wt_stats(reset: bool = False, device=None):
     """(symbols computed by the wave-per-symbol indicator kernels, speculative chunks that failed the bit test, chunk re-runs,
     symbols handed to the gated lane-per-symbol path) since the last reset -- pq_wt_stats (csrc/wt_dev.h).  Synchronises."""
-    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    out = (C.c_int64 * 4)()
-    with torch.cuda.device(dev):
-        check(lib().pq_wt_stats(ctx(dev.index), out, 1 if reset else 0))
-    return tuple(int(v) for v in out)
+    return _stats("pq_wt_stats", 4, reset, device)
 
 
 def factor_ic(factor, fwd_return, method: int = 0):
@@ -412,26 +427,19 @@ def factor_ic(factor, fwd_return, method: int = 0):
     n, T = f.shape
     ic = torch.empty(T, dtype=torch.float64, device=dev)
     nv = torch.zeros(T, dtype=torch.int32, device=dev)
-    b = Batch(n, T, T)
-    if T:
-        with torch.cuda.device(dev):
-            check(lib().pq_factor_ic(ctx(dev.index), C.byref(b), C.c_void_p(f.data_ptr()) if n else None,
-                                     C.c_void_p(r.data_ptr()) if n else None, int(method), C.c_void_p(ic.data_ptr()),
-                                     C.c_void_p(nv.data_ptr())) if n else 0)
-        if n == 0:
-            ic.fill_(float("nan"))
+    if T and n:
+        _call("pq_factor_ic", dev, _batch(f, dense=True), f, r, int(method), ic, nv)
+    elif T:
+        ic.fill_(float("nan"))
     return ic, nv
 
 
 def rolling_ic(ic, window: int):
     """D-12: rolling mean of the IC series and its information ratio -> (rolling_ic, rolling_ir) device tensors [T]"""
     t = _to_device(ic)[0].contiguous().reshape(-1)
-    dev = t.device
     ric, rir = torch.empty_like(t), torch.empty_like(t)
     if t.numel():
-        with torch.cuda.device(dev):
-            check(lib().pq_rolling_ic(ctx(dev.index), C.c_void_p(t.data_ptr()), t.numel(), int(window), C.c_void_p(ric.data_ptr()),
-                                      C.c_void_p(rir.data_ptr())))
+        _call("pq_rolling_ic", t.device, t, t.numel(), int(window), ric, rir)
     return ric, rir
 
 
@@ -441,7 +449,7 @@ def _xsec_inputs(cols):
     if any(t.shape != ts[0].shape for t in ts):
         raise ValueError("factor and fwd_return must have the same shape")
     ts = _same_layout(ts)
-    return ts, _batch_of(ts[0])
+    return ts, _batch(ts[0])
 
 
 def _factor_groups(fn_name, factor, fwd_return, n_groups, scalars, labels):
@@ -456,11 +464,7 @@ def _factor_groups(fn_name, factor, fwd_return, n_groups, scalars, labels):
         "summary": torch.empty((n_groups + 1, SUMMARY_COLS), dtype=torch.float64, device=dev),
     }
     lab = torch.empty((n, b.stride), dtype=torch.uint8, device=dev) if labels else None
-    vp = C.c_void_p
-    with torch.cuda.device(dev):
-        check(getattr(lib(), fn_name)(ctx(dev.index), C.byref(b), vp(f.data_ptr()) if n else None, vp(r.data_ptr()) if n else None,
-                                      *scalars, vp(lab.data_ptr()) if lab is not None and n else None,
-                                      *[vp(out[k].data_ptr()) for k in ("mean_return", "count", "turnover", "spread", "summary")]))
+    _call(fn_name, dev, b, f, r, *scalars, lab, *out.values())
     if lab is not None:
         out["labels"] = lab[:, :T]
     return out
@@ -474,14 +478,14 @@ def factor_quantiles(factor, fwd_return, n_quantiles: int = 5, labels: bool = Fa
     """D-15: per-day quantile sort of the factor (bucket 0 = lowest values, ties share a bucket) -> dict of device tensors:
     mean_return / count / turnover [Q, T], spread [T] (top - bottom bucket), summary [Q + 1, 5] (last row: the spread), and with
     labels=True labels uint8 [N, T] (LABEL_OUT outside the day's cross-section)"""
-    return _factor_groups("pq_factor_quantiles", factor, fwd_return, int(n_quantiles), [C.c_int32(int(n_quantiles))], labels)
+    return _factor_groups("pq_factor_quantiles", factor, fwd_return, int(n_quantiles), [int(n_quantiles)], labels)
 
 
 def factor_long_short(factor, fwd_return, top_pct: float = 0.2, bottom_pct: float = 0.2, labels: bool = False):
     """D-15: per-day long (top top_pct) and short (bottom bottom_pct) legs -> dict of device tensors: mean_return / count / turnover
     [2, T] (row 0 = short, row 1 = long), ls_return [T] = long - short, summary [3, 5], and with labels=True labels uint8 [N, T]
     (1 long, 0 short, LABEL_MID in neither leg, LABEL_OUT outside the day's cross-section)"""
-    out = _factor_groups("pq_factor_long_short", factor, fwd_return, 2, [C.c_double(float(top_pct)), C.c_double(float(bottom_pct))], labels)
+    out = _factor_groups("pq_factor_long_short", factor, fwd_return, 2, [float(top_pct), float(bottom_pct)], labels)
     out["ls_return"] = out.pop("spread")
     return out
 
@@ -489,28 +493,49 @@ def factor_long_short(factor, fwd_return, top_pct: float = 0.2, bottom_pct: floa
 def factor_coverage(factor):
     """D-15: share of the symbols with a non-null finite factor value, per day -> device tensor [T]"""
     (f,), b = _xsec_inputs([factor])
-    dev = f.device
-    n, T = f.shape
-    cov = torch.empty(T, dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        check(lib().pq_factor_coverage(ctx(dev.index), C.byref(b), C.c_void_p(f.data_ptr()) if n else None, C.c_void_p(cov.data_ptr())))
+    cov = torch.empty(f.shape[1], dtype=torch.float64, device=f.device)
+    _call("pq_factor_coverage", f.device, b, f, cov)
     return cov
 
 
 def ic_stats(ic):
     """D-15: statistics of an IC series over its non-null days -> device tensor [5]: n_days, mean, std, ir (mean / std), win_rate"""
     t = _to_device(ic)[0].contiguous().reshape(-1)
-    dev = t.device
-    out = torch.empty(5, dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        check(lib().pq_ic_stats(ctx(dev.index), C.c_void_p(t.data_ptr()) if t.numel() else None, C.c_int64(t.numel()),
-                                C.c_void_p(out.data_ptr())))
+    out = torch.empty(5, dtype=torch.float64, device=t.device)
+    _call("pq_ic_stats", t.device, t, t.numel(), out)
     return out
 
 
 CLEAN_WINSORIZE = {None: 0, "mad": 1, "sigma": 2, "percentile": 3}     # pq_factor_clean's winsorize codes
 CLEAN_WINSORIZE_N = {"mad": 3.0, "sigma": 3.0, "percentile": 1.0}    # the README's defaults
 MAX_INDUSTRIES = 256
+
+
+def _int_codes(codes, what):
+    """integer codes handed over as a tensor or an array -> tensor (where it is); floating point or boolean codes are refused"""
+    g = codes if isinstance(codes, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(codes)))
+    if g.dtype.is_floating_point or g.dtype.is_complex or g.dtype == torch.bool:
+        raise ValueError(f"{what} must hold integer codes")
+    return g
+
+
+def _n_codes(g, what, limit):
+    """max code + 1 of the codes g (at least 1), at most `limit`"""
+    G = int(g.max()) + 1 if g.numel() else 1
+    if G > limit:
+        raise ValueError(f"{what} codes must be < {limit} (negative = unclassified), got a code {G - 1}")
+    return max(G, 1)
+
+
+def _codes_on_pitch(codes, b, dev, spread: bool = False):
+    """integer codes [N] or [N, T] -> (int32 device tensor, its row pitch): [N, T] codes go onto the batch's row pitch; [N] codes stay
+    one per symbol (pitch 0), or with `spread` are written to every day of the symbol's row"""
+    g = codes.to(device=dev, dtype=torch.int32)
+    if g.dim() == 1 and not spread:
+        return g.contiguous(), 0
+    gp = torch.empty((b.n_series, b.stride), dtype=torch.int32, device=dev)
+    gp[:, :b.len] = g if g.dim() == 2 else g[:, None]
+    return gp, b.stride
 
 
 def _clean_args(winsorize, winsorize_n, industry):
@@ -523,16 +548,10 @@ def _clean_args(winsorize, winsorize_n, industry):
         raise ValueError(f"winsorize_n must be finite and >= 0 for {winsorize!r}, not {wn}")
     if winsorize == "percentile" and not (0.0 <= wn / 100.0 < 0.5):
         raise ValueError(f"percentile winsorize needs 0 <= winsorize_n < 50 (percent), not {wn}")
-    ind, G = None, 0
-    if industry is not None:
-        ind = industry if isinstance(industry, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(industry)))
-        if ind.dtype.is_floating_point or ind.dtype == torch.bool:
-            raise ValueError("industry must hold integer codes")
-        G = int(ind.max()) + 1 if ind.numel() else 1
-        if G > MAX_INDUSTRIES:
-            raise ValueError(f"industry codes must be < {MAX_INDUSTRIES} (negative = unclassified), got a code {G - 1}")
-        G = max(G, 1)
-    return mode, wn, ind, G
+    if industry is None:
+        return mode, wn, None, 0
+    ind = _int_codes(industry, "industry")
+    return mode, wn, ind, _n_codes(ind, "industry", MAX_INDUSTRIES)
 
 
 def factor_clean(factor, winsorize=None, winsorize_n=None, cap=None, log_cap: bool = True, industry=None, standardize: bool = False):
@@ -557,25 +576,17 @@ def factor_clean(factor, winsorize=None, winsorize_n=None, cap=None, log_cap: bo
         ts.append(z)
     ts = _same_layout(ts)
     f, z = ts[0], ts[1] if cap is not None else None
-    b = _batch_of(f)
+    b = _batch(f)
     dev = f.device
     ib = None
     if ind is not None:
-        ind = ind.to(device=dev, dtype=torch.int32)
-        if ind.dim() == 1:
-            ind = ind[:, None]
-        if ind.dim() != 2 or ind.shape[0] != n or ind.shape[1] not in (1, T):
-            raise ValueError(f"industry must be [N] or [N, T] with N = {n}, T = {T}, not {tuple(ind.shape)}")
-        ib = torch.empty((n, b.stride), dtype=torch.int32, device=dev)     # on the factor's row pitch
-        ib[:, :T] = ind
+        ish = tuple(ind.shape) + ((1,) if ind.dim() == 1 else ())
+        if len(ish) != 2 or ish[0] != n or ish[1] not in (1, T):
+            raise ValueError(f"industry must be [N] or [N, T] with N = {n}, T = {T}, not {ish}")
+        ib, _ = _codes_on_pitch(ind, b, dev, spread=True)
     out = torch.empty((n, b.stride), dtype=torch.float64, device=dev)
-    vp = C.c_void_p
-    with torch.cuda.device(dev):
-        check(lib().pq_factor_clean(ctx(dev.index), C.byref(b), vp(f.data_ptr()) if n else None, C.c_int32(mode), C.c_double(wn),
-                                    vp(z.data_ptr()) if z is not None and n else None, vp(ib.data_ptr()) if ib is not None and n else None,
-                                    C.c_int32(G), C.c_int32(1 if standardize else 0), vp(out.data_ptr()) if n else None))
+    _call("pq_factor_clean", dev, b, f, mode, wn, z, ib, G, 1 if standardize else 0, out)
     return out[:, :T]
-
 
 
 REGRESS_MAX_K = 8             # PQ_REGRESS_MAX_K
@@ -586,21 +597,28 @@ def _shape(x):
     return tuple(x.shape) if hasattr(x, "shape") else np.shape(x)
 
 
+def _columns(x, what, lo, hi, ndim=None, shapes="", exc=ValueError):
+    """a list / tuple of columns, or one stacked [K, ...] array of `ndim` dimensions (`shapes` words the refusal of another), holding
+    lo..hi columns (else exc: "`what` must be in lo..hi") -> the list of the columns"""
+    if isinstance(x, (list, tuple)):
+        cols = list(x)
+    else:
+        s = _shape(x)
+        if ndim is not None and len(s) != ndim:
+            raise ValueError(f"{shapes}, not {s}")
+        cols = [x[j] for j in range(s[0])]
+    if not lo <= len(cols) <= hi:
+        raise exc(f"{what} must be in {lo}..{hi}, not {len(cols)}")
+    return cols
+
+
 def _regress_args(factors, ret, series_ok):
     """argument checks of xsec_regress / ts_regress that need no device: factors a list / tuple of [N, T] (or, series_ok, [T]) arrays
     or one [K, N, T] array -> (list of factor columns, [N, T] of the return)"""
     rs = _shape(ret)
     if len(rs) != 2:
         raise ValueError(f"the return must be [N, T], not {rs}")
-    if isinstance(factors, (list, tuple)):
-        cols = list(factors)
-    else:
-        fs = _shape(factors)
-        if len(fs) != 3:
-            raise ValueError(f"factors must be a list of [N, T] arrays or one [K, N, T] array, not {fs}")
-        cols = [factors[j] for j in range(fs[0])]
-    if not 1 <= len(cols) <= REGRESS_MAX_K:
-        raise ValueError(f"the number of factors must be in 1..{REGRESS_MAX_K}, not {len(cols)}")
+    cols = _columns(factors, "the number of factors", 1, REGRESS_MAX_K, 3, "factors must be a list of [N, T] arrays or one [K, N, T] array")
     for j, c in enumerate(cols):
         cs = _shape(c)
         if cs != rs and not (series_ok and cs == rs[1:]):
@@ -615,19 +633,12 @@ def _regress_call(fn_name, cols, ret, series_ok, make_outs, extra):
     ser = [series_ok and len(_shape(c)) == 1 for c in cols]
     mats = _same_layout([_to_device(c)[0] for c, s in zip(cols, ser) if not s] + [_to_device(ret)[0]])
     r = mats[-1]
-    dev = r.device
-    n, T = r.shape
-    b = _batch_of(r)
     it = iter(mats[:-1])
     fs = [_to_device(c)[0].reshape(-1).contiguous() if s else next(it) for c, s in zip(cols, ser)]
     mask = sum(1 << j for j, s in enumerate(ser) if s)
-    vp = C.c_void_p
-    ptrs = (vp * len(fs))(*[f.data_ptr() for f in fs])
-    outs = make_outs(dev)
-    with torch.cuda.device(dev):
-        check(getattr(lib(), fn_name)(ctx(dev.index), C.byref(b), ptrs if n and T else None, C.c_int32(len(fs)), *extra(mask),
-                                      vp(r.data_ptr()) if n and T else None, *[vp(o.data_ptr()) if o is not None and o.numel() else None
-                                                                              for o in outs]))
+    ptrs = (C.c_void_p * len(fs))(*[f.data_ptr() for f in fs]) if r.numel() else None
+    outs = make_outs(r.device)
+    _call(fn_name, r.device, _batch(r), ptrs, len(fs), *extra(mask), r, *outs)
     return outs
 
 
@@ -662,7 +673,7 @@ def ts_regress(factors, returns):
         f64 = dict(dtype=torch.float64, device=dev)
         return [torch.empty((n, K + 1), **f64), torch.empty((n, K + 1), **f64), torch.empty((n, K + 1), **f64), torch.empty(n, **f64),
                 torch.empty(n, dtype=torch.int32, device=dev)]
-    coef, t, p, r2, nobs = _regress_call("pq_ts_regress", cols, returns, True, make, lambda mask: (C.c_uint32(mask),))
+    coef, t, p, r2, nobs = _regress_call("pq_ts_regress", cols, returns, True, make, lambda mask: (mask,))
     return {"coef": coef, "t_stat": t, "p_value": p, "r_squared": r2, "n_obs": nobs}
 
 
@@ -675,12 +686,8 @@ def corr_t_test(corr, n_valid):
     nv = nv.contiguous().reshape(-1)
     if nv.numel() != c.numel():
         raise ValueError(f"n_valid must have one count per correlation: {nv.numel()} vs {c.numel()}")
-    dev = c.device
     t, p = torch.empty_like(c), torch.empty_like(c)
-    vp = C.c_void_p
-    with torch.cuda.device(dev):
-        check(lib().pq_corr_t_test(ctx(dev.index), vp(c.data_ptr()) if c.numel() else None, vp(nv.data_ptr()) if c.numel() else None,
-                                   C.c_int64(c.numel()), vp(t.data_ptr()) if c.numel() else None, vp(p.data_ptr()) if c.numel() else None))
+    _call("pq_corr_t_test", c.device, c, nv, c.numel(), t, p)
     return t, p
 
 
@@ -695,15 +702,8 @@ def linear(xs, y, outputs: bool = True):
     ys = _shape(y)
     if len(ys) not in (1, 2):
         raise ValueError(f"y must be [M] or [N, T], not {ys}")
-    if isinstance(xs, (list, tuple)):
-        cols = list(xs)
-    else:
-        fs = _shape(xs)
-        if len(fs) != len(ys) + 1:
-            raise ValueError(f"xs must be a list of columns shaped like y or one [K, ...] array, not {fs}")
-        cols = [xs[j] for j in range(fs[0])]
-    if not 1 <= len(cols) <= REGRESS_MAX_K:
-        raise ValueError(f"the number of regressors must be in 1..{REGRESS_MAX_K}, not {len(cols)}")
+    cols = _columns(xs, "the number of regressors", 1, REGRESS_MAX_K, len(ys) + 1,
+                    "xs must be a list of columns shaped like y or one [K, ...] array")
     for j, c in enumerate(cols):
         if _shape(c) != ys:
             raise ValueError(f"x column {j} must have shape {ys}, not {_shape(c)}")
@@ -713,18 +713,13 @@ def linear(xs, y, outputs: bool = True):
         mats = _same_layout(mats)
     r = mats[-1]
     dev = r.device
-    n, T = r.shape
-    b = _batch_of(r)
-    vp = C.c_void_p
-    ptrs = (vp * K)(*[m.data_ptr() for m in mats[:-1]])
+    b = _batch(r)
+    ptrs = (C.c_void_p * K)(*[m.data_ptr() for m in mats[:-1]]) if r.numel() else None
     f64 = dict(dtype=torch.float64, device=dev)
     coef, t, p = (torch.empty(K + 1, **f64) for _ in range(3))
     r2, nobs = torch.empty((), **f64), torch.empty((), dtype=torch.int64, device=dev)
-    cols_out = [torch.empty_strided((n, T), (b.stride, 1), **f64) for _ in range(2)] if outputs else [None, None]
-    with torch.cuda.device(dev):
-        check(lib().pq_linear(ctx(dev.index), C.byref(b), ptrs if n and T else None, C.c_int32(K), vp(r.data_ptr()) if n and T else None,
-                              vp(coef.data_ptr()), vp(t.data_ptr()), vp(p.data_ptr()), vp(r2.data_ptr()), vp(nobs.data_ptr()),
-                              *[vp(o.data_ptr()) if o is not None and o.numel() else None for o in cols_out]))
+    cols_out = [torch.empty_strided(tuple(r.shape), (b.stride, 1), **f64) for _ in range(2)] if outputs else [None, None]
+    _call("pq_linear", dev, b, ptrs, K, r, coef, t, p, r2, nobs, *cols_out)
     out = {"coef": coef, "t_stat": t, "p_value": p, "r_squared": r2, "n": nobs}
     if outputs:
         out["pred"], out["resid"] = (o[0] if len(ys) == 1 else o for o in cols_out)
@@ -739,15 +734,7 @@ def _orth_args(factors, mode):
     shape or one [K, N, T] array -> (list of factor columns, (N, T))"""
     if mode not in (0, 1):
         raise ValueError(f"mode must be 0 (orthogonalize) or 1 (neutralize), not {mode!r}")
-    if isinstance(factors, (list, tuple)):
-        cols = list(factors)
-    else:
-        fs = _shape(factors)
-        if len(fs) != 3:
-            raise ValueError(f"factors must be a list of [N, T] arrays or one [K, N, T] array, not {fs}")
-        cols = [factors[j] for j in range(fs[0])]
-    if not 2 <= len(cols) <= REGRESS_MAX_K:
-        raise ValueError(f"the number of factors must be in 2..{REGRESS_MAX_K}, not {len(cols)}")
+    cols = _columns(factors, "the number of factors", 2, REGRESS_MAX_K, 3, "factors must be a list of [N, T] arrays or one [K, N, T] array")
     s0 = _shape(cols[0])
     if len(s0) != 2:
         raise ValueError(f"factor 0 must be [N, T], not {s0}")
@@ -774,7 +761,7 @@ def factor_orthogonalize(factors, mode: int = 0, out=None, keep_first: bool = Fa
         return torch.empty((K - 1 + (1 if keep_first else 0), n, T), dtype=torch.float64, device=dev)
     mats = _same_layout([_to_device(c)[0] for c in cols])
     dev = mats[0].device
-    b = _batch_of(mats[0])
+    b = _batch(mats[0])
     if out is None:
         lead = 1 if keep_first else 0
         buf = torch.empty((K - 1 + lead, n, b.stride), dtype=torch.float64, device=dev)[:, :, :T]
@@ -789,13 +776,9 @@ def factor_orthogonalize(factors, mode: int = 0, out=None, keep_first: bool = Fa
             if not (isinstance(o, torch.Tensor) and o.device == dev and o.dtype == torch.float64 and tuple(o.shape) == (n, T)
                     and (T <= 1 or o.stride(1) == 1) and (n <= 1 or o.stride(0) == b.stride)):
                 raise ValueError(f"out[{j}] must be a float64 [N, T] tensor on {dev} with row pitch {b.stride}")
-    vp = C.c_void_p
-    live = n > 0 and T > 0
-    fp = (vp * K)(*[m.data_ptr() for m in mats])
-    op = (vp * (K - 1))(*[o.data_ptr() for o in outs])
-    with torch.cuda.device(dev):
-        check(lib().pq_factor_orthogonalize(ctx(dev.index), C.byref(b), fp if live else None, C.c_int32(K), C.c_int32(mode),
-                                            op if live else None))
+    fp = (C.c_void_p * K)(*[m.data_ptr() for m in mats])
+    op = (C.c_void_p * (K - 1))(*[o.data_ptr() for o in outs])
+    _call("pq_factor_orthogonalize", dev, b, fp, K, int(mode), op)
     return res
 
 
@@ -818,14 +801,11 @@ def _ic_rows(fn_name, factor, fwd_return, V, args):
     """uploads factor / fwd_return onto one row pitch and runs a D-18 call that writes ic / n_valid [V, T] and summary [V, 5]"""
     (f, r), b = _xsec_inputs([factor, fwd_return])
     dev = f.device
-    n, T = f.shape
+    T = f.shape[1]
     ic = torch.empty((V, T), dtype=torch.float64, device=dev)
     nv = torch.empty((V, T), dtype=torch.int32, device=dev)
     summ = torch.empty((V, IC_SUMMARY_COLS), dtype=torch.float64, device=dev)
-    vp = C.c_void_p
-    with torch.cuda.device(dev):
-        check(getattr(lib(), fn_name)(ctx(dev.index), C.byref(b), vp(f.data_ptr()) if n and T else None, vp(r.data_ptr()) if n and T else None,
-                                      *args(b, dev), vp(ic.data_ptr()) if T else None, vp(nv.data_ptr()) if T else None, vp(summ.data_ptr())))
+    _call(fn_name, dev, b, f, r, *args(b, dev), ic, nv, summ)
     return {"ic": ic, "n_valid": nv, "summary": summ}
 
 
@@ -837,20 +817,15 @@ def ic_decay(factor, fwd_return, max_lag: int = 10, method: int = 0):
     if isinstance(max_lag, bool) or not isinstance(max_lag, (int, np.integer)) or not 1 <= max_lag <= IC_DECAY_MAX_LAG:
         raise ValueError(f"max_lag must be an integer in 1..{IC_DECAY_MAX_LAG}, not {max_lag!r}")
     L = int(max_lag)
-    return _ic_rows("pq_ic_decay", factor, fwd_return, L, lambda b, dev: (C.c_int32(method), C.c_int32(L)))
+    return _ic_rows("pq_ic_decay", factor, fwd_return, L, lambda b, dev: (int(method), L))
 
 
 def _group_codes(group, n, T):
     """argument checks of ic_subgroup that need no device: integer codes [N] or [N, T] (negative = unclassified) -> (codes, G)"""
-    g = group if isinstance(group, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(group)))
-    if g.dtype.is_floating_point or g.dtype.is_complex or g.dtype == torch.bool:
-        raise ValueError("group must hold integer codes")
+    g = _int_codes(group, "group")
     if tuple(g.shape) not in ((n,), (n, T)):
         raise ValueError(f"group must be [N] or [N, T] with N = {n}, T = {T}, not {tuple(g.shape)}")
-    G = int(g.max()) + 1 if g.numel() else 1
-    if G > IC_MAX_GROUPS:
-        raise ValueError(f"group codes must be < {IC_MAX_GROUPS} (negative = unclassified), got a code {G - 1}")
-    return g, max(G, 1)
+    return g, _n_codes(g, "group", IC_MAX_GROUPS)
 
 
 def ic_subgroup(factor, fwd_return, group, method: int = 0):
@@ -859,18 +834,7 @@ def ic_subgroup(factor, fwd_return, group, method: int = 0):
     std, t_stat, p_value).  method 0 Pearson IC, 1 Spearman Rank-IC"""
     n, T = _ic_pair_args(factor, fwd_return, method)
     g, G = _group_codes(group, n, T)
-
-    def args(b, dev):
-        gd = g.to(device=dev, dtype=torch.int32)
-        if gd.dim() == 2:       # onto the factor's row pitch
-            gp = torch.empty((n, b.stride), dtype=torch.int32, device=dev)
-            gp[:, :T] = gd
-            gd, gs = gp, b.stride
-        else:
-            gd, gs = gd.contiguous(), 0
-        args.keep = gd          # kept alive until the call has returned
-        return (C.c_void_p(gd.data_ptr()) if gd.numel() else None, C.c_int64(gs), C.c_int32(G), C.c_int32(method))
-    return _ic_rows("pq_ic_subgroup", factor, fwd_return, G, args)
+    return _ic_rows("pq_ic_subgroup", factor, fwd_return, G, lambda b, dev: (*_codes_on_pitch(g, b, dev), G, int(method)))
 
 
 RANK_MODES = {"rank": 0, "pct": 1, "quantile": 2}              # pq_factor_rank's mode codes
@@ -896,11 +860,7 @@ def _build_call(fn_name, cols, make_args):
     dev = ts[0].device
     n, T = ts[0].shape
     out = torch.empty((n, b.stride), dtype=torch.float64, device=dev)
-    vp = C.c_void_p
-    live = n > 0 and T > 0
-    with torch.cuda.device(dev):
-        check(getattr(lib(), fn_name)(ctx(dev.index), C.byref(b), *[vp(t.data_ptr()) if live else None for t in ts], *make_args(b, dev),
-                                      vp(out.data_ptr()) if live else None))
+    _call(fn_name, dev, b, *ts, *make_args(b, dev), out if T else None)
     return out[:, :T]
 
 
@@ -913,7 +873,7 @@ def factor_rank(factor, mode: int = 0, descending: bool = False):
     if mode == 2 and descending:
         raise ValueError("mode 2 (mid-rank position) is ascending only")
     _build_shapes(("factor",), (factor,))
-    return _build_call("pq_factor_rank", [factor], lambda b, dev: (C.c_int32(mode), C.c_int32(1 if descending else 0)))
+    return _build_call("pq_factor_rank", [factor], lambda b, dev: (int(mode), 1 if descending else 0))
 
 
 def factor_normalize(factor, method: str = "zscore"):
@@ -936,20 +896,8 @@ def factor_weighted(factor, weight, group=None):
     on that day -> device tensor [N, T], NULL outside the sample and where W == 0."""
     n, T = _build_shapes(("factor", "weight"), (factor, weight))
     g, G = _group_codes(group, n, T) if group is not None else (None, 0)
-
-    def args(b, dev):
-        if g is None:
-            return (None, C.c_int64(0), C.c_int32(0))
-        gd = g.to(device=dev, dtype=torch.int32)
-        if gd.dim() == 2:       # onto the factor's row pitch
-            gp = torch.empty((n, b.stride), dtype=torch.int32, device=dev)
-            gp[:, :T] = gd
-            gd, gs = gp, b.stride
-        else:
-            gd, gs = gd.contiguous(), 0
-        args.keep = gd          # kept alive until the call has returned
-        return (C.c_void_p(gd.data_ptr()) if gd.numel() else None, C.c_int64(gs), C.c_int32(G))
-    return _build_call("pq_factor_weighted", [factor, weight], args)
+    return _build_call("pq_factor_weighted", [factor, weight],
+                       lambda b, dev: (None, 0, 0) if g is None else (*_codes_on_pitch(g, b, dev), G))
 
 
 def factor_binary(a, b, op: int = 0):
@@ -958,7 +906,7 @@ def factor_binary(a, b, op: int = 0):
     if op not in (0, 1, 2):
         raise ValueError(f"op must be 0 (a / b), 1 (a - b) or 2 ((a - b) / |b|), not {op!r}")
     _build_shapes(("a", "b"), (a, b))
-    return _build_call("pq_factor_binary", [a, b], lambda bb, dev: (C.c_int32(op),))
+    return _build_call("pq_factor_binary", [a, b], lambda bb, dev: (int(op),))
 
 
 ROLLING_OPS = {"mean": 0, "momentum": 1, "volatility": 2, "skewness": 3, "relative_strength": 4}   # pq_factor_rolling's op codes
@@ -982,7 +930,7 @@ def factor_rolling(x, op: int, window: int, skip: int = 0):
     if skip < 0 or (skip != 0 and op != ROLLING_OPS["momentum"]):
         raise ValueError(f"skip must be >= 0, and 0 except for momentum, not {skip!r}")
     _build_shapes(("factor",), (x,))
-    return _build_call("pq_factor_rolling", [x], lambda b, dev: (C.c_int32(int(op)), C.c_int64(int(window)), C.c_int64(int(skip))))
+    return _build_call("pq_factor_rolling", [x], lambda b, dev: (int(op), int(window), int(skip)))
 
 
 def split_periods(T: int, n_splits: int):
@@ -1003,9 +951,7 @@ def series_split_summary(x, n_splits: int):
     split_periods(T, n_splits)
     t = _to_device(x)[0].contiguous().reshape(-1)
     out = torch.empty((int(n_splits), IC_SUMMARY_COLS), dtype=torch.float64, device=t.device)
-    with torch.cuda.device(t.device):
-        check(lib().pq_series_split_summary(ctx(t.device.index), C.c_void_p(t.data_ptr()), C.c_int64(T), C.c_int32(int(n_splits)),
-                                            C.c_void_p(out.data_ptr())))
+    _call("pq_series_split_summary", t.device, t, T, int(n_splits), out)
     return out
 
 
@@ -1016,13 +962,10 @@ def _signal_call(fn_name, cols, *scalars):
     for t in ts:
         if t.shape != (n, T):
             raise ValueError("signal rule inputs must have the same shape")
-    b = Batch(n, T, T)
     buy = torch.zeros((n, T), dtype=torch.uint8, device=dev)
     sell = torch.zeros((n, T), dtype=torch.uint8, device=dev)
     if n * T:
-        with torch.cuda.device(dev):
-            check(getattr(lib(), fn_name)(ctx(dev.index), C.byref(b), *[C.c_void_p(t.data_ptr()) for t in ts], *scalars,
-                                          C.c_void_p(buy.data_ptr()), C.c_void_p(sell.data_ptr())))
+        _call(fn_name, dev, _batch(ts[0], dense=True), *ts, *scalars, buy, sell)
     return buy, sell
 
 
@@ -1046,16 +989,14 @@ def _dev2(x, dtype=torch.float64):
 
 
 def _rule(fn_name, shape_like, args, outs, same=()):
-    """one of the strategy rule kernels (csrc/strategy.hip): args = ctypes values, outs = output tensors (returned); `same`:
-    the other tensor arguments, which must have shape_like's shape (the kernel indexes all of them with one batch)"""
+    """one of the strategy rule kernels (csrc/strategy.hip): args = the arguments between the batch and the outputs, outs = output
+    tensors (returned); `same`: the other tensor arguments, which must have shape_like's shape (the kernel indexes all of them with
+    one batch)"""
     for t in same:
         if t is not None and tuple(t.shape) != tuple(shape_like.shape):
             raise PqError(f"{fn_name}: input shapes differ: {tuple(t.shape)} vs {tuple(shape_like.shape)}")
-    n, T = shape_like.shape
-    b = Batch(n, T, T)
-    if n * T:
-        with torch.cuda.device(shape_like.device):
-            check(getattr(lib(), fn_name)(ctx(shape_like.device.index), C.byref(b), *args, *[C.c_void_p(o.data_ptr()) for o in outs]))
+    if shape_like.numel():
+        _call(fn_name, shape_like.device, _batch(shape_like, dense=True), *args, *outs)
     return outs
 
 
@@ -1064,19 +1005,17 @@ def gate_signals(buy, sell, a, mode: int, k0: float = 0.0, k1: float = 0.0, c=No
     a_, bu, se = _dev2(a), _dev2(buy, torch.uint8), _dev2(sell, torch.uint8)
     c_ = _dev2(c) if c is not None else None
     outs = [torch.empty_like(bu), torch.empty_like(se)]
-    return tuple(_rule("pq_gate_signals", a_, [C.c_void_p(a_.data_ptr()), C.c_void_p(c_.data_ptr()) if c_ is not None else None, int(mode),
-                                               C.c_double(float(k0)), C.c_double(float(k1)), C.c_void_p(bu.data_ptr()), C.c_void_p(se.data_ptr())], outs, same=(bu, se, c_)))
+    return tuple(_rule("pq_gate_signals", a_, [a_, c_, int(mode), float(k0), float(k1), bu, se], outs, same=(bu, se, c_)))
 
 
 def zscore(price, upper, mid):
     p, u, m = _dev2(price), _dev2(upper), _dev2(mid)
-    return _rule("pq_zscore", p, [C.c_void_p(t.data_ptr()) for t in (p, u, m)], [torch.empty_like(p)], same=(u, m))[0]
+    return _rule("pq_zscore", p, [p, u, m], [torch.empty_like(p)], same=(u, m))[0]
 
 
 def scale_band(base, f_lo: float, f_hi: float):
     b_ = _dev2(base)
-    return tuple(_rule("pq_scale_band", b_, [C.c_void_p(b_.data_ptr()), C.c_double(float(f_lo)), C.c_double(float(f_hi))],
-                       [torch.empty_like(b_), torch.empty_like(b_)]))
+    return tuple(_rule("pq_scale_band", b_, [b_, float(f_lo), float(f_hi)], [torch.empty_like(b_), torch.empty_like(b_)]))
 
 
 def _u8_pair(like):
@@ -1085,12 +1024,12 @@ def _u8_pair(like):
 
 def volume_surge_signals(volume, avg_volume, close, multiplier: float):
     v, sv, c = _dev2(volume), _dev2(avg_volume), _dev2(close)
-    return tuple(_rule("pq_volume_surge_signals", v, [C.c_void_p(t.data_ptr()) for t in (v, sv, c)] + [C.c_double(float(multiplier))], _u8_pair(v), same=(sv, c)))
+    return tuple(_rule("pq_volume_surge_signals", v, [v, sv, c, float(multiplier)], _u8_pair(v), same=(sv, c)))
 
 
 def gap_signals(open, high, low, f_up: float, f_dn: float):
     o, h, l = _dev2(open), _dev2(high), _dev2(low)
-    return tuple(_rule("pq_gap_signals", o, [C.c_void_p(t.data_ptr()) for t in (o, h, l)] + [C.c_double(float(f_up)), C.c_double(float(f_dn))], _u8_pair(o), same=(h, l)))
+    return tuple(_rule("pq_gap_signals", o, [o, h, l, float(f_up), float(f_dn)], _u8_pair(o), same=(h, l)))
 
 
 def pattern_any_signals(bullish, bearish):
@@ -1113,7 +1052,6 @@ def backtest_leveraged(price, buy, sell, benchmark=None, max_trades: int = 64, *
     """README `Backtest` engine (decision D-10): price/buy/sell [N, T], benchmark [T] or None.
     -> dict of device tensors: cash, stock_value, total_value [N,T]; trade_count [N]; trades {field: [N,max_trades]};
     summary [N,8]"""
-    from ._lib import LevParams
     from ._spec import LEV_DEFAULTS, TRADE_FIELDS
     prm = LevParams(**{**LEV_DEFAULTS, **kw})
     p, _, _ = _to_device(price)
@@ -1127,20 +1065,15 @@ def backtest_leveraged(price, buy, sell, benchmark=None, max_trades: int = 64, *
         bm = _to_device(benchmark)[0].contiguous().reshape(-1)
         if bm.numel() != T:
             raise ValueError("benchmark must be one series with as many rows as the prices")
-    b = Batch(n, T, T)
     mk = lambda: torch.empty((n, T), dtype=torch.float64, device=dev)
     cash, sv, tv = mk(), mk(), mk()
     cnt = torch.zeros(n, dtype=torch.int32, device=dev)
     tr = {k: torch.zeros((n, max_trades), dtype=torch.int32 if k in ("entry_day", "exit_day", "reason") else torch.float64, device=dev)
           for k in TRADE_FIELDS}
     summ = torch.empty((n, 8), dtype=torch.float64, device=dev)
-    vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
     if n * T:
-        with torch.cuda.device(dev):
-            check(lib().pq_backtest_leveraged(ctx(dev.index), C.byref(b), vp(p), vp(bu), vp(se), vp(bm), C.byref(prm), vp(cash), vp(sv),
-                                              vp(tv), max_trades, vp(cnt),
-                                              *[vp(tr[k]) if max_trades > 0 else None for k in ("entry_day", "exit_day", "entry_price", "exit_price",
-                                                                          "quantity", "pnl", "pnl_pct", "reason")], vp(summ)))
+        _call("pq_backtest_leveraged", dev, _batch(p, dense=True), p, bu, se, bm, prm, cash, sv, tv, max_trades, cnt,
+              *[tr[k] for k in ("entry_day", "exit_day", "entry_price", "exit_price", "quantity", "pnl", "pnl_pct", "reason")], summ)
     return dict(cash=cash, stock_value=sv, total_value=tv, trade_count=cnt, trades=tr, summary=summ)
 
 
@@ -1148,15 +1081,10 @@ def portfolio_metrics(total_value, initial_total: float, benchmark=None):
     """get_performance_metrics: total_value [N, T] -> [T, 10] device tensor (columns: _spec.PORTFOLIO_COLS + reserved)"""
     tv, _, _ = _to_device(total_value)
     tv = tv.contiguous()
-    dev = tv.device
-    n, T = tv.shape
     bm = _to_device(benchmark)[0].contiguous().reshape(-1) if benchmark is not None else None
-    out = torch.zeros((T, 10), dtype=torch.float64, device=dev)
-    b = Batch(n, T, T)
-    if n * T:
-        with torch.cuda.device(dev):
-            check(lib().pq_portfolio_metrics(ctx(dev.index), C.byref(b), C.c_void_p(tv.data_ptr()), float(initial_total),
-                                             C.c_void_p(bm.data_ptr()) if bm is not None else None, C.c_void_p(out.data_ptr())))
+    out = torch.zeros((tv.shape[1], 10), dtype=torch.float64, device=tv.device)
+    if tv.numel():
+        _call("pq_portfolio_metrics", tv.device, _batch(tv, dense=True), tv, float(initial_total), bm, out)
     return out
 
 
@@ -1190,7 +1118,6 @@ def backtest_report(total_value, initial_capital: float, benchmark=None, trades=
     with the fields _spec.REPORT_TRADE_FIELDS (further fields are ignored) and trade_count [N], as backtest_leveraged returns them;
     max_trades = 0 takes the records' width.  lev_params: the engine's commission_rate / min_commission (and the rest of its parameters).
     -> device [N, 48] f64, columns _spec.REPORT_COLS; a missing value is NULL.  Every check raises ValueError before any device work."""
-    from ._lib import LevParams
     from ._spec import LEV_DEFAULTS, REPORT_COLS, REPORT_TRADE_FIELDS
     n, T = _rp_meta(total_value, "total_value", 2)
     if T < 1:
@@ -1237,11 +1164,7 @@ def backtest_report(total_value, initial_capital: float, benchmark=None, trades=
     if trades is not None and width > 0:
         rec = [_rp_dev(trades[k], torch.int32 if k in ("entry_day", "exit_day", "reason") else torch.float64, dev).contiguous()
                for k in REPORT_TRADE_FIELDS]
-    vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
-    b = Batch(n, T, tv.stride(0) if n > 1 else T)
-    with torch.cuda.device(dev):
-        check(lib().pq_backtest_report(ctx(dev.index), C.byref(b), vp(tv), c0, vp(bm), C.byref(prm), int(width), vp(cnt),
-                                       *[vp(t) for t in rec], vp(out)))
+    _call("pq_backtest_report", dev, _batch(tv, lone_dense=True), tv, c0, bm, prm, int(width), cnt, *rec, out)
     return out
 
 
@@ -1263,9 +1186,7 @@ def report_portfolio(report, curve_row, initial_capital: float):
     dev = rep.device
     cur = _rp_dev(curve_row, torch.float64, dev).reshape(-1).contiguous()
     out = torch.zeros(ncol, dtype=torch.float64, device=dev)
-    with torch.cuda.device(dev):
-        check(lib().pq_report_portfolio(ctx(dev.index), shape[0], C.c_void_p(rep.data_ptr()), C.c_void_p(cur.data_ptr()), c0,
-                                        C.c_void_p(out.data_ptr())))
+    _call("pq_report_portfolio", dev, shape[0], rep, cur, c0, out)
     return out
 
 
@@ -1277,7 +1198,6 @@ def backtest_sequential(period_offsets, asset, quantity, price, n_assets: int, b
     -> dict of device tensors: equity, cash [B, T]; position [B, A]; counts [B, 2] int64 (trades, wins); summary [B, 8].
     T = 0 launches nothing.  Shape checks raise ValueError before any device work; n_assets above 6144 (PQ_SEQ_MAX_ASSETS) is the
     library's argument error (PqError)."""
-    from ._lib import SeqParams
     from ._spec import SEQ_DEFAULTS
     shape = tuple(period_offsets.shape) if isinstance(period_offsets, torch.Tensor) else np.shape(period_offsets)
     if len(shape) == 1:
@@ -1318,25 +1238,17 @@ def backtest_sequential(period_offsets, asset, quantity, price, n_assets: int, b
         elif tuple(t.shape) != shp or t.dtype != dt or not t.is_contiguous() or t.device != dev:
             raise ValueError(f"out[{k!r}] must be a contiguous {dt} tensor of shape {shp} on {dev}")
         r[k] = t
-    vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
     if B and T:
-        with torch.cuda.device(dev):
-            check(lib().pq_backtest_sequential(ctx(dev.index), B, T, A, vp(off), vp(a), vp(q), vp(px), n_orders, vp(bm), prm, len(plist),
-                                               vp(r["equity"]), vp(r["cash"]), vp(r["position"]), vp(r["counts"]), vp(r["summary"])))
+        _call("pq_backtest_sequential", dev, B, T, A, off, a, q, px, n_orders, bm, prm, len(plist), *r.values())
     return r
 
 
 def macd_cross_signals(close, fastperiod=12, slowperiod=26, signalperiod=9):
     p, kind, squeeze = _to_device(close)
     p = p.contiguous()
-    dev = p.device
-    n, T = p.shape
-    b = Batch(n, T, T)
-    bu = torch.empty((n, T), dtype=torch.uint8, device=dev)
-    se = torch.empty((n, T), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        check(lib().pq_macd_cross_signals(ctx(dev.index), C.byref(b), C.c_void_p(p.data_ptr()), fastperiod, slowperiod,
-                                          signalperiod, C.c_void_p(bu.data_ptr()), C.c_void_p(se.data_ptr())))
+    bu = torch.empty(tuple(p.shape), dtype=torch.uint8, device=p.device)
+    se = torch.empty(tuple(p.shape), dtype=torch.uint8, device=p.device)
+    _call("pq_macd_cross_signals", p.device, _batch(p, dense=True), p, fastperiod, slowperiod, signalperiod, bu, se)
     k = kind if kind in (_Kind.TORCH, _Kind.NUMPY) else _Kind.NUMPY
     return _from_device(bu, k, squeeze), _from_device(se, k, squeeze)
 
@@ -1348,25 +1260,30 @@ SWEEP_MAX_LINES = 512
 
 def SWEEP_ROW_TILE(n_lines: int) -> int:
     """pq_sweep_row_tile: the rows of one LDS tile of the sweep kernel for n_lines lines (0: n_lines is out of range)"""
-    return int(lib().pq_sweep_row_tile(int(n_lines)))
+    return int(_call("pq_sweep_row_tile", None, int(n_lines), checked=False))
 
 
-def sweep_params(rules) -> np.ndarray:
-    """a SWEEP_PARAM_DTYPE array from one, or from a dict of equally long rule / a / b / k0 / k1 columns (missing ones are 0)"""
-    if isinstance(rules, np.ndarray) and rules.dtype == SWEEP_PARAM_DTYPE:
+def _rule_table(rules, dtype, dtype_name):
+    """a `dtype` record array from one, or from a dict of equally long columns under its field names (missing ones are 0)"""
+    if isinstance(rules, np.ndarray) and rules.dtype == dtype:
         return np.ascontiguousarray(rules.reshape(-1))
     if not isinstance(rules, dict) or "rule" not in rules or "a" not in rules:
-        raise ValueError("rules must be a SWEEP_PARAM_DTYPE array or a dict with at least the columns 'rule' and 'a'")
-    unknown = set(rules) - {"rule", "a", "b", "k0", "k1"}
+        raise ValueError(f"rules must be a {dtype_name} array or a dict with at least the columns 'rule' and 'a'")
+    unknown = set(rules) - (set(dtype.names) - {"_pad"})
     if unknown:
         raise ValueError(f"unknown rule columns {sorted(unknown)}")
-    out = np.zeros(len(np.atleast_1d(rules["rule"])), dtype=SWEEP_PARAM_DTYPE)
+    out = np.zeros(len(np.atleast_1d(rules["rule"])), dtype=dtype)
     for k, v in rules.items():
         v = np.atleast_1d(np.asarray(v))
         if v.shape != out.shape:
             raise ValueError(f"rule column {k!r} has shape {v.shape}, expected {out.shape}")
         out[k] = v
     return out
+
+
+def sweep_params(rules) -> np.ndarray:
+    """a SWEEP_PARAM_DTYPE array from one, or from a dict of equally long rule / a / b / k0 / k1 columns (missing ones are 0)"""
+    return _rule_table(rules, SWEEP_PARAM_DTYPE, "SWEEP_PARAM_DTYPE")
 
 
 def sweep_windows(windows) -> np.ndarray:
@@ -1383,17 +1300,14 @@ def _backtest_sweep(who, entry, tab, price, lines, benchmark, out, offsets, kw, 
     """pq_backtest_sweep and pq_backtest_sweep_rules take the same arguments: `entry` is the one to call, `tab` its 32-byte table.
     windows (D-26): a sweep_windows table, which goes to pq_backtest_sweep_windows instead (either table is the same 32 bytes)"""
     prm = BtParams(**{**BT_DEFAULTS, **kw})
-    cols = list(lines) if isinstance(lines, (list, tuple)) else [lines[j] for j in range(_shape(lines)[0])]
-    if not 1 <= len(cols) <= SWEEP_MAX_LINES:
-        raise PqError(f"{who}: the number of lines must be in 1..{SWEEP_MAX_LINES}, not {len(cols)}")
+    cols = _columns(lines, f"{who}: the number of lines", 1, SWEEP_MAX_LINES, exc=PqError)
     mats = _same_layout([_to_device(price)[0]] + [_to_device(c)[0] for c in cols])
     p = mats[0]
     dev = p.device
     n, T = p.shape
-    b = _batch_of(p)
-    keep = None
+    b = _batch(p)
     if offsets is not None:
-        b, keep = ragged_batch(offsets, dev)
+        b, _off = ragged_batch(offsets, dev)
     P = len(tab)
     bm, bstride = None, 0
     if benchmark is not None:
@@ -1412,16 +1326,12 @@ def _backtest_sweep(who, entry, tab, price, lines, benchmark, out, offsets, kw, 
         raise ValueError(f"out must be a contiguous float64 tensor of shape {shape} on {dev}")
     if n and P and (win is None or len(win)):
         dtab = torch.from_numpy(tab.view(np.uint8).reshape(P, tab.dtype.itemsize)).to(dev)
-        vp = C.c_void_p
-        ptrs = (vp * len(cols))(*[m.data_ptr() for m in mats[1:]])
-        head = (ctx(dev.index), C.byref(b), vp(p.data_ptr()), ptrs, C.c_int32(len(cols)), vp(dtab.data_ptr()), C.c_int64(P))
-        tail = (vp(bm.data_ptr()) if bm is not None else None, C.c_int64(bstride), C.byref(prm), vp(out.data_ptr()))
-        with torch.cuda.device(dev):
-            if win is None:
-                check(getattr(lib(), entry)(*head, *tail))
-            else:
-                check(lib().pq_backtest_sweep_windows(*head, vp(win.ctypes.data), C.c_int64(len(win)), *tail))
-    del keep
+        ptrs = (C.c_void_p * len(cols))(*[m.data_ptr() for m in mats[1:]])
+        head, tail = (b, p, ptrs, len(cols), dtab, P), (bm, bstride, prm, out)
+        if win is None:
+            _call(entry, dev, *head, *tail)
+        else:
+            _call("pq_backtest_sweep_windows", dev, *head, win, len(win), *tail)
     return out.permute(1, 0, 2) if win is None else out.permute(0, 2, 1, 3)
 
 
@@ -1449,20 +1359,7 @@ SWEEP_RULE_DTYPE = np.dtype([("rule", "<i4"), ("a", "<i4"), ("b", "<i4"), ("c", 
 
 def sweep_rules(rules) -> np.ndarray:
     """a SWEEP_RULE_DTYPE array from one, or from a dict of equally long rule / a / b / c / k0 / k1 columns (missing ones are 0)"""
-    if isinstance(rules, np.ndarray) and rules.dtype == SWEEP_RULE_DTYPE:
-        return np.ascontiguousarray(rules.reshape(-1))
-    if not isinstance(rules, dict) or "rule" not in rules or "a" not in rules:
-        raise ValueError("rules must be a SWEEP_RULE_DTYPE array or a dict with at least the columns 'rule' and 'a'")
-    unknown = set(rules) - set(SWEEP_RULE_DTYPE.names)
-    if unknown:
-        raise ValueError(f"unknown rule columns {sorted(unknown)}")
-    out = np.zeros(len(np.atleast_1d(rules["rule"])), dtype=SWEEP_RULE_DTYPE)
-    for k, v in rules.items():
-        v = np.atleast_1d(np.asarray(v))
-        if v.shape != out.shape:
-            raise ValueError(f"rule column {k!r} has shape {v.shape}, expected {out.shape}")
-        out[k] = v
-    return out
+    return _rule_table(rules, SWEEP_RULE_DTYPE, "SWEEP_RULE_DTYPE")
 
 
 def backtest_sweep_rules(price, lines, rules, benchmark=None, out=None, windows=None, **kw):
@@ -1493,9 +1390,5 @@ def sweep_select(summary, train, test, metric, maximize=True):
     dev = base.device
     chosen = torch.empty((F, n), dtype=torch.int32, device=dev)
     ins, outs = (torch.empty((F, n, 8), dtype=torch.float64, device=dev) for _ in range(2))
-    vp = C.c_void_p
-    with torch.cuda.device(dev):
-        check(lib().pq_sweep_select(ctx(dev.index), vp(base.data_ptr()), C.c_int64(W), C.c_int64(n), C.c_int64(P), vp(tr.ctypes.data),
-                                    vp(te.ctypes.data), C.c_int64(F), C.c_int32(int(col)), C.c_int32(1 if maximize else 0),
-                                    vp(chosen.data_ptr()), vp(ins.data_ptr()), vp(outs.data_ptr())))
+    _call("pq_sweep_select", dev, base, W, n, P, tr, te, F, int(col), 1 if maximize else 0, chosen, ins, outs)
     return chosen, ins, outs

@@ -98,15 +98,14 @@ class CabiComm:
         import ctypes as C
 
         from . import api
-        from ._lib import check, lib
-        self._C, self._check, self._lib = C, check, lib()
+        self._api_call = api._call
         self.device = torch.device(device)
         self.h = api.ctx(self.device.index)
         self.stream = torch.cuda.current_stream(self.device)   # the communicator lives on this context = this stream
         idbuf = torch.zeros(129, dtype=torch.uint8)   # [ok flag, 128 id bytes]: every rank learns whether rank 0 could make the id
         if rank == 0:
             raw = (C.c_ubyte * 128)()
-            if self._lib.pq_comm_unique_id(raw) == 0:
+            if api._call("pq_comm_unique_id", None, raw, checked=False) == 0:
                 idbuf = torch.tensor([1] + list(raw), dtype=torch.uint8)
         if world > 1:
             on = idbuf.to(self.device) if dist.get_backend(group) == "nccl" else idbuf
@@ -116,12 +115,15 @@ class CabiComm:
             raise RuntimeError("pq_comm_unique_id failed on rank 0 (is RCCL loadable?)")
         idbuf = idbuf[1:]
         raw = (C.c_ubyte * 128)(*idbuf.tolist())
-        with torch.cuda.device(self.device):
-            check(self._lib.pq_comm_init(self.h, rank, world, raw))
+        self._call("pq_comm_init", rank, world, raw)
         self.rank, self.world = rank, world
 
+    def _call(self, name: str, *args) -> None:
+        """a C-ABI call on the communicator's context (the one of the stream it was made on), with its device current"""
+        with torch.cuda.device(self.device):
+            self._api_call(name, None, self.h, *args)
+
     def gather_summaries(self, local: torch.Tensor, n_symbols: int) -> torch.Tensor:
-        C = self._C
         lo, hi = shard_range(n_symbols, self.rank, self.world)
         if local.shape[0] != hi - lo:
             raise ValueError(f"rank {self.rank} of {self.world} owns {hi - lo} of {n_symbols} symbols, got {local.shape[0]} summary rows")
@@ -131,8 +133,7 @@ class CabiComm:
         if cur != self.stream:        # the collective runs on the communicator's stream: order it behind the producer of `local` ...
             self.stream.wait_stream(cur)
             out.record_stream(self.stream); loc.record_stream(self.stream)
-        with torch.cuda.device(self.device):
-            self._check(self._lib.pq_gather_summaries(self.h, C.c_void_p(loc.data_ptr()), n_symbols, C.c_void_p(out.data_ptr())))
+        self._call("pq_gather_summaries", loc, n_symbols, out)
         if cur != self.stream:        # ... and the consumers of `out` behind the collective
             cur.wait_stream(self.stream)
         return out
@@ -140,28 +141,24 @@ class CabiComm:
     def gather_begin(self, local: torch.Tensor, n_symbols: int, out: torch.Tensor, slot: int) -> None:
         """pq_gather_summaries_begin: the exchange of `local` ([n_local, 8], contiguous, written by work already enqueued on the
         context's stream) into `out` ([n_symbols, 8]) on the communicator's own stream; returns at once"""
-        C = self._C
         lo, hi = shard_range(n_symbols, self.rank, self.world)
         if local.shape[0] != hi - lo or not local.is_contiguous() or not out.is_contiguous() or out.shape[0] != n_symbols:
             raise ValueError(f"rank {self.rank} of {self.world}: local must be the contiguous [{hi - lo}, 8] shard, out [{n_symbols}, 8]")
         cur = torch.cuda.current_stream(self.device)
         if cur != self.stream:        # the context lives on another stream than the step: bridge (device-side waits only)
             self.stream.wait_stream(cur)
-        with torch.cuda.device(self.device):
-            self._check(self._lib.pq_gather_summaries_begin(self.h, C.c_void_p(local.data_ptr()), n_symbols, C.c_void_p(out.data_ptr()), slot))
+        self._call("pq_gather_summaries_begin", local, n_symbols, out, slot)
 
     def gather_end(self, slot: int) -> None:
         """pq_gather_summaries_end: the context's stream -- and torch's current stream -- wait (on the device) for that slot's exchange"""
-        with torch.cuda.device(self.device):
-            self._check(self._lib.pq_gather_summaries_end(self.h, slot))
+        self._call("pq_gather_summaries_end", slot)
         cur = torch.cuda.current_stream(self.device)
         if cur != self.stream:
             cur.wait_stream(self.stream)
 
     def sync(self) -> None:
         """pq_comm_sync: block the HOST until the communicator's own stream is idle"""
-        with torch.cuda.device(self.device):
-            self._check(self._lib.pq_comm_sync(self.h))
+        self._call("pq_comm_sync")
 
     def trial(self, timeout_note: str = "") -> torch.Tensor:
         """one exchange of [1, 8] rows per rank on the communicator's OWN stream, waited for on the host: the stream the steps run on is
@@ -175,8 +172,7 @@ class CabiComm:
         return out
 
     def close(self):
-        with torch.cuda.device(self.device):
-            self._check(self._lib.pq_comm_destroy(self.h))
+        self._call("pq_comm_destroy")
 
 
 class OverlappedGather:

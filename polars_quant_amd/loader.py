@@ -13,7 +13,6 @@ run while `high` is still on the bus (`Suite.record_staged` / `run_staged`).
 """
 from __future__ import annotations
 
-import ctypes as C
 from dataclasses import dataclass, field
 from pathlib import Path
 
@@ -148,18 +147,18 @@ class DeviceFrame:
 
     def register(self, host: HostFrame, names=None) -> None:
         """pin the host columns once (an Arrow buffer handed over by the caller is pinned in place)"""
-        from ._lib import check, lib
+        from .api import _call
         for c in (names or list(self.columns)):
             a = host.columns[c]
             if not (a.flags["C_CONTIGUOUS"] and a.dtype == np.float64):
                 raise ValueError(f"column {c}: the host side must be contiguous f64")
-            check(lib().pq_host_register(a.ctypes.data_as(C.c_void_p), a.nbytes))
+            _call("pq_host_register", None, a, a.nbytes)
             self._host.append(a)
 
     def unregister(self) -> None:
-        from ._lib import check, lib
+        from .api import _call
         for a in self._host:
-            check(lib().pq_host_unregister(a.ctypes.data_as(C.c_void_p)))
+            _call("pq_host_unregister", None, a)
         self._host = []
 
     def upload(self, host: HostFrame, order=None, copy_stream=None) -> None:
@@ -167,8 +166,7 @@ class DeviceFrame:
         `torch.cuda.current_stream().wait_event(frame.events[name])` (Suite.run_staged does) and starts while later columns copy."""
         import torch
 
-        from ._lib import check, lib
-        from .api import ctx
+        from .api import _call, ctx
         names = list(order or self.columns)
         any_col = self.columns[names[0]]
         dev = any_col.device
@@ -187,8 +185,7 @@ class DeviceFrame:
                 if tuple(col.shape) != (n, T) or (T > 1 and col.stride(1) != 1) or (n > 1 and col.stride(0) != self.stride):
                     # (a pitched copy into a buffer of another pitch writes past its rows)
                     raise ValueError(f"column {c}: device column has a row pitch of {col.stride(0)} elements, the frame's is {self.stride}")
-                check(lib().pq_memcpy_h2d_pitched(h, C.c_void_p(self.columns[c].data_ptr()), self.stride * 8, a.ctypes.data_as(C.c_void_p), T * 8,
-                                                  T * 8, n))
+                _call("pq_memcpy_h2d_pitched", None, h, self.columns[c], self.stride * 8, a, T * 8, T * 8, n)
                 ev = self.events.get(c) or torch.cuda.Event()
                 ev.record(copy_stream)
                 self.events[c] = ev

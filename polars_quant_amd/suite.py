@@ -9,9 +9,9 @@ import ctypes as C
 import numpy as np
 import torch
 
-from ._lib import Batch, BtParams, check, lib
+from ._lib import Batch, BtParams
 from ._spec import BT_DEFAULTS, I, PATTERN_NAMES, PATTERN_PEN_DEFAULT, SPEC
-from .api import ctx
+from .api import _call, ctx
 
 COLMAP = {"real": "close"}
 
@@ -58,7 +58,7 @@ class Suite:
         self._pens = (C.c_double * 61)(*[PATTERN_PEN_DEFAULT[nm] for nm in PATTERN_NAMES])
         self._pat_ptrs = (C.c_void_p * 61)(*[self.pat[nm].data_ptr() for nm in PATTERN_NAMES])
         self._prm = BtParams(**BT_DEFAULTS)
-        self._defaults = {name: [C.c_int64(int(d)) if k == I else C.c_double(float(d)) for _, k, d in p]
+        self._defaults = {name: [int(d) if k == I else float(d) for _, k, d in p]
                           for name, (_c, p, _o, _f) in SPEC.items()}
         self.bytes_per_row = algorithmic_bytes_per_row()
 
@@ -78,65 +78,48 @@ class Suite:
                                  f"pass the columns through Suite.house() (or build the suite with exact_layout=True)")
 
     def run_one(self, name: str, ohlcv: dict) -> None:
-        L, h, b = lib(), ctx(self.dev.index), self.batch
         self._on_layout(ohlcv)
+        h, o = ctx(self.dev.index), self.out
+        run = lambda fn, *args: _call("pq_" + fn, None, h, self.batch, *args)
+        P = lambda *ks: [ohlcv[k] for k in ks]
+        O = lambda *ns: [t for n in ns for t in o[n]]       # every output column of the named functions, in SPEC's order
         if name == "cdl_all":
-            check(L.pq_cdl_all(h, C.byref(b), *[C.c_void_p(ohlcv[k].data_ptr()) for k in ("open", "high", "low", "close")],
-                               self._pens, self._pat_ptrs))
+            run(name, *P("open", "high", "low", "close"), self._pens, self._pat_ptrs)
         elif name == "backtest_macd_cross":
-            check(L.pq_backtest_macd_cross(h, C.byref(b), C.c_void_p(ohlcv["close"].data_ptr()), 12, 26, 9, C.byref(self._prm),
-                                           *[C.c_void_p(t.data_ptr()) for t in self.bt], C.c_void_p(self.summary.data_ptr())))
+            run(name, ohlcv["close"], 12, 26, 9, self._prm, *self.bt, self.summary)
+        # multi-output forms: the listed functions share their inputs and (default) parameters -> one job
         elif name == "dmi_all":   # calc_dm evaluated once for its five users (all timeperiod=14 by default)
-            o = self.out
-            check(L.pq_dmi_all(h, C.byref(b), *[C.c_void_p(ohlcv[k].data_ptr()) for k in ("high", "low", "close")], 14,
-                               *[C.c_void_p(o[n][0].data_ptr()) for n in ("dx", "plus_di", "minus_di", "adx", "adxr")]))
-        elif name in ("ema_all", "atr_all", "dm_pair", "ad_all", "macd_pair", "apo_ppo", "stoch_all", "sar_pair", "volume_all", "dm_system_all", "cmo_rsi",
-                      "sma_ma"):
-            # multi-output forms: the listed functions share their inputs and (default) parameters -> one job
-            o, P = self.out, lambda k: C.c_void_p(ohlcv[k].data_ptr())
-            O = lambda n, i=0: C.c_void_p(o[n][i].data_ptr())
-            if name == "ema_all":
-                check(L.pq_ema_all(h, C.byref(b), P("close"), 30, O("ema"), O("dema"), O("tema"), O("trix")))
-            elif name == "atr_all":
-                check(L.pq_atr_all(h, C.byref(b), P("high"), P("low"), P("close"), 14, O("atr"), O("natr")))
-            elif name == "dm_pair":
-                check(L.pq_dm_pair(h, C.byref(b), P("high"), P("low"), 14, O("plus_dm"), O("minus_dm")))
-            elif name == "ad_all":
-                check(L.pq_ad_all(h, C.byref(b), P("high"), P("low"), P("close"), P("volume"), 3, 10, O("ad"), O("adosc")))
-            elif name == "dm_system_all":
-                check(L.pq_dm_system_all(h, C.byref(b), P("high"), P("low"), P("close"), 14, O("dx"), O("plus_di"), O("minus_di"), O("adx"),
-                                         O("adxr"), O("atr"), O("natr")))
-            elif name == "cmo_rsi":
-                check(L.pq_cmo_rsi(h, C.byref(b), P("close"), 14, O("cmo"), O("rsi")))
-            elif name == "sma_ma":    # SMA(30) and MA(30, matype 0): the same walk (overlap.rs:857-869), one job, the value written twice
-                check(L.pq_sma_ma(h, C.byref(b), P("close"), 30, O("sma"), O("ma")))
-            elif name == "volume_all":
-                check(L.pq_volume_all(h, C.byref(b), P("high"), P("low"), P("close"), P("volume"), 14, 3, 10, O("mfi"), O("ad"), O("adosc"),
-                                      O("obv")))
-            elif name == "sar_pair":   # Python-wrapper defaults: every parameter 0.0 (overlap.py:115-157)
-                check(L.pq_sar_pair(h, C.byref(b), P("high"), P("low"), *([C.c_double(0.0)] * 10), O("sar"), O("sarext")))
-            elif name == "stoch_all":
-                check(L.pq_stoch_all(h, C.byref(b), P("high"), P("low"), P("close"), 5, 3, 0, 3, 0, 3, 0, O("stoch", 0), O("stoch", 1),
-                                     O("stochf", 0), O("stochf", 1)))
-            elif name == "macd_pair":
-                check(L.pq_macd_pair(h, C.byref(b), P("close"), 12, 26, 9, 9, O("macd", 0), O("macd", 1), O("macd", 2),
-                                     O("macdfix", 0), O("macdfix", 1), O("macdfix", 2)))
-            else:
-                check(L.pq_apo_ppo(h, C.byref(b), P("close"), 12, 26, 0, O("apo"), O("ppo")))
+            run(name, *P("high", "low", "close"), 14, *O("dx", "plus_di", "minus_di", "adx", "adxr"))
+        elif name == "ema_all":
+            run(name, ohlcv["close"], 30, *O("ema", "dema", "tema", "trix"))
+        elif name == "atr_all":
+            run(name, *P("high", "low", "close"), 14, *O("atr", "natr"))
+        elif name == "dm_pair":
+            run(name, *P("high", "low"), 14, *O("plus_dm", "minus_dm"))
+        elif name == "ad_all":
+            run(name, *P("high", "low", "close", "volume"), 3, 10, *O("ad", "adosc"))
+        elif name == "dm_system_all":
+            run(name, *P("high", "low", "close"), 14, *O("dx", "plus_di", "minus_di", "adx", "adxr", "atr", "natr"))
+        elif name == "cmo_rsi":
+            run(name, ohlcv["close"], 14, *O("cmo", "rsi"))
+        elif name == "sma_ma":    # SMA(30) and MA(30, matype 0): the same walk (overlap.rs:857-869), one job, the value written twice
+            run(name, ohlcv["close"], 30, *O("sma", "ma"))
+        elif name == "volume_all":
+            run(name, *P("high", "low", "close", "volume"), 14, 3, 10, *O("mfi", "ad", "adosc", "obv"))
+        elif name == "sar_pair":   # Python-wrapper defaults: every parameter 0.0 (overlap.py:115-157)
+            run(name, *P("high", "low"), *([0.0] * 10), *O("sar", "sarext"))
+        elif name == "stoch_all":
+            run(name, *P("high", "low", "close"), 5, 3, 0, 3, 0, 3, 0, *O("stoch", "stochf"))
+        elif name == "macd_pair":
+            run(name, ohlcv["close"], 12, 26, 9, 9, *O("macd", "macdfix"))
+        elif name == "apo_ppo":
+            run(name, ohlcv["close"], 12, 26, 0, *O("apo", "ppo"))
         elif name == "aroon_all":  # AROON + AROONOSC (both timeperiod=14 by default) from one window scan
-            o = self.out
-            check(L.pq_aroon_all(h, C.byref(b), C.c_void_p(ohlcv["high"].data_ptr()), C.c_void_p(ohlcv["low"].data_ptr()), 14,
-                                 C.c_void_p(o["aroon"][0].data_ptr()), C.c_void_p(o["aroon"][1].data_ptr()),
-                                 C.c_void_p(o["aroonosc"][0].data_ptr())))
+            run(name, *P("high", "low"), 14, *O("aroon", "aroonosc"))
         elif name == "ht_all":    # the Hilbert pipeline evaluated once for dcperiod / dcphase / phasor / sine
-            o = self.out
-            outs = [o["ht_dcperiod"][0], o["ht_dcphase"][0], o["ht_phasor"][0], o["ht_phasor"][1], o["ht_sine"][0], o["ht_sine"][1]]
-            check(L.pq_ht_all(h, C.byref(b), C.c_void_p(ohlcv["close"].data_ptr()), *[C.c_void_p(t.data_ptr()) for t in outs]))
+            run(name, ohlcv["close"], *O("ht_dcperiod", "ht_dcphase", "ht_phasor", "ht_sine"))
         else:
-            outs = self.out[name]
-            cols = SPEC[name][0]
-            check(getattr(L, "pq_" + name)(h, C.byref(b), *[C.c_void_p(self._col(ohlcv, c).data_ptr()) for c in cols],
-                                           *self._defaults[name], *[C.c_void_p(t.data_ptr()) for t in outs]))
+            run(name, *[self._col(ohlcv, c) for c in SPEC[name][0]], *self._defaults[name], *o[name])
 
     FUSED = {"dm_system_all": ("dx", "plus_di", "minus_di", "adx", "adxr", "atr", "natr"), "cmo_rsi": ("cmo", "rsi"),
              "ht_all": ("ht_dcperiod", "ht_dcphase", "ht_phasor", "ht_sine"),
@@ -228,7 +211,6 @@ class Suite:
         keep the exchange of one table in flight while the next step fills the other (distributed.OverlappedGather)."""
         self.close()
         self._housed, self._stale_warned = {}, False   # copies of an earlier recording are not this one's
-        L, h = lib(), ctx(self.dev.index)
         ohlcv = self._house(ohlcv)
         self._ohlcv = ohlcv  # keep the inputs alive: the suite holds raw device pointers
         handles, keep, ok = [], self.summary, False
@@ -236,17 +218,7 @@ class Suite:
             for summ in (summaries or [self.summary]):
                 assert summ.shape == (self.n, 8) and summ.dtype == torch.float64 and summ.is_contiguous()
                 self.summary = summ
-                with torch.cuda.device(self.dev):
-                    check(L.pq_suite_begin(h, C.byref(self.batch)))
-                    try:
-                        for name in (tasks or self.tasks(fused=True)):
-                            self.run_one(name, ohlcv)
-                    except Exception:
-                        L.pq_suite_abort(h)
-                        raise
-                    out = C.c_void_p()
-                    check(L.pq_suite_end(h, C.byref(out)))
-                handles.append(out)
+                handles.append(self._record(tasks or self.tasks(fused=True), ohlcv))
             ok = True
         finally:
             if ok:
@@ -254,10 +226,25 @@ class Suite:
             else:   # a later recording failed: the earlier handles (job tables, events) must not leak, the object keeps its old table
                 self.summary = keep
                 for hnd in handles:
-                    L.pq_suite_destroy(h, hnd)
+                    _call("pq_suite_destroy", None, ctx(self.dev.index), hnd, checked=False)
         self._summaries = list(summaries) if summaries else [self.summary]
         self._suites = handles
         self._suite = handles[0]
+
+    def _record(self, names, ohlcv: dict):
+        """pq_suite_begin, run_one for every name (pq_suite_abort if one raises), pq_suite_end -> the handle of the recording"""
+        with torch.cuda.device(self.dev):
+            h = ctx(self.dev.index)
+            _call("pq_suite_begin", None, h, self.batch)
+            try:
+                for name in names:
+                    self.run_one(name, ohlcv)
+            except Exception:
+                _call("pq_suite_abort", None, h, checked=False)
+                raise
+            out = C.c_void_p()
+            _call("pq_suite_end", None, h, C.byref(out))
+        return out
 
     # ---- staged form: the step split by the input columns a task needs, so that a stage starts as soon as ITS columns have
     # arrived from the host (loader.DeviceFrame.upload records one event per column on the copy stream)
@@ -285,7 +272,6 @@ class Suite:
             raise ValueError(f"record_staged: columns {slow} are not on the suite's row pitch ({self.stride} elements): pass suite.house(columns)")
         self.close()
         self._housed, self._stale_warned = {}, False   # every column is read in place: no copies of an earlier recording stay
-        L, h = lib(), ctx(self.dev.index)
         self._ohlcv = ohlcv
         stages, have, left = [], set(), list(self.tasks(fused=True))
         for col in self.STAGE_ORDER:
@@ -296,50 +282,40 @@ class Suite:
                 stages.append((col, ready))
         assert not left, left
         self._stages = []
-        with torch.cuda.device(self.dev):
-            for col, names in stages:
-                check(L.pq_suite_begin(h, C.byref(self.batch)))
-                try:
-                    for name in names:
-                        self.run_one(name, ohlcv)
-                except Exception:
-                    L.pq_suite_abort(h)
-                    raise
-                out = C.c_void_p()
-                check(L.pq_suite_end(h, C.byref(out)))
-                self._stages.append((col, out, len(names)))
+        for col, names in stages:     # (one by one: close() finds the stages recorded before one that fails)
+            self._stages.append((col, self._record(names, ohlcv), len(names)))
         return [(col, n) for col, _, n in self._stages]
 
     def run_staged(self, events: dict | None = None) -> None:
         """the staged step on the current stream; events[column] (from DeviceFrame.upload): wait for that column's copy first"""
         cur = torch.cuda.current_stream(self.dev)
         with torch.cuda.device(self.dev):
+            h = ctx(self.dev.index)
             for col, handle, _n in self._stages:
                 if events is not None:
                     for c in self.STAGE_ORDER[: self.STAGE_ORDER.index(col) + 1]:
                         if c in events:
                             cur.wait_event(events[c])
-                check(lib().pq_suite_run(ctx(self.dev.index), handle))
+                _call("pq_suite_run", None, h, handle)
 
     def info(self):
         a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
-        check(lib().pq_suite_info(self._suite, C.byref(a), C.byref(b), C.byref(c)))
+        _call("pq_suite_info", None, self._suite, C.byref(a), C.byref(b), C.byref(c))
         return {"phases": a.value, "seq_jobs": b.value, "row_launches": c.value}
 
     def set_timing(self, on: bool = True) -> None:
         """HIP events around every sequential-job grid (on its launch stream) for the following runs"""
-        check(lib().pq_suite_set_timing(self._suite, 1 if on else 0))
+        _call("pq_suite_set_timing", None, self._suite, 1 if on else 0)
 
     def grid_stats(self):
         """-> list of dicts per SEQ grid: avg_ms over the timed runs, algorithmic bytes per launch, jobs, LDS bytes"""
         out, k = [], 0
         while True:
             ms, by, nj, lds, runs = C.c_double(), C.c_double(), C.c_int32(), C.c_int32(), C.c_int32()
-            st = lib().pq_suite_grid_stats(self._suite, k, C.byref(ms), C.byref(by), C.byref(nj), C.byref(lds), C.byref(runs))
-            if st != 0:
+            if _call("pq_suite_grid_stats", None, self._suite, k, C.byref(ms), C.byref(by), C.byref(nj), C.byref(lds), C.byref(runs), checked=False) != 0:
                 break
             var = C.c_int32()
-            check(lib().pq_suite_grid_variant(self._suite, k, C.byref(var)))
+            _call("pq_suite_grid_variant", None, self._suite, k, C.byref(var))
             out.append({"avg_ms": ms.value, "alg_bytes": by.value, "n_jobs": nj.value, "lds_bytes": lds.value, "runs": runs.value,
                         "kernel": f"seq_jobs_kernel<{var.value}>" if var.value < 3 else ("seq_jobs_kernel<3>" if var.value == 4 else "row_chain")})
             k += 1
@@ -349,7 +325,7 @@ class Suite:
         """-> (mean ms from the earliest start to the latest end of the grids launching seq_jobs_kernel<variant>, their
         algorithmic bytes per step)"""
         ms, by = C.c_double(), C.c_double()
-        check(lib().pq_suite_span_stats(self._suite, variant, C.byref(ms), C.byref(by)))
+        _call("pq_suite_span_stats", None, self._suite, variant, C.byref(ms), C.byref(by))
         return ms.value, by.value
 
     def run(self, ohlcv: dict | None = None, slot: int = 0) -> None:
@@ -378,18 +354,17 @@ class Suite:
             warnings.warn("Suite.run() on a created stream: on this runtime a recorded suite replays 17-38 % slower there than on the NULL "
                           "(default) stream -- two of its four chains share a compute pipe of the command processor (INTEGRATION.md); "
                           "warned once per process", PqLayoutWarning, stacklevel=2)
-        with torch.cuda.device(self.dev):
-            check(lib().pq_suite_run(ctx(self.dev.index), self._suites[slot]))
+        _call("pq_suite_run", self.dev, self._suites[slot])
 
     _stream_warned = False
 
     def close(self):
         for hnd in getattr(self, "_suites", []) or []:
-            check(lib().pq_suite_destroy(ctx(self.dev.index), hnd))
+            _call("pq_suite_destroy", None, ctx(self.dev.index), hnd)
         self._suites = []
         self._suite = None
         for _col, handle, _n in getattr(self, "_stages", []):
-            check(lib().pq_suite_destroy(ctx(self.dev.index), handle))
+            _call("pq_suite_destroy", None, ctx(self.dev.index), handle)
         self._stages = []
 
     def __del__(self):

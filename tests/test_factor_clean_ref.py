@@ -195,6 +195,7 @@ def test_public_surface():
     (dict(neutralize_industry=True), "needs industry"),
     (dict(neutralize_industry=True, industry=np.array([0, 1, 256])), "industry codes"),
     (dict(neutralize_industry=True, industry=np.array([0.5, 1.0, 2.0])), "integer"),
+    (dict(neutralize_industry=True, industry=np.array([0j, 1j, 2j])), "integer"),
 ])
 def test_argument_errors_raise_before_device_work(kw, msg):
     """on a machine without a GPU any device work raises PqError; these raise ValueError first"""
