@@ -590,6 +590,34 @@ pq_status pq_factor_coverage(pq_ctx *, const pq_batch *, const double *factor, d
  * win_rate = #(ic > 0) / n_days; all but n_days null below 2 days, ir null where std is 0 */
 pq_status pq_ic_stats(pq_ctx *, const double *ic, int64_t len, double *out);
 
+/* ---- rank 3, continued: the group portfolios of D-15's labels held between rebalance days, with weights, drift and a fee on the
+ * traded value, Factor.portfolio_backtest (beyond the README; decision D-27 in DESIGN.md section 2).  labels: uint8 [n_series][stride]
+ * (the pitch of the batch, as D-15 writes them); price / weight: f64 on the batch's pitch, weight NULL = equal weights;
+ * rebalance_days d_0 < ... < d_{R-1}: a HOST array, each in [label_lag, len), copied into the context workspace.
+ *   usable       a price (a weight) that is non-null, finite and > 0
+ *   members      M_k(g) = the symbols with labels[s][d_k - label_lag] == g, a usable price[s][d_k] and, where weight is given, a usable
+ *                weight[s][d_k]; a label >= n_groups (PQ_LABEL_MID, PQ_LABEL_OUT) belongs to no group; count[g][k] = |M_k(g)|
+ *   weights      a_s = weight[s][d_k] (1.0 without weight), A_k(g) = the sum of a_s over M_k(g) in D-12's order (blocks of 256 symbols,
+ *                ascending symbols inside a block from 0.0, blocks added in ascending order from 0.0), w_s = a_s / A_k(g)
+ *   held price   h(s, t), t >= d_k: the price on the latest day in [d_k, t] with a usable price (a suspended stock keeps its last price)
+ *   ownership    day t > d_0 belongs to the segment k with d_k < t <= d_{k+1}; the last segment runs to len - 1
+ *   growth       G(g, t) = the sum over M_k(g) of w_s * (h(s, t) / price[s][d_k]) in D-12's order; 1.0 where M_k(g) is empty (cash)
+ *   turnover     traded value over portfolio value, buys and sells both counted: turnover[g][k] = the sum over ALL symbols, in D-12's
+ *                order, of |w_new - w_old|; w_new = w_s of rebalance k (0 for a non-member); w_old = 0 at k = 0, else for s in
+ *                M_{k-1}(g) its weight drifted to d_k, w_s * (h(s, d_k) / price[s][d_{k-1}]) / G(g, d_k) (0 for a symbol not held)
+ *   value        P_0 = initial_capital, P_k = B_{k-1} * G(g, d_k), B_k = P_k * (1 - cost_rate * turnover[g][k]), a sequential product
+ *                over k; value[g][t] = initial_capital for t < d_0, B_k at t = d_k, B_k * G(g, t) for d_k < t <= d_{k+1}
+ * Plain IEEE f64; value holds no NULL, a non-finite result stays as it is.  n_groups in [1, 20], label_lag >= 0, cost_rate in [0, 1),
+ * initial_capital > 0 and finite, n_rebalance >= 0 (0: every value cell is initial_capital); len == 0 returns PQ_OK.  value:
+ * [n_groups][len], turnover / count: [n_groups][n_rebalance].  No ragged batches, not recordable.  Uses the context workspace
+ * (8 bytes per group, day and block of 256 symbols). */
+pq_status pq_factor_portfolio(pq_ctx *, const pq_batch *, const uint8_t *labels, int32_t n_groups, int32_t label_lag,
+                              const double *price, const double *weight /* NULL: equal weights */,
+                              const int32_t *rebalance_days /* HOST, n_rebalance entries */, int64_t n_rebalance,
+                              double cost_rate, double initial_capital,
+                              double *value /* [n_groups][len] */, double *turnover /* [n_groups][n_rebalance] */,
+                              int32_t *count /* [n_groups][n_rebalance] */);
+
 /* ---- rank 3, continued: per-day factor cleaning, clean(...) (README.md:244-345; README-only, decision D-16 in DESIGN.md section 2).
  * factor / cap_z: f64 [n_series][stride], industry: int32 [n_series][stride], all on the batch's row pitch.  Per day, the cross-section is
  * every symbol with a non-null finite factor, a non-null finite cap_z (size neutralization on) and an industry code in [0, n_industries)

@@ -134,6 +134,7 @@ factor_quantiles       i pBppipppppp
 factor_long_short      i pBppddpppppp
 factor_coverage        i pBpp
 ic_stats               i pplp
+factor_portfolio       i pBpiippplddppp
 factor_clean           i pBpidppiip
 xsec_regress           i pBpippppppp
 ts_regress             i pBpiupppppp

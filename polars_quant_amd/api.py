@@ -506,6 +506,52 @@ def ic_stats(ic):
     return out
 
 
+def _labels_on_pitch(labels, b, dev, shape):
+    """uint8 group labels [N, T] -> a device tensor whose rows lie on the batch's pitch: the tensor that factor_quantiles / factor_long_short
+    (labels=True) returned for columns of the same pitch is taken as it is, anything else is copied once"""
+    lab = labels if isinstance(labels, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(labels)))
+    if tuple(lab.shape) != tuple(shape):
+        raise ValueError(f"labels must have the shape of price {tuple(shape)}, not {tuple(lab.shape)}")
+    if lab.dtype != torch.uint8:
+        raise ValueError(f"labels must be uint8 (group numbers, LABEL_MID, LABEL_OUT), not {lab.dtype}")
+    n, T = shape
+    if lab.device == dev and (T <= 1 or lab.stride(1) == 1) and (n <= 1 or lab.stride(0) == b.stride):
+        return lab
+    buf = torch.empty((n, b.stride), dtype=torch.uint8, device=dev)
+    buf[:, :T].copy_(lab)
+    return buf[:, :T]
+
+
+def factor_portfolio(labels, price, n_groups: int, rebalance_days, weight=None, label_lag: int = 0, cost_rate: float = 0.0,
+                     initial_capital: float = 1_000_000.0):
+    """D-27: the portfolios of the groups 0 .. n_groups - 1 of `labels` (uint8 [N, T], as factor_quantiles / factor_long_short return
+    them with labels=True), re-formed on the ascending day indices `rebalance_days` from the labels of day d - label_lag and held in
+    between: members weighted by weight[s][d] (None: equally) drift with their prices (a symbol without a usable price keeps its last
+    one), and every rebalance pays cost_rate on the traded value (buys and sells both counted).  -> dict of device tensors: value
+    [G, T] (initial_capital before the first rebalance day), turnover [G, R] (traded value over portfolio value), count int32 [G, R]
+    (members), rebalance_days int32 [R].  The definitions are in include/pq_hip.h."""
+    days = np.asarray(rebalance_days)
+    if days.size and days.dtype.kind not in "iu":
+        raise ValueError("rebalance_days must hold integer day indices")
+    days = days.reshape(-1).astype(np.int64)
+    if days.size and (days.min() < -2**31 or days.max() >= 2**31):
+        raise ValueError("rebalance_days must fit int32")
+    days = np.ascontiguousarray(days.astype(np.int32))
+    ts, b = _xsec_inputs([price] if weight is None else [price, weight])
+    p, wt = ts[0], (ts[1] if weight is not None else None)
+    dev = p.device
+    n, T = p.shape
+    lab = _labels_on_pitch(labels, b, dev, (n, T))
+    G, R = max(int(n_groups), 0), days.size
+    out = {"value": torch.empty((G, T), dtype=torch.float64, device=dev),
+           "turnover": torch.empty((G, R), dtype=torch.float64, device=dev),
+           "count": torch.empty((G, R), dtype=torch.int32, device=dev)}
+    _call("pq_factor_portfolio", dev, b, lab, int(n_groups), int(label_lag), p, wt, days if R else None, R, float(cost_rate),
+          float(initial_capital), *out.values())
+    out["rebalance_days"] = torch.from_numpy(days).to(dev)
+    return out
+
+
 CLEAN_WINSORIZE = {None: 0, "mad": 1, "sigma": 2, "percentile": 3}     # pq_factor_clean's winsorize codes
 CLEAN_WINSORIZE_N = {"mad": 3.0, "sigma": 3.0, "percentile": 1.0}    # the README's defaults
 MAX_INDUSTRIES = 256

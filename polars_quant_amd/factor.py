@@ -8,6 +8,8 @@ tests ic_decay / subsample_test / subgroup_test (decision D-18), and the multi-f
 (README.md:1423-1426, :1472-1477; decision D-21) roll along the days of every symbol.  README-only in the reference.  Inputs are [N, T] arrays (symbol-major, like every other column of this package): the
 factor and the forward return of every symbol on every day.
 `clean` is the README's factor cleaning step that comes before the evaluation (decision D-16).
+`portfolio_backtest` (decision D-27, beyond the README) holds the groups of the sorts as portfolios: rebalance days, weights, drift and
+a fee on the traded value, as value curves with the backtest report's statistics; it takes the factor and the PRICE of every symbol.
 """
 from __future__ import annotations
 
@@ -128,6 +130,40 @@ class Factor:
         """-> share of the non-null days with a positive (rank) IC (nan below 2 days)"""
         ic, _ = _api.factor_ic(factor, next_return, 1 if rank else 0)
         return float(_api.ic_stats(ic)[4])
+
+    # ---- D-27: the sorts' groups as portfolios that are held between rebalance days, with weights, drift and a fee on the traded value
+    def portfolio_backtest(self, factor, price, n_quantiles=5, top_pct=None, bottom_pct=None, rebalance=20, start=0, weight=None, lag=0,
+                           cost_rate=0.001, initial_capital=1_000_000.0, benchmark=None):
+        """factor, price (and weight, e.g. the market cap; None: equal weights) [N, T].  The groups are the quantile buckets of the
+        factor (0 = lowest values) or, with top_pct / bottom_pct, the two legs (0 = short, 1 = long), sorted per day over the symbols
+        with a valid factor and a non-null finite price; a member also needs a price > 0.  rebalance: an interval in days (the
+        rebalance days are start, start + rebalance, ...) or a sequence of day indices; a rebalance on day d uses the labels of day
+        d - lag.  -> {"value": [G, T], "turnover": [G, R], "count": [G, R], "rebalance_days": [R], "daily_return": [G, T],
+        "ls_return": [T] (top group minus bottom group, two long-only curves), "statistics": {name: [G]}, the curve columns of the
+        backtest report and, with a benchmark [T], its benchmark columns}"""
+        from ._spec import REPORT_COLS
+        if (top_pct is None) != (bottom_pct is None):
+            raise ValueError("top_pct and bottom_pct go together")
+        T = _api._shape(price)[-1]
+        if hasattr(rebalance, "__index__"):
+            if int(rebalance) < 1:
+                raise ValueError(f"rebalance must be an interval of at least one day or a sequence of days, not {rebalance!r}")
+            rebalance = range(int(start), T, int(rebalance))
+        if top_pct is None:
+            groups = int(n_quantiles)
+            lab = _api.factor_quantiles(factor, price, groups, labels=True)["labels"]
+        else:
+            groups = 2
+            lab = _api.factor_long_short(factor, price, top_pct, bottom_pct, labels=True)["labels"]
+        out = _api.factor_portfolio(lab, price, groups, list(rebalance), weight, lag, cost_rate, initial_capital)
+        value = out["value"]
+        (daily,) = _api.call("returns", value, period=1)
+        out["daily_return"] = daily
+        out["ls_return"] = _api.factor_binary(daily[groups - 1:], daily[:1], _api.BINARY_OPS["diff"])[0]
+        rep = _api.backtest_report(value, initial_capital, benchmark)
+        cols = list(range(15)) + (list(range(38, 45)) if benchmark is not None else [])
+        out["statistics"] = {REPORT_COLS[c]: rep[:, c] for c in cols}
+        return out
 
     # ---- D-17: regressions and significance tests (README.md:1521-1600)
     def ic_test(self, factor, next_return, method="pearson"):
