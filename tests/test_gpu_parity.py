@@ -59,43 +59,10 @@ def rich(oracle, request):
     return d
 
 
-def bits(a):
-    return np.ascontiguousarray(a).view(np.uint64 if a.dtype == np.float64 else np.uint32)
-
-
 from pattern_kats import UNSAT, kat_series
 
 KAT_MARKS = {}   # (symbols, days) of a rich data set -> {symbol: [(row, recogniser, hand-derived value)]}
-from tolerance import SCALE_OF  # which transcendental outputs are judged against a natural scale, and why
-
-
-def assert_same(name, got, exp, exact=True, price=None):
-    got = np.asarray(got)
-    assert got.shape == exp.shape and got.dtype == exp.dtype, (name, got.shape, exp.shape, got.dtype, exp.dtype)
-    if exp.dtype != np.float64:
-        assert (got == exp).all(), f"{name}: {np.sum(got != exp)} int mismatches"
-        return
-    NULLB = np.uint64(0x7FF80000504E554C)
-    gn, en = bits(got) == NULLB, bits(exp) == NULLB
-    assert (gn == en).all(), f"{name}: null masks differ at {np.argwhere(gn != en)[:5].tolist()}"
-    if exact:
-        bad = (bits(got) != bits(exp)) & ~(np.isnan(got) & np.isnan(exp))
-        assert not bad.any(), (f"{name}: {bad.sum()} of {bad.size} not bit-exact; first at {np.argwhere(bad)[:3].tolist()} "
-                               f"got {got[bad][:3]} exp {exp[bad][:3]}")
-    else:
-        key = name.split("{")[0]
-        scale = SCALE_OF.get(key, 0.0)
-        if isinstance(scale, str):
-            assert price is not None, f"{name}: judged against the price level, which the caller must pass"
-            scale = np.abs(price)
-        ok = ~en
-        g, e = got[ok], exp[ok]
-        sc = np.broadcast_to(scale, exp.shape)[ok]
-        both_nan = np.isnan(g) & np.isnan(e)
-        with np.errstate(invalid="ignore"):
-            err = np.abs(g - e) / np.maximum(np.maximum(np.abs(e), sc), 1e-300)
-        err[both_nan | (g == e)] = 0        # (equal infinities: inf - inf is NaN)
-        assert (err <= RTOL).all(), f"{name}: max error {np.nanmax(err):.3e} (relative to max(|expected|, scale))"
+from parity_util import assert_same, bits  # the comparison with the oracle, shared with tests/test_indicator_forms_gpu.py
 
 
 def run_gpu(pq, name, d, **params):

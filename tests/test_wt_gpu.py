@@ -86,6 +86,44 @@ def test_single_functions(pq, oracle, data, name, cols, prm):
         same(f"{name}[{k}]{prm}", g.cpu().numpy(), e)
 
 
+LIMITS = [1023, 1024, 1025, 4095, 4096, 4097]   # WT_MIN_LEN = 1024 and WT_MAX_LEN = 4096 (csrc/wt_dev.h) from the outside and one step inside
+_limit_cols = {}
+
+
+def _limit_data(oracle, T):
+    """3 series of T rows: the host columns, and device copies on the 128-byte row pitch (an odd length under an even pitch: the dense
+    odd shapes of SHAPES run the 8-byte tiled body, which is outside the form's scope)"""
+    from polars_quant_amd import api
+    if T not in _limit_cols:
+        d = oracle.gen_ohlcv(SEED + 9, 3, T, 0)
+        dev = {}
+        for k, v in d.items():
+            buf = torch.full((3, api.recommended_stride(T)), 777.0, dtype=torch.float64, device="cuda")
+            buf[:, :T] = torch.from_numpy(v).cuda()
+            dev[k] = buf[:, :T]
+        _limit_cols[T] = (d, dev)
+    return _limit_cols[T]
+
+
+@pytest.mark.parametrize("T", LIMITS)
+@pytest.mark.parametrize("name,cols,prm", CASES, ids=[f"{c[0]}-{'-'.join(str(v) for v in c[2].values())}" for c in CASES])
+def test_limits_of_the_length_range(pq, oracle, name, cols, prm, T):
+    """the wave form runs at 1024 <= len <= 4096 and not at 1023 and 4097; the same bits either way"""
+    from polars_quant_amd import api
+    d, dev = _limit_data(oracle, T)
+    api.wt_stats(reset=True)
+    got = api.call(name, *[dev[c] for c in cols], **prm)
+    st = api.wt_stats()
+    rings_above_64k = name == "midprice" and prm.get("timeperiod", 0) > 30      # (as in test_single_functions)
+    if 1024 <= T <= 4096 and not rings_above_64k:
+        assert st[0] == 3 and st[3] == 0, f"the wave form did not run at len {T}: {st}"
+    else:
+        assert st == (0, 0, 0, 0), f"the wave form ran at len {T}: {st}"
+    exp = oracle.call(name, *[d[c] for c in cols], **prm)
+    for k, (g, e) in enumerate(zip(got, exp)):
+        same(f"{name}[{k}]{prm} len {T}", g.cpu().numpy(), e)
+
+
 @pytest.mark.parametrize("name", ["dema", "tema", "ema", "trix", "rsi", "atr", "natr", "adx", "macd", "midpoint"])
 def test_timeperiod_one(pq, oracle, name):
     """Period 1 is where the reference's if-chains degenerate: every seeding branch of DEMA / TEMA (overlap.rs:590-597, :1238-1240)
