@@ -744,6 +744,29 @@ pq_status pq_factor_binary(pq_ctx *, const pq_batch *, const double *a, const do
 /* op 0 mean, 1 momentum, 2 volatility, 3 skewness, 4 relative strength (decision D-21) */
 pq_status pq_factor_rolling(pq_ctx *, const pq_batch *, const double *x, int32_t op, int64_t window, int64_t skip, double *out);
 
+/* ---- rank 3, continued: rolling-window OLS, Factor.rolling_regression / rolling_beta / idiosyncratic_volatility (the README computes
+ * one whole-history beta to the market with `linear`, README.md:231; one value per (symbol, day) is decision D-28 in DESIGN.md section
+ * 2).  Model y = a + sum_j b_j x_j over the days t-w+1 .. t of one symbol, w = window, K = n_x, 1 <= K <= PQ_ROLLING_REGRESS_MAX_K.  x is
+ * a HOST array of K device pointers; y and x[j] are f64 [n_series][stride] on the batch's row pitch, except that bit j of series_mask
+ * makes x[j] one [len] series shared by every symbol (e.g. a market return), as in pq_ts_regress.  A row has a result only if
+ * t >= w - 1 and all K + 1 values are non-null and finite on every day of its window (D-21's rule; no min_periods).  The arithmetic is
+ * D-17's with n = w, every sum a plain sum over the window in ascending day order from 0.0, evaluated directly (no sliding sums), so
+ * every output is bit-exact: the K + 1 means; the centred products and C = L D L^T in D-17's order with its singular rule (a pivot
+ * D_j <= 1e-12 C[j][j], a NaN pivot, anything behind one); alpha = ybar - sum_j b_j xbar_j; e = d_y - sum_j b_j d_j, sse = sum e e.
+ *   beta      [n_x][n_series][stride]   b_j
+ *   alpha     [n_series][stride]        a
+ *   resid_std [n_series][stride]        sqrt(sse / (w - K - 1))
+ *   r_squared [n_series][stride]        1 - sse / Syy; NULL where Syy == 0 (the other outputs stay)
+ *   resid     [n_series][stride]        the e of the window's last day t
+ * Each output may be a NULL pointer: it is not written.  A row without its sample, with a singular window or with a result that comes
+ * out NaN is NULL in every output.  K + 2 <= window <= PQ_FACTOR_ROLLING_MAX_WINDOW, n_x outside 1 .. 4, a series_mask bit beyond n_x,
+ * a ragged batch, and an output that overlaps an input or another output (a workgroup reads a halo of days that another workgroup
+ * writes) are PQ_ERR_ARG; suite recording is refused (PQ_ERR_UNSUPPORTED); n_series = 0 or len = 0 launches nothing.  No workspace. */
+#define PQ_ROLLING_REGRESS_MAX_K 4
+pq_status pq_factor_rolling_regress(pq_ctx *, const pq_batch *, const double *const *x, int32_t n_x, uint32_t series_mask,
+                                    const double *y, int64_t window, double *beta /* [n_x][n_series][stride] */, double *alpha,
+                                    double *resid_std, double *r_squared, double *resid);
+
 /* ---- suites: record many calls, replay them as a few chip-filling grids ----
  * One indicator over N symbols is only N/64 wavefronts -- far too few for 256 CUs -- but a DataFrame query asks
  * for many indicators at once (df.with_columns([...]) in the reference; Polars then calls the plugin once per

@@ -149,6 +149,7 @@ factor_minmax          i pBpp
 factor_weighted        i pBppplip
 factor_binary          i pBppip
 factor_rolling         i pBpillp
+factor_rolling_regress i pBpiuplppppp
 suite_begin            i pB
 suite_end              i pp
 suite_abort            i p

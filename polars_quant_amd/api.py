@@ -673,9 +673,9 @@ def _regress_args(factors, ret, series_ok):
     return cols, rs
 
 
-def _regress_call(fn_name, cols, ret, series_ok, make_outs, extra):
-    """uploads the factor columns and the return onto one row pitch, allocates the outputs on their device (make_outs(device) -> list of
-    output tensors, None: not written) and calls fn_name"""
+def _regress_upload(cols, ret, series_ok):
+    """uploads the factor columns and the return onto one row pitch -> (the device columns, the mask of the [T] series among them, the
+    device return, the host array of the columns' pointers or None for an empty batch)"""
     ser = [series_ok and len(_shape(c)) == 1 for c in cols]
     mats = _same_layout([_to_device(c)[0] for c, s in zip(cols, ser) if not s] + [_to_device(ret)[0]])
     r = mats[-1]
@@ -683,6 +683,13 @@ def _regress_call(fn_name, cols, ret, series_ok, make_outs, extra):
     fs = [_to_device(c)[0].reshape(-1).contiguous() if s else next(it) for c, s in zip(cols, ser)]
     mask = sum(1 << j for j, s in enumerate(ser) if s)
     ptrs = (C.c_void_p * len(fs))(*[f.data_ptr() for f in fs]) if r.numel() else None
+    return fs, mask, r, ptrs
+
+
+def _regress_call(fn_name, cols, ret, series_ok, make_outs, extra):
+    """uploads the factor columns and the return onto one row pitch, allocates the outputs on their device (make_outs(device) -> list of
+    output tensors, None: not written) and calls fn_name"""
+    fs, mask, r, ptrs = _regress_upload(cols, ret, series_ok)
     outs = make_outs(r.device)
     _call(fn_name, r.device, _batch(r), ptrs, len(fs), *extra(mask), r, *outs)
     return outs
@@ -977,6 +984,49 @@ def factor_rolling(x, op: int, window: int, skip: int = 0):
         raise ValueError(f"skip must be >= 0, and 0 except for momentum, not {skip!r}")
     _build_shapes(("factor",), (x,))
     return _build_call("pq_factor_rolling", [x], lambda b, dev: (int(op), int(window), int(skip)))
+
+
+ROLLING_REGRESS_MAX_K = 4                                      # PQ_ROLLING_REGRESS_MAX_K
+ROLLING_REGRESS_OUTPUTS = ("beta", "alpha", "resid_std", "r_squared", "resid")   # pq_factor_rolling_regress's output pointers, in order
+
+
+def _rolling_regress_args(y, xs, window, outputs):
+    """argument checks of factor_rolling_regress that need no device -> (list of regressor columns, (N, T), tuple of output names)"""
+    if isinstance(outputs, str):
+        outputs = (outputs,)
+    names = tuple(outputs)
+    if not names:
+        raise ValueError(f"outputs must name at least one of {ROLLING_REGRESS_OUTPUTS}")
+    for nm in names:
+        if nm not in ROLLING_REGRESS_OUTPUTS:
+            raise ValueError(f"outputs must be among {ROLLING_REGRESS_OUTPUTS}, not {nm!r}")
+    if len(_shape(y)) != 2:
+        raise ValueError(f"y must be [N, T], not {_shape(y)}")
+    cols = _columns(xs, "the number of regressors", 1, ROLLING_REGRESS_MAX_K, 3,
+                    "xs must be a list of [N, T] or [T] arrays or one [K, N, T] array")
+    cols, shape = _regress_args(cols, y, True)
+    if isinstance(window, bool) or not isinstance(window, (int, np.integer)):
+        raise ValueError(f"window must be an integer, not {window!r}")
+    if not len(cols) + 2 <= window <= ROLLING_MAX_WINDOW:
+        raise ValueError(f"window must be in {len(cols) + 2}..{ROLLING_MAX_WINDOW} for {len(cols)} regressors, not {window!r}")
+    return cols, shape, names
+
+
+def factor_rolling_regress(y, xs, window: int, outputs=ROLLING_REGRESS_OUTPUTS):
+    """D-28: the OLS y = a + sum_j b_j x_j over the last `window` days of every symbol, one fit per (symbol, day).  y [N, T]; xs: K
+    regressors (1 <= K <= 4; a list, or one [K, N, T] array), each [N, T] or a [T] series shared by every symbol (e.g. a market return)
+    -> dict of device tensors, only those named in `outputs`: beta [K, N, T], alpha, resid_std (sqrt(sse / (window - K - 1))),
+    r_squared (NULL where y is constant over the window) and resid (the window's last day) [N, T].  A row is NULL unless all K + 1
+    values are non-null and finite on every day of its window, and where the window is singular.  K + 2 <= window <= 1024."""
+    cols, (n, T), names = _rolling_regress_args(y, xs, window, outputs)
+    K = len(cols)
+    fs, mask, r, ptrs = _regress_upload(cols, y, True)
+    b = _batch(r)
+    f64 = dict(dtype=torch.float64, device=r.device)      # the outputs sit on the inputs' row pitch
+    outs = [(torch.empty((K, n, b.stride) if nm == "beta" else (n, b.stride), **f64) if nm in names else None)
+            for nm in ROLLING_REGRESS_OUTPUTS]
+    _call("pq_factor_rolling_regress", r.device, b, ptrs, K, mask, r, int(window), *outs)
+    return {nm: o[..., :T] for nm, o in zip(ROLLING_REGRESS_OUTPUTS, outs) if o is not None}
 
 
 def split_periods(T: int, n_splits: int):

@@ -5,7 +5,8 @@ them (README.md:1429-1430, :1480-1482, :1626-1634): per-day cross-sectional IC, 
 regressions and significance tests ic_test / factor_return / fama_macbeth / time_series_regression (decision D-17), and the robustness
 tests ic_decay / subsample_test / subgroup_test (decision D-18), and the multi-factor orthogonalization / neutralization Factor().clean
 (decision D-19).  The common technical factors moving_average / momentum / volatility / skewness / relative_strength
-(README.md:1423-1426, :1472-1477; decision D-21) roll along the days of every symbol.  README-only in the reference.  Inputs are [N, T] arrays (symbol-major, like every other column of this package): the
+(README.md:1423-1426, :1472-1477; decision D-21) roll along the days of every symbol, and so do the two-column ones rolling_regression /
+rolling_beta / idiosyncratic_volatility (decision D-28: rolling-window OLS).  README-only in the reference.  Inputs are [N, T] arrays (symbol-major, like every other column of this package): the
 factor and the forward return of every symbol on every day.
 `clean` is the README's factor cleaning step that comes before the evaluation (decision D-16).
 `portfolio_backtest` (decision D-27, beyond the README) holds the groups of the sorts as portfolios: rebalance days, weights, drift and
@@ -77,6 +78,23 @@ class Factor:
         """-> 100 G / (G + L) over the last `window` day-to-day differences, G the sum of the rises and L of the falls (the
         simple-average form, no warm-up memory); NULL unless the window + 1 values are non-null and finite, and where G + L == 0"""
         return _api.factor_rolling(factor, _api.ROLLING_OPS["relative_strength"], window)
+
+    # ---- D-28: rolling-window OLS of the returns on K regressors (1 <= K <= 4, each [N, T] or a [T] series shared by every symbol, e.g.
+    # the market return), one fit per (symbol, day) over the last `window` days; a row is NULL unless every value of its window is
+    # non-null and finite, and where the window is singular; K + 2 <= window <= 1024
+    def rolling_regression(self, returns, factors, window=60):
+        """-> {"beta": [K, N, T], "alpha", "resid_std", "r_squared", "resid": [N, T]}: the slopes, the intercept, the residual std
+        sqrt(sse / (window - K - 1)), R^2 (NULL where the returns are constant over the window) and the residual of the window's last
+        day"""
+        return _api.factor_rolling_regress(returns, factors, window)
+
+    def rolling_beta(self, returns, market, window=60):
+        """-> [N, T]: the slope of the rolling OLS of the returns on one regressor, [N, T] or a [T] market series"""
+        return _api.factor_rolling_regress(returns, [market], window, outputs=("beta",))["beta"][0]
+
+    def idiosyncratic_volatility(self, returns, factors, window=60):
+        """-> [N, T]: the residual std of the rolling OLS of the returns on the factors (not annualised)"""
+        return _api.factor_rolling_regress(returns, factors, window, outputs=("resid_std",))["resid_std"]
 
     def ic(self, factor, next_return):
         """-> (ic [T], n_valid [T]): Pearson correlation across symbols, per day"""
