@@ -4,7 +4,8 @@
 //
 // The three passes, the centred normal equations, the solve and the standard errors are D-17's (regress.hip): pass 1 n and the sums,
 // pass 2 the packed triangle of the K + 1 columns x_0 .. x_{K-1}, y that xsec_ols.h factorises, pass 3 the squared residuals -- here
-// of the residuals it writes, resid = y - pred with pred = a + sum_j b_j x_j (j ascending, from a).  What differs is the reduction: D-17
+// of the residuals it writes, resid = y - pred with pred = a + sum_j b_j x_j (j ascending, from a).  The solve is xo_fit (xsec_ols.h) and
+// the coefficient statistics are rg_coef_stats / rg_r2 (xsec_ttest.h), the functions regress.hip calls.  What differs is the reduction: D-17
 // has one thread per (unit, block of 256 indices) and a serial combine per unit, and a pooled fit is ONE unit of up to 5e7 rows.
 //
 // Summation order (a function of the logical row index r = s * len + t alone: not of the grid, the CU count or the row pitch):
@@ -209,7 +210,7 @@ __global__ __launch_bounds__(LN_THREADS) void ln_sum_kernel(const double *ps, in
     if (threadIdx.x == 0) sums[blockIdx.x] = v;
 }
 
-// after pass 2 (one thread): rg_solve_kernel's operations on the triangle -- C = L D L^T, b, the intercept, diag(C^-1) and
+// after pass 2 (one thread): the triangle goes through xo_fit, as in rg_solve_kernel -- b, the intercept, diag(C^-1) and
 // 1/n + xbar^T C^-1 xbar
 template <int K> __global__ __launch_bounds__(64) void ln_solve_kernel(LnState st) {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
@@ -218,43 +219,11 @@ template <int K> __global__ __launch_bounds__(64) void ln_solve_kernel(LnState s
 #pragma unroll
     for (int q = 0; q < NA; q++) s[q] = st.sums[q];
     *st.syy = s[NA - 1];
-    const int64_t n = *st.n;
-    double L[K][K], D[K];
-    const bool ok = xo_ldl<K>(s, L, D) == K && n >= K + 2;
-    *st.ok = ok ? 1 : 0;
-    if (!ok) return;
-    double z[K], b[K], xbar[K];
-#pragma unroll
-    for (int j = 0; j < K; j++) xbar[j] = st.mean[j];
-    xo_forward<K>(L, s + xo_tri(K), K, z);   // c = row K of the triangle
-    xo_back<K>(L, D, z, K, b);
-    double sa = 0.0;
-#pragma unroll
-    for (int j = 0; j < K; j++) sa += b[j] * xbar[j];
-#pragma unroll
-    for (int j = 0; j < K; j++) st.b[j] = b[j];
-    st.b[K] = st.mean[K] - sa;
-    // (C^-1)_jj = sum_m (L^-1 e_j)_m^2 / D_m, m ascending from 0.0
-#pragma unroll
-    for (int j = 0; j < K; j++) {
-        double e[K], w[K];
-#pragma unroll
-        for (int m = 0; m < K; m++) e[m] = m == j ? 1.0 : 0.0;
-        xo_forward<K>(L, e, K, w);
-        double vj = 0.0;
-#pragma unroll
-        for (int m = 0; m < K; m++) vj += w[m] * w[m] / D[m];
-        st.v[j] = vj;
-    }
-    double w[K], q = 0.0;
-    xo_forward<K>(L, xbar, K, w);
-#pragma unroll
-    for (int m = 0; m < K; m++) q += w[m] * w[m] / D[m];
-    st.v[K] = 1.0 / (double)n + q;
+    *st.ok = xo_fit<K>(s, *st.n, st.mean, st.mean + K, st.b, st.v, 1) ? 1 : 0;
 }
 
-// stage 2 after pass 3 and the statistics, as rg_final_kernel: s^2 = SSE / (n - K - 1), se_j = sqrt(s^2 V_jj), t_j = b_j / se_j, p on
-// n - K - 1, R^2 = 1 - SSE / Syy.  Thread j <= K writes coefficient j.
+// stage 2 after pass 3 and the statistics of rg_final_kernel (xsec_ttest.h) on n - K - 1 degrees of freedom.  Thread j <= K writes
+// coefficient j.
 template <int K>
 __global__ __launch_bounds__(LN_THREADS) void ln_final_kernel(const double *ps, int64_t ntile, LnState st, double *coef, double *tst,
                                                               double *pv, double *r2, int64_t *n_out) {
@@ -272,14 +241,9 @@ __global__ __launch_bounds__(LN_THREADS) void ln_final_kernel(const double *ps, 
     const double df = (double)(n - K - 1), s2 = sse / df, syy = ok ? *st.syy : 0.0;
     if (j == 0) {
         *n_out = n;
-        *r2 = ok && syy != 0.0 ? 1.0 - sse / syy : pq_null();
+        *r2 = rg_r2(ok, sse, syy);
     }
-    if (!ok) { coef[j] = pq_null(); tst[j] = pq_null(); pv[j] = pq_null(); return; }
-    const double bj = st.b[j], se = sqrt(s2 * st.v[j]);
-    coef[j] = bj;
-    const double t = se == 0.0 ? pq_null() : bj / se;
-    tst[j] = t;
-    pv[j] = se == 0.0 ? pq_null() : rg_t_pvalue(t, df);
+    rg_coef_stats(ok, st.b + j, st.v + j, s2, df, coef + j, tst + j, pv + j);
 }
 
 struct LnOut {
@@ -321,16 +285,7 @@ template <int K> pq_status ln_layout(pq_ctx *ctx, const LnIn &in, const LnOut &o
 }
 
 pq_status ln_dispatch(pq_ctx *ctx, int k, const LnIn &in, const LnOut &out) {
-    switch (k) {
-    case 1: return ln_layout<1>(ctx, in, out);
-    case 2: return ln_layout<2>(ctx, in, out);
-    case 3: return ln_layout<3>(ctx, in, out);
-    case 4: return ln_layout<4>(ctx, in, out);
-    case 5: return ln_layout<5>(ctx, in, out);
-    case 6: return ln_layout<6>(ctx, in, out);
-    case 7: return ln_layout<7>(ctx, in, out);
-    default: return ln_layout<8>(ctx, in, out);
-    }
+    return xo_with_k<XO_MAX_K>(k, [&](auto K) { return ln_layout<decltype(K)::value>(ctx, in, out); });
 }
 
 } // namespace

@@ -13,7 +13,9 @@
 //              writes coef / t / p / R^2 / n.  The operation order is D-17's, restated in tests/xsec_regress_ref.py.  The combine,
 //              the means, the factorization, the two substitutions and the head of the workspace are in xsec_ols.h, which orth.hip
 //              (D-19) shares: pass 2's sums are the packed triangle of the K + 1 columns f_0 .. f_{K-1}, r, and D-19's last level is
-//              this regression with r = f_{K-1}.  The pass kernel is this file's own (xsec_ols.h says why).
+//              this regression with r = f_{K-1}.  The whole solve after pass 2 is xo_fit (xsec_ols.h) and the statistics after
+//              pass 3 are rg_coef_stats / rg_r2 (xsec_ttest.h): linear.hip (D-24) calls the same two.  The pass kernel is this
+//              file's own (xsec_ols.h says why).
 //  3. summary: (cross-sectional) one 64-lane workgroup per regressor: the Fama-MacBeth mean / std / t / p over the days with a solution.
 // p-values: two-sided Student t, p = I_{df / (df + t^2)}(df / 2, 1/2), by the Lentz continued fraction in double-double arithmetic
 // (near x = 1 the fraction loses ~log10(1 / (1 - x)) digits in plain f64), with log Gamma(a + 1/2) / Gamma(a) from its asymptotic
@@ -122,7 +124,8 @@ __global__ __launch_bounds__(64) void rg_pass_kernel(RgIn in, RgUnit un, double 
     if (P == RG_P1) pcnt[(int64_t)blockIdx.y * units + u] = cnt;
 }
 
-// after pass 2: C = L D L^T by rows, the solution b, the intercept, diag(C^-1) and 1/n + fbar^T C^-1 fbar
+// after pass 2: the combined triangle goes through xo_fit, which leaves b, the intercept, diag(C^-1) and 1/n + fbar^T C^-1 fbar in the
+// unit's rows
 template <int K>
 __global__ __launch_bounds__(64) void rg_solve_kernel(const double *ps, int64_t nblk, int64_t units, RgUnit un) {
     const int64_t u = (int64_t)blockIdx.x * 64 + threadIdx.x;
@@ -131,39 +134,7 @@ __global__ __launch_bounds__(64) void rg_solve_kernel(const double *ps, int64_t 
     double s[NA];
     xo_combine<NA>(ps, nblk, units, u, s);
     un.srr[u] = s[NA - 1];
-    const int32_t n = un.n[u];
-    double L[K][K], D[K];
-    const bool ok = xo_ldl<K>(s, L, D) == K && n >= K + 2;
-    un.ok[u] = ok ? 1 : 0;
-    if (!ok) return;
-    double z[K], b[K], fbar[K];
-#pragma unroll
-    for (int j = 0; j < K; j++) fbar[j] = un.mean[(int64_t)(j + 1) * units + u];
-    xo_forward<K>(L, s + xo_tri(K), K, z);   // c = row K of the triangle
-    xo_back<K>(L, D, z, K, b);
-    double sa = 0.0;
-#pragma unroll
-    for (int j = 0; j < K; j++) sa += b[j] * fbar[j];
-#pragma unroll
-    for (int j = 0; j < K; j++) un.b[(int64_t)j * units + u] = b[j];
-    un.b[(int64_t)K * units + u] = un.mean[u] - sa;
-    // (C^-1)_jj = sum_m (L^-1 e_j)_m^2 / D_m, m ascending from 0.0
-#pragma unroll
-    for (int j = 0; j < K; j++) {
-        double e[K], w[K];
-#pragma unroll
-        for (int m = 0; m < K; m++) e[m] = m == j ? 1.0 : 0.0;
-        xo_forward<K>(L, e, K, w);
-        double vj = 0.0;
-#pragma unroll
-        for (int m = 0; m < K; m++) vj += w[m] * w[m] / D[m];
-        un.v[(int64_t)j * units + u] = vj;
-    }
-    double w[K], q = 0.0;
-    xo_forward<K>(L, fbar, K, w);
-#pragma unroll
-    for (int m = 0; m < K; m++) q += w[m] * w[m] / D[m];
-    un.v[(int64_t)K * units + u] = 1.0 / (double)n + q;
+    un.ok[u] = xo_fit<K>(s, un.n[u], un.mean + units + u, un.mean + u, un.b + u, un.v + u, units) ? 1 : 0;
 }
 
 // after pass 3: s^2 = SSE / (n - K - 1), se_j = sqrt(s^2 V_jj), t_j = b_j / se_j, p on n - K - 1, R^2 = 1 - SSE / Srr.
@@ -179,16 +150,11 @@ __global__ __launch_bounds__(64) void rg_final_kernel(const double *ps, int64_t 
     n_obs[u] = n;
     const bool ok = un.ok[u] != 0;
     const double df = (double)(n - K - 1), s2 = sse[0] / df, srr = ok ? un.srr[u] : 0.0;
-    r2[u] = ok && srr != 0.0 ? 1.0 - sse[0] / srr : pq_null();
+    r2[u] = rg_r2(ok, sse[0], srr);
 #pragma unroll
     for (int j = 0; j <= K; j++) {
-        const int64_t o = TS ? u * (K + 1) + j : (int64_t)j * units + u;
-        if (!ok) { coef[o] = pq_null(); tst[o] = pq_null(); pv[o] = pq_null(); continue; }
-        const double bj = un.b[(int64_t)j * units + u], se = sqrt(s2 * un.v[(int64_t)j * units + u]);
-        coef[o] = bj;
-        const double t = se == 0.0 ? pq_null() : bj / se;
-        tst[o] = t;
-        pv[o] = se == 0.0 ? pq_null() : rg_t_pvalue(t, df);
+        const int64_t o = TS ? u * (K + 1) + j : (int64_t)j * units + u, w = (int64_t)j * units + u;
+        rg_coef_stats(ok, un.b + w, un.v + w, s2, df, coef + o, tst + o, pv + o);
     }
 }
 
@@ -238,16 +204,7 @@ pq_status rg_run(pq_ctx *ctx, const RgIn &in, const RgOut &out) {
 
 template <bool TS>
 pq_status rg_dispatch(pq_ctx *ctx, int k, const RgIn &in, const RgOut &out) {
-    switch (k) {
-    case 1: return rg_run<1, TS>(ctx, in, out);
-    case 2: return rg_run<2, TS>(ctx, in, out);
-    case 3: return rg_run<3, TS>(ctx, in, out);
-    case 4: return rg_run<4, TS>(ctx, in, out);
-    case 5: return rg_run<5, TS>(ctx, in, out);
-    case 6: return rg_run<6, TS>(ctx, in, out);
-    case 7: return rg_run<7, TS>(ctx, in, out);
-    default: return rg_run<8, TS>(ctx, in, out);
-    }
+    return xo_with_k<XO_MAX_K>(k, [&](auto K) { return rg_run<decltype(K)::value, TS>(ctx, in, out); });
 }
 
 pq_status rg_args(pq_ctx *ctx, const pq_batch *b, const char *what, const double *const *factors, int32_t k, const double *ret, RgIn &in) {

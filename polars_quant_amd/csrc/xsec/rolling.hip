@@ -11,13 +11,15 @@
 //               unusable entry at or before it (a max-scan over the staged stretch: every thread scans a short run, the runs are joined
 //               by a wave scan), so "is the whole window usable" is one compare.  Each thread then evaluates its own row's window
 //               directly, in ascending order from 0.0, out of LDS: consecutive threads read consecutive 8-byte words at every step (no
-//               bank conflict), and the order of the additions is the definition's, which a sliding sum would not keep.
+//               bank conflict), and the order of the additions is the definition's, which a sliding sum would not keep.  The tile
+//               constant, the job split, the scan (xw_last_scan), the launch shape and the overlap check are xsec_window.h's, which
+//               rolling_regress.hip (D-28) shares.
 //  momentum:    two loads per row, no LDS.
-#include "xsec_dev.h"
+#include "xsec_window.h"
 
 namespace {
 
-constexpr int RL_TILE = 256;                                    // days per workgroup = threads per workgroup
+constexpr int RL_TILE = XW_TILE;                                // days per workgroup = threads per workgroup
 constexpr int RL_MAX_W = PQ_FACTOR_ROLLING_MAX_WINDOW;
 constexpr int RL_STAGE = RL_TILE + RL_MAX_W - 1;                // staged entries at the widest window: 10 KiB of f64 + 5 KiB of i32
 
@@ -30,11 +32,9 @@ __global__ __launch_bounds__(RL_TILE) void rl_window_kernel(const double *x, Dim
     __shared__ double val[RL_STAGE];
     __shared__ int last[RL_STAGE];          // index of the last unusable entry <= l, -1 without one
     __shared__ int wave_last[RL_TILE / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int M = RL_TILE + w - 1, C = (M + RL_TILE - 1) / RL_TILE;
-    const int lo = tid * C < M ? tid * C : M, hi = lo + C < M ? lo + C : M;
+    const int tid = threadIdx.x, M = RL_TILE + w - 1;
     for (int64_t job = blockIdx.x; job < total; job += gridDim.x) {
-        const int64_t s = job / chunks, t0 = (job - s * chunks) * RL_TILE, g0 = t0 - (w - 1);
+        const auto [s, t0, g0] = xw_job(job, chunks, w);
         const double *row = x + s * d.stride;
         for (int l = tid; l < M; l += RL_TILE) {
             const int64_t g = g0 + l;
@@ -52,24 +52,7 @@ __global__ __launch_bounds__(RL_TILE) void rl_window_kernel(const double *x, Dim
             val[l] = v;
             last[l] = ok ? -1 : l;
         }
-        __syncthreads();
-        int m = -1;                                             // the marks grow with l, so the maximum is the last one
-        for (int l = lo; l < hi; l++) m = last[l] > m ? last[l] : m;
-        int inc = m;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int u = __shfl_up(inc, o, 64);
-            if (lane >= o && u > inc) inc = u;
-        }
-        if (lane == 63) wave_last[wave] = inc;
-        __syncthreads();
-        int carry = __shfl_up(inc, 1, 64);
-        if (lane == 0) carry = -1;
-        for (int k = 0; k < wave; k++) carry = wave_last[k] > carry ? wave_last[k] : carry;
-        for (int l = lo; l < hi; l++) {
-            carry = last[l] > carry ? last[l] : carry;
-            last[l] = carry;
-        }
-        __syncthreads();
+        xw_last_scan(last, M, wave_last);
         const int64_t t = t0 + tid;
         if (t < d.len) {
             const int e = tid + w - 1;
@@ -124,7 +107,8 @@ __global__ __launch_bounds__(RL_TILE) void rl_window_kernel(const double *x, Dim
 __global__ __launch_bounds__(RL_TILE) void rl_momentum_kernel(const double *x, Dims d, int64_t w, int64_t skip, int64_t chunks, int64_t total,
                                                               double *out) {
     for (int64_t job = blockIdx.x; job < total; job += gridDim.x) {
-        const int64_t s = job / chunks, t = (job - s * chunks) * RL_TILE + threadIdx.x;
+        const auto [s, t0, g0] = xw_job(job, chunks, 1);        // nothing is staged: no halo
+        const int64_t t = t0 + threadIdx.x;
         if (t >= d.len) continue;
         const double *row = x + s * d.stride;
         const int64_t ia = t - skip, ib = ia - w;
@@ -159,19 +143,19 @@ pq_status pq_factor_rolling(pq_ctx *ctx, const pq_batch *b, const double *x, int
     if (b->len == 0 || b->n_series == 0) return PQ_OK;
     const Dims d = dims_of(b);
     // a workgroup reads a halo of days that another workgroup writes: the two [n_series][stride] columns must be disjoint
-    const uintptr_t xa = (uintptr_t)x, oa = (uintptr_t)out, bytes = (uintptr_t)d.n * (uintptr_t)d.stride * 8;
-    PQ_REQUIRE(xa + bytes <= oa || oa + bytes <= xa, "pq_factor_rolling: out must not overlap x");
-    const int64_t chunks = (d.len + RL_TILE - 1) / RL_TILE, total = chunks * d.n;
-    const dim3 grid((unsigned)(total < (int64_t)1 << 20 ? total : (int64_t)1 << 20)), block(RL_TILE);
+    const uintptr_t bytes = (uintptr_t)d.n * (uintptr_t)d.stride * 8;
+    PQ_REQUIRE(xw_disjoint(xw_span(x, bytes), xw_span(out, bytes)), "pq_factor_rolling: out must not overlap x");
+    const XwGrid g = xw_grid(d);
+    const dim3 block(RL_TILE);
     hipStream_t st = ctx->stream;
     const int w = (int)window;
     if (skip > d.len) skip = d.len;                             // every row is NULL from skip + window >= len on
     switch (op) {
-    case RL_MEAN: hipLaunchKernelGGL(rl_window_kernel<RL_MEAN>, grid, block, 0, st, x, d, w, chunks, total, out); break;
-    case RL_MOM: hipLaunchKernelGGL(rl_momentum_kernel, grid, block, 0, st, x, d, window, skip, chunks, total, out); break;
-    case RL_VOL: hipLaunchKernelGGL(rl_window_kernel<RL_VOL>, grid, block, 0, st, x, d, w, chunks, total, out); break;
-    case RL_SKEW: hipLaunchKernelGGL(rl_window_kernel<RL_SKEW>, grid, block, 0, st, x, d, w, chunks, total, out); break;
-    default: hipLaunchKernelGGL(rl_window_kernel<RL_RS>, grid, block, 0, st, x, d, w, chunks, total, out); break;
+    case RL_MEAN: hipLaunchKernelGGL(rl_window_kernel<RL_MEAN>, g.grid, block, 0, st, x, d, w, g.chunks, g.total, out); break;
+    case RL_MOM: hipLaunchKernelGGL(rl_momentum_kernel, g.grid, block, 0, st, x, d, window, skip, g.chunks, g.total, out); break;
+    case RL_VOL: hipLaunchKernelGGL(rl_window_kernel<RL_VOL>, g.grid, block, 0, st, x, d, w, g.chunks, g.total, out); break;
+    case RL_SKEW: hipLaunchKernelGGL(rl_window_kernel<RL_SKEW>, g.grid, block, 0, st, x, d, w, g.chunks, g.total, out); break;
+    default: hipLaunchKernelGGL(rl_window_kernel<RL_RS>, g.grid, block, 0, st, x, d, w, g.chunks, g.total, out); break;
     }
     PQ_HIP_TRY(hipGetLastError());
     return PQ_OK;

@@ -6,20 +6,24 @@
 // y = a + sum_j b_j x_j over the `window` days that end at the row, K = n_x regressors (1 .. 4).  The sample rule is rolling.hip's (D-21):
 // a row has a result only if all K + 1 values are non-null and finite on every day of its window.  The arithmetic is D-17's
 // (regress.hip, restated in tests/xsec_regress_ref.py) with n = window and every blocked sum replaced by a plain sum over the window in
-// ascending day order from 0.0; the L D L^T core is xsec_ols.h's.
-//  launch:  one workgroup of 256 threads per (symbol, tile of 256 days), walked with a grid stride, as rl_window_kernel.
+// ascending day order from 0.0; the L D L^T core is xsec_ols.h's.  The row's solve is the first half of xo_fit (b and the intercept,
+// no standard errors) written out here on xo_ldl / xo_forward / xo_back: through xo_fit the kernel compiled to other code and one
+// timing left the parent's range (EXPERIMENTS.md, "One fit and one window stage for the regress / rolling kernels").
+//  launch:  one workgroup of 256 threads per (symbol, tile of 256 days), walked with a grid stride, as rl_window_kernel: the tile
+//           constant, the job split, the launch shape and the overlap check are xsec_window.h's.
 //  stage:   the tile and a halo of window - 1 earlier days of all K + 1 columns go into dynamic LDS, sized by the actual window
 //           ((K + 1)(255 + window) f64 and (255 + window) i32: 6.3 KB at K = 1, window = 60; 56.3 KB at K = 4, window = 1024), loads
-//           coalesced along days.  One last[] array marks an entry unusable if any column is; the max-scan of rolling.hip turns it into
-//           "the last unusable entry at or before l", so "is the whole window usable" is one compare.
+//           coalesced along days.  One last[] array marks an entry unusable if any column is; xw_last_scan (xsec_window.h) turns it
+//           into "the last unusable entry at or before l", so "is the whole window usable" is one compare.
 //  rows:    each thread evaluates its own row's three passes directly out of LDS (sliding sums would not keep the order of the
 //           additions): consecutive threads read consecutive 8-byte words of one column at every step, so no bank conflict.  The kernel
 //           is templated on K: every index of the xo_* arrays is static and nothing goes to scratch (rolling_regress.resources.txt).
 #include "xsec_ols.h"
+#include "xsec_window.h"
 
 namespace {
 
-constexpr int RR_TILE = 256;                                    // days per workgroup = threads per workgroup
+constexpr int RR_TILE = XW_TILE;                                // days per workgroup = threads per workgroup
 constexpr int RR_MAX_W = PQ_FACTOR_ROLLING_MAX_WINDOW;
 constexpr int RR_MAX_K = PQ_ROLLING_REGRESS_MAX_K;
 
@@ -43,14 +47,12 @@ __global__ __launch_bounds__(RR_TILE) void rr_window_kernel(RrIn in, RrOut out, 
     __shared__ int wave_last[RR_TILE / 64];
     constexpr int NV = K + 1, NA = xo_tri(NV);
     const Dims d = in.d;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int M = RR_TILE + w - 1, C = (M + RR_TILE - 1) / RR_TILE;
-    const int lo = tid * C < M ? tid * C : M, hi = lo + C < M ? lo + C : M;
+    const int tid = threadIdx.x, M = RR_TILE + w - 1;
     double *val = rr_lds;
     int *last = (int *)(rr_lds + (size_t)NV * M);               // index of the last unusable entry <= l, -1 without one
     const int64_t plane = d.n * d.stride;
     for (int64_t job = blockIdx.x; job < total; job += gridDim.x) {
-        const int64_t s = job / chunks, t0 = (job - s * chunks) * RR_TILE, g0 = t0 - (w - 1);
+        const auto [s, t0, g0] = xw_job(job, chunks, w);
         const double *col[NV];
 #pragma unroll
         for (int c = 0; c < K; c++) col[c] = in.x[c] + (((in.series >> c) & 1u) ? 0 : s * d.stride);
@@ -67,24 +69,7 @@ __global__ __launch_bounds__(RR_TILE) void rr_window_kernel(RrIn in, RrOut out, 
             }
             last[l] = ok ? -1 : l;
         }
-        __syncthreads();
-        int m = -1;                                             // the marks grow with l, so the maximum is the last one
-        for (int l = lo; l < hi; l++) m = last[l] > m ? last[l] : m;
-        int inc = m;
-        for (int o = 1; o < 64; o <<= 1) {
-            const int u = __shfl_up(inc, o, 64);
-            if (lane >= o && u > inc) inc = u;
-        }
-        if (lane == 63) wave_last[wave] = inc;
-        __syncthreads();
-        int carry = __shfl_up(inc, 1, 64);
-        if (lane == 0) carry = -1;
-        for (int k = 0; k < wave; k++) carry = wave_last[k] > carry ? wave_last[k] : carry;
-        for (int l = lo; l < hi; l++) {
-            carry = last[l] > carry ? last[l] : carry;
-            last[l] = carry;
-        }
-        __syncthreads();
+        xw_last_scan(last, M, wave_last);
         const int64_t t = t0 + tid;
         if (t < d.len) {
             const int e = tid + w - 1;
@@ -161,13 +146,6 @@ __global__ __launch_bounds__(RR_TILE) void rr_window_kernel(RrIn in, RrOut out, 
     }
 }
 
-template <int K> void rr_launch(hipStream_t st, dim3 grid, size_t lds, const RrIn &in, const RrOut &out, int w, int64_t chunks, int64_t total) {
-    hipLaunchKernelGGL(rr_window_kernel<K>, grid, dim3(RR_TILE), lds, st, in, out, w, chunks, total);
-}
-
-struct RrSpan { uintptr_t lo, hi; };
-inline bool rr_disjoint(const RrSpan &a, const RrSpan &b) { return a.hi <= b.lo || b.hi <= a.lo; }
-
 } // namespace
 
 extern "C" {
@@ -190,36 +168,31 @@ pq_status pq_factor_rolling_regress(pq_ctx *ctx, const pq_batch *b, const double
     const Dims d = in.d;
     // a workgroup reads a halo of days that another workgroup writes: no output may overlap an input or another output
     const uintptr_t colb = ((uintptr_t)(d.n - 1) * (uintptr_t)d.stride + (uintptr_t)d.len) * 8, plane = (uintptr_t)d.n * (uintptr_t)d.stride * 8;
-    RrSpan ins[RR_MAX_K + 1], outs[5];
+    XwSpan ins[RR_MAX_K + 1], outs[5];
     int n_in = 0, n_out = 0;
-    ins[n_in++] = RrSpan{(uintptr_t)y, (uintptr_t)y + colb};
+    ins[n_in++] = xw_span(y, colb);
     for (int j = 0; j < n_x; j++) {
         PQ_REQUIRE(x[j], "pq_factor_rolling_regress: null regressor pointer");
         in.x[j] = x[j];
-        ins[n_in++] = RrSpan{(uintptr_t)x[j], (uintptr_t)x[j] + (((series_mask >> j) & 1u) ? (uintptr_t)d.len * 8 : colb)};
+        ins[n_in++] = xw_span(x[j], ((series_mask >> j) & 1u) ? (uintptr_t)d.len * 8 : colb);
     }
-    if (beta) outs[n_out++] = RrSpan{(uintptr_t)beta, (uintptr_t)beta + (uintptr_t)(n_x - 1) * plane + colb};
+    if (beta) outs[n_out++] = xw_span(beta, (uintptr_t)(n_x - 1) * plane + colb);
     for (double *p : {alpha, resid_std, r_squared, resid})
-        if (p) outs[n_out++] = RrSpan{(uintptr_t)p, (uintptr_t)p + colb};
+        if (p) outs[n_out++] = xw_span(p, colb);
     for (int i = 0; i < n_out; i++) {
         for (int j = 0; j < n_in; j++)
-            PQ_REQUIRE(rr_disjoint(outs[i], ins[j]), "pq_factor_rolling_regress: an output must not overlap an input");
+            PQ_REQUIRE(xw_disjoint(outs[i], ins[j]), "pq_factor_rolling_regress: an output must not overlap an input");
         for (int j = 0; j < i; j++)
-            PQ_REQUIRE(rr_disjoint(outs[i], outs[j]), "pq_factor_rolling_regress: two outputs must not overlap");
+            PQ_REQUIRE(xw_disjoint(outs[i], outs[j]), "pq_factor_rolling_regress: two outputs must not overlap");
     }
     if (n_out == 0) return PQ_OK;
     const RrOut out{beta, alpha, resid_std, r_squared, resid};
     const int w = (int)window;
-    const int64_t chunks = (d.len + RR_TILE - 1) / RR_TILE, total = chunks * d.n;
-    const dim3 grid((unsigned)(total < (int64_t)1 << 20 ? total : (int64_t)1 << 20));
+    const XwGrid g = xw_grid(d);
     const size_t M = (size_t)(RR_TILE + w - 1), lds = (size_t)(n_x + 1) * M * 8 + M * 4;
-    hipStream_t st = ctx->stream;
-    switch (n_x) {
-    case 1: rr_launch<1>(st, grid, lds, in, out, w, chunks, total); break;
-    case 2: rr_launch<2>(st, grid, lds, in, out, w, chunks, total); break;
-    case 3: rr_launch<3>(st, grid, lds, in, out, w, chunks, total); break;
-    default: rr_launch<4>(st, grid, lds, in, out, w, chunks, total); break;
-    }
+    xo_with_k<RR_MAX_K>(n_x, [&](auto K) {
+        hipLaunchKernelGGL(rr_window_kernel<decltype(K)::value>, g.grid, dim3(RR_TILE), lds, ctx->stream, in, out, w, g.chunks, g.total);
+    });
     PQ_HIP_TRY(hipGetLastError());
     return PQ_OK;
 }

@@ -1,4 +1,5 @@
-// xsec/xsec_ols.h -- the moments and L D L^T core of D-17, shared by regress.hip (D-17) and orth.hip (D-19).
+// xsec/xsec_ols.h -- the moments and L D L^T core of D-17, shared by regress.hip (D-17), orth.hip (D-19) and rolling_regress.hip (D-28),
+// and D-17's fit on it, which regress.hip and linear.hip (D-24) share.
 //
 // D-17's return is one more column behind the factors: with NV = K + 1 columns f_0 .. f_{K-1}, r its pass 2 is the packed lower triangle
 // of the centred cross-products, s[j (j + 1) / 2 + l] = sum d_j d_l (l <= j): C in rows 0 .. K-1, then c and Srr in row K.  D-19's pass 2 is
@@ -8,10 +9,16 @@
 //  * solve:    xo_ldl factorises the leading R x R block C = L D L^T by rows and counts the leading pivots that are not singular; it is
 //              prefix-consistent, so the leading k x k block is what D-17 factorises for k regressors.  xo_forward and xo_back solve
 //              on that block.  The operation order is D-17's, restated in tests/xsec_regress_ref.py and tests/xsec_orth_ref.py.
+//  * fit:      xo_fit is the whole of D-17's solve on one triangle: the factorization, b, the intercept, and diag(C^-1) and
+//              1/n + xbar^T C^-1 xbar for the standard errors.  rg_solve_kernel and ln_solve_kernel are calls of it, so the two agree
+//              bit for bit by construction.  Two callers stay on xo_ldl / xo_forward / xo_back: orth.hip's or_solve_kernel solves
+//              K - 1 nested prefix systems without an intercept, and rr_window_kernel (rolling_regress.hip) keeps the fit's first half
+//              in its row loop (its header says why).
 //  * host:     xo_workspace carves what both workspaces begin with; each caller appends its own rows.
 // The blocked pass kernels, and with them the structs of input columns, stay one per file: one kernel on NV columns compiles to other
 // code for regress.hip and its time-series form ran slower (EXPERIMENTS.md, "One pass kernel for regress.hip and orth.hip").
 #pragma once
+#include <type_traits>
 #include "xsec_dev.h"
 
 namespace {
@@ -100,7 +107,53 @@ __device__ __forceinline__ void xo_back(const double (&L)[R][R], const double (&
     }
 }
 
+// D-17's fit on the packed triangle s of the K + 1 columns x_0 .. x_{K-1}, y (C in rows 0 .. K-1, then c and Syy in row K), n members:
+// b[0 .. K) and the intercept b[K] = ybar - sum_j b_j xbar_j, v[0 .. K) = diag(C^-1) and v[K] = 1/n + xbar^T C^-1 xbar for the standard
+// errors.  xbar, b and v are read and written `stride` doubles apart: a [rows][units] workspace, or arrays (stride 1).  Returns whether
+// the system solved; without a solution nothing is read or written.
+template <int K>
+__device__ __forceinline__ bool xo_fit(const double *s, int64_t n, const double *xbar, const double *ybar, double *b, double *v,
+                                       int64_t stride) {
+    double L[K][K], D[K];
+    if (!(xo_ldl<K>(s, L, D) == K && n >= K + 2)) return false;
+    double z[K], bb[K], fbar[K];
+#pragma unroll
+    for (int j = 0; j < K; j++) fbar[j] = xbar[j * stride];
+    xo_forward<K>(L, s + xo_tri(K), K, z);   // c = row K of the triangle
+    xo_back<K>(L, D, z, K, bb);
+    double sa = 0.0;
+#pragma unroll
+    for (int j = 0; j < K; j++) sa += bb[j] * fbar[j];
+#pragma unroll
+    for (int j = 0; j < K; j++) b[j * stride] = bb[j];
+    b[K * stride] = *ybar - sa;
+    // (C^-1)_jj = sum_m (L^-1 e_j)_m^2 / D_m, m ascending from 0.0
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+        double e[K], w[K];
+#pragma unroll
+        for (int m = 0; m < K; m++) e[m] = m == j ? 1.0 : 0.0;
+        xo_forward<K>(L, e, K, w);
+        double vj = 0.0;
+#pragma unroll
+        for (int m = 0; m < K; m++) vj += w[m] * w[m] / D[m];
+        v[j * stride] = vj;
+    }
+    double w[K], q = 0.0;
+    xo_forward<K>(L, fbar, K, w);
+#pragma unroll
+    for (int m = 0; m < K; m++) q += w[m] * w[m] / D[m];
+    v[K * stride] = 1.0 / (double)n + q;
+    return true;
+}
+
 // ---------------------------------------------------------------- host
+// f(std::integral_constant<int, k>) for a runtime k in [1, MAX] (the entry points check the range): one instantiation per K
+template <int MAX, int K = 1, class F> auto xo_with_k(int k, F &&f) {
+    if constexpr (K == MAX) return f(std::integral_constant<int, K>{});
+    else return k == K ? f(std::integral_constant<int, K>{}) : xo_with_k<MAX, K + 1>(k, f);
+}
+
 // workspace: n, flag (i32) | `rows` f64 rows, `row` doubles apart: the nv means, then the caller's own | block partials [nblk][na][units]
 // (f64) | block counts (i32)
 struct XoWs {

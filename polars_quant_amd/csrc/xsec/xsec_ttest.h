@@ -1,5 +1,6 @@
 // xsec/xsec_ttest.h -- Student-t p-values and the sequential summary row (D-17), shared by regress.hip (Fama-MacBeth, ic_test) and
-// robust.hip (D-18: IC decay, sub-period and sub-group tests).  Moved unchanged from regress.hip, whose header notes the method.
+// robust.hip (D-18: IC decay, sub-period and sub-group tests).  Moved unchanged from regress.hip, whose header notes the method.  Also
+// the coefficient statistics of a fit (coef / t / p and R^2 with their NULL rules), shared by regress.hip and linear.hip (D-24).
 #pragma once
 #include "xsec_dev.h"
 
@@ -88,6 +89,21 @@ __device__ double rg_t_pvalue(double t, double df) {
     if (x.hi < (a + 1.0) / (a + 2.5)) return front * rg_betacf(x, a, 0.5) / a;
     return 1.0 - front * rg_betacf(y, 0.5, a) / 0.5;
 }
+
+// Coefficient j of a fit (xo_fit's b_j and v_j, read only where the fit solved) with s^2 = SSE / df: coef = b_j, se = sqrt(s^2 v_j),
+// t = b_j / se, p on df; t and p are NULL where se == 0, and all three without a solution.  Shared by rg_final_kernel (regress.hip)
+// and ln_final_kernel (linear.hip); where the three values go is the caller's.
+__device__ __forceinline__ void rg_coef_stats(bool ok, const double *bj, const double *vj, double s2, double df, double *coef, double *tst,
+                                              double *pv) {
+    if (!ok) { *coef = pq_null(); *tst = pq_null(); *pv = pq_null(); return; }
+    const double b = *bj, se = sqrt(s2 * *vj);
+    *coef = b;
+    const double t = se == 0.0 ? pq_null() : b / se;
+    *tst = t;
+    *pv = se == 0.0 ? pq_null() : rg_t_pvalue(t, df);
+}
+// R^2 = 1 - SSE / Syy; NULL without a solution or where the dependent column is constant
+__device__ __forceinline__ double rg_r2(bool ok, double sse, double syy) { return ok && syy != 0.0 ? 1.0 - sse / syy : pq_null(); }
 
 // Summary row of one series, one 64-lane workgroup: n_days, mean, std (ddof 1), t = mean / (std / sqrt(n_days)), p on n_days - 1, over
 // the non-NaN days of x[0 .. len), ascending sequential sums from 0.0; o[0 .. RG_SUMMARY_COLS) is written by lane 0

@@ -12,6 +12,13 @@ torch = pytest.importorskip("torch")
 
 SHAPES = [(37, 50), (300, 131), (2, 3), (1, 5)]
 KS = [1, 2, 3, 8]
+TS_SHAPES = [(37, 50), (20, 600), (300, 131), (2, 3), (1, 5)]
+
+
+def cases(shapes):
+    """every shape at every K of KS; the K between them (the fit of xsec_ols.h is instantiated for 1 .. 8) at (37, 50) only"""
+    return [pytest.param(s, K, id=f"{s[0]}x{s[1]}-{K}") for K in KS for s in shapes] + \
+           [pytest.param((37, 50), K, id=f"37x50-{K}") for K in (4, 5, 6, 7)]
 
 
 @pytest.fixture(scope="module")
@@ -112,8 +119,7 @@ def check_ts(pq, cols, r, pitch=None):
     return got, exp
 
 
-@pytest.mark.parametrize("K", KS)
-@pytest.mark.parametrize("shape", SHAPES, ids=[f"{n}x{t}" for n, t in SHAPES])
+@pytest.mark.parametrize("shape,K", cases(SHAPES))
 def test_xsec_regress_bitwise(pq, shape, K):
     n, T = shape
     F, r = make(K, n, T, 100 * K + n + T)
@@ -131,8 +137,7 @@ def test_xsec_regress_odd_pitch_and_clean_data(pq, K):
     check_xsec(pq, F, r, pitch=139)
 
 
-@pytest.mark.parametrize("K", KS)
-@pytest.mark.parametrize("shape", [(37, 50), (20, 600), (300, 131), (2, 3), (1, 5)], ids=lambda s: f"{s[0]}x{s[1]}")
+@pytest.mark.parametrize("shape,K", cases(TS_SHAPES))
 def test_ts_regress_bitwise(pq, shape, K):
     n, T = shape
     F, r = make(K, n, T, 7 * K + n + T)

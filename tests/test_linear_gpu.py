@@ -114,7 +114,7 @@ def check(pq, X, y, tag, surface=True):
 
 
 # ---- sizes
-@pytest.mark.parametrize("K", [1, 2, 3, 8])
+@pytest.mark.parametrize("K", [1, 2, 3, 4, 5, 6, 7, 8])
 def test_small_sizes(pq, K):
     for M in (0, 1, K + 1, K + 2, 63, 64, 65):
         X, y = make(K, (M,), 100 * K + M)
