@@ -767,6 +767,35 @@ pq_status pq_factor_rolling_regress(pq_ctx *, const pq_batch *, const double *co
                                     const double *y, int64_t window, double *beta /* [n_x][n_series][stride] */, double *alpha,
                                     double *resid_std, double *r_squared, double *resid);
 
+/* ---- rank 3, continued: the time-series operators of factor construction, Factor.ts_sum / ts_std / ts_zscore / ts_min / ts_max /
+ * ts_argmin / ts_argmax / ts_rank / decay_linear / delay / delta and ts_cov / ts_corr (beyond the README: the windowed operators that
+ * formulaic alphas are written in; decision D-29 in DESIGN.md section 2).  x, y: f64 [n_series][stride]; out: f64 [n_series][stride] on
+ * the same pitch.  Everything runs along the days of one symbol.  w = window, dw = (double)w; win[0 .. w) = x[t-w+1 .. t], oldest to
+ * newest; D-21's rule: a row is NULL unless t >= w - 1 and every value of its window is non-null and finite; every sum starts at 0.0
+ * and adds in ascending k, evaluated directly (no sliding sums), so every output is bit-exact.
+ *   op 0 sum:           sum of win[k]
+ *   op 1 std:           w >= 2: mean = sum / dw, q2 = sum of (win[k] - mean)^2, sqrt(q2 / (w - 1))   (volatility's order)
+ *   op 2 zscore:        w >= 2: (win[w-1] - mean) / std; NULL at q2 == 0
+ *   op 3 min, 4 max:    the window's extreme (of equal extremes the oldest: -0 ties with +0)
+ *   op 5 argmin, 6 argmax: the 0-based offset of the extreme from the window's OLDEST day, 0 .. w-1, as f64; compares are < and >, so
+ *                       ties go to the oldest day (numpy.argmin / argmax of the window)
+ *   op 7 rank:          of win[w-1] within the window: (2 #less + #equal + 1) / 2 with #equal counting the day itself, compares < and
+ *                       ==; mode 0: that rank in 1 .. w, mode 1: the rank / dw
+ *   op 8 decay_linear:  (sum of (k + 1) win[k]) / (w (w + 1) / 2)
+ *   op 9 delay:         x[t-w] where t >= w and it is non-null and not NaN (+-inf passes), else NULL
+ *   op 10 delta:        x[t] - x[t-w] where t >= w and both are non-null and finite, else NULL
+ * A result that comes out NaN is NULL (+-inf passes).  1 <= window <= PQ_FACTOR_ROLLING_MAX_WINDOW and at least the op's minimum; mode
+ * is rank's alone, 0 for every other op; anything else is PQ_ERR_ARG.  out must NOT overlap x (PQ_ERR_ARG): a workgroup reads a halo of
+ * days that another workgroup writes.  Ragged batches and suite recording are refused; n_series = 0 or len = 0 launches nothing.  No
+ * workspace. */
+pq_status pq_factor_ts(pq_ctx *, const pq_batch *, const double *x, int32_t op, int64_t window, int32_t mode, double *out);
+/* the two-column operators on the same sample rule applied to both columns: mx = (sum x) / dw, my = (sum y) / dw, then in one ascending
+ * pass sxy = sum (x - mx)(y - my), sxx = sum (x - mx)^2, syy = sum (y - my)^2.
+ *   op 0 cov:   sxy / (w - 1)
+ *   op 1 corr:  sxy / (sqrt(sxx) sqrt(syy)); NULL at sxx == 0 or syy == 0
+ * 2 <= window <= PQ_FACTOR_ROLLING_MAX_WINDOW; out must overlap neither x nor y; otherwise as pq_factor_ts. */
+pq_status pq_factor_ts_pair(pq_ctx *, const pq_batch *, const double *x, const double *y, int32_t op, int64_t window, double *out);
+
 /* ---- suites: record many calls, replay them as a few chip-filling grids ----
  * One indicator over N symbols is only N/64 wavefronts -- far too few for 256 CUs -- but a DataFrame query asks
  * for many indicators at once (df.with_columns([...]) in the reference; Polars then calls the plugin once per

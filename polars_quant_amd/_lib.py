@@ -150,6 +150,8 @@ factor_weighted        i pBppplip
 factor_binary          i pBppip
 factor_rolling         i pBpillp
 factor_rolling_regress i pBpiuplppppp
+factor_ts              i pBpilip
+factor_ts_pair         i pBppilp
 suite_begin            i pB
 suite_end              i pp
 suite_abort            i p

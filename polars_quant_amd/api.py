@@ -986,6 +986,50 @@ def factor_rolling(x, op: int, window: int, skip: int = 0):
     return _build_call("pq_factor_rolling", [x], lambda b, dev: (int(op), int(window), int(skip)))
 
 
+TS_OPS = {"sum": 0, "std": 1, "zscore": 2, "min": 3, "max": 4, "argmin": 5, "argmax": 6, "rank": 7, "decay_linear": 8, "delay": 9,
+          "delta": 10}                                         # pq_factor_ts's op codes
+TS_PAIR_OPS = {"cov": 0, "corr": 1}                            # pq_factor_ts_pair's op codes
+TS_MIN_WINDOW = {"sum": 1, "std": 2, "zscore": 2, "min": 1, "max": 1, "argmin": 1, "argmax": 1, "rank": 1, "decay_linear": 1, "delay": 1,
+                 "delta": 1, "cov": 2, "corr": 2}              # per op name of either table
+
+
+def _ts_args(table, op, window, mode=0):
+    """argument checks of factor_ts / factor_ts_pair that need no device: op a code of `table`, window an integer in the op's range,
+    mode 0, or 1 for rank"""
+    names = {code: nm for nm, code in table.items()}
+    if isinstance(op, bool) or not isinstance(op, (int, np.integer)) or op not in names:
+        raise ValueError(f"op must be one of the integer codes {sorted(names)} ({table}), not {op!r}")
+    for nm, v in (("window", window), ("mode", mode)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{nm} must be an integer, not {v!r}")
+    lo = TS_MIN_WINDOW[names[op]]
+    if not lo <= window <= ROLLING_MAX_WINDOW:
+        raise ValueError(f"window must be in {lo}..{ROLLING_MAX_WINDOW} for op {op} ({names[op]}), not {window!r}")
+    if mode != 0 and not (mode == 1 and op == TS_OPS["rank"] and table is TS_OPS):
+        raise ValueError(f"mode must be 0, or 1 (rank / window) for rank alone, not {mode!r}")
+
+
+def factor_ts(x, op: int, window: int, mode: int = 0):
+    """D-29: one time-series operator along the days of every symbol of an [N, T] column -> device tensor [N, T], NULL unless every
+    value of the row's window is non-null and finite, and where the result is NaN.  op (TS_OPS) over the last `window` days, oldest to
+    newest: sum; std (sample, ddof 1); zscore (today - mean) / std; min; max; argmin / argmax (0-based offset from the window's oldest
+    day, ties to the oldest); rank of today's value within the window (average rank in 1 .. window, mode 1: divided by the window);
+    decay_linear (weights 1 .. window, the newest day the heaviest); delay x[t - window]; delta x[t] - x[t - window].
+    1 <= window <= 1024 and at least TS_MIN_WINDOW[name]; mode is rank's alone."""
+    _ts_args(TS_OPS, op, window, mode)
+    _build_shapes(("x",), (x,))
+    return _build_call("pq_factor_ts", [x], lambda b, dev: (int(op), int(window), int(mode)))
+
+
+def factor_ts_pair(x, y, op: int, window: int):
+    """D-29: the covariance (op 0, ddof 1) or the Pearson correlation (op 1; TS_PAIR_OPS) of two [N, T] columns over the last `window`
+    days of every symbol -> device tensor [N, T], NULL unless both columns are non-null and finite on every day of the window, and for
+    the correlation where either is constant over it.  2 <= window <= 1024."""
+    _ts_args(TS_PAIR_OPS, op, window)
+    _build_shapes(("x", "y"), (x, y))
+    return _build_call("pq_factor_ts_pair", [x, y], lambda b, dev: (int(op), int(window)))
+
+
 ROLLING_REGRESS_MAX_K = 4                                      # PQ_ROLLING_REGRESS_MAX_K
 ROLLING_REGRESS_OUTPUTS = ("beta", "alpha", "resid_std", "r_squared", "resid")   # pq_factor_rolling_regress's output pointers, in order
 

@@ -6,7 +6,9 @@ regressions and significance tests ic_test / factor_return / fama_macbeth / time
 tests ic_decay / subsample_test / subgroup_test (decision D-18), and the multi-factor orthogonalization / neutralization Factor().clean
 (decision D-19).  The common technical factors moving_average / momentum / volatility / skewness / relative_strength
 (README.md:1423-1426, :1472-1477; decision D-21) roll along the days of every symbol, and so do the two-column ones rolling_regression /
-rolling_beta / idiosyncratic_volatility (decision D-28: rolling-window OLS).  README-only in the reference.  Inputs are [N, T] arrays (symbol-major, like every other column of this package): the
+rolling_beta / idiosyncratic_volatility (decision D-28: rolling-window OLS).  The time-series operators of factor construction ts_sum /
+ts_std / ts_zscore / ts_min / ts_max / ts_argmin / ts_argmax / ts_rank / decay_linear / delay / delta / ts_cov / ts_corr (decision
+D-29, beyond the README) are the windowed operators that formulaic alphas are written in.  README-only in the reference.  Inputs are [N, T] arrays (symbol-major, like every other column of this package): the
 factor and the forward return of every symbol on every day.
 `clean` is the README's factor cleaning step that comes before the evaluation (decision D-16).
 `portfolio_backtest` (decision D-27, beyond the README) holds the groups of the sorts as portfolios: rebalance days, weights, drift and
@@ -95,6 +97,66 @@ class Factor:
     def idiosyncratic_volatility(self, returns, factors, window=60):
         """-> [N, T]: the residual std of the rolling OLS of the returns on the factors (not annualised)"""
         return _api.factor_rolling_regress(returns, factors, window, outputs=("resid_std",))["resid_std"]
+
+    # ---- D-29: the time-series operators of factor construction, along the days of every symbol over the last `window` days (oldest to
+    # newest); a row is NULL unless every value of its window is non-null and finite, so is a result that comes out NaN;
+    # 1 <= window <= 1024; every result is a device f64 [N, T] column, so -rank(ts_corr(open, volume, 10)) never leaves the device
+    def ts_sum(self, x, window):
+        """-> the sum of the last `window` days (moving_average times the window, before its division)"""
+        return _api.factor_ts(x, _api.TS_OPS["sum"], window)
+
+    def ts_std(self, x, window):
+        """-> the sample std (ddof 1) of the last `window` days (window >= 2); on period-1 returns this is volatility"""
+        return _api.factor_ts(x, _api.TS_OPS["std"], window)
+
+    def ts_zscore(self, x, window):
+        """-> (today's value - the window's mean) / ts_std (window >= 2); NULL over a constant stretch"""
+        return _api.factor_ts(x, _api.TS_OPS["zscore"], window)
+
+    def ts_min(self, x, window):
+        """-> the smallest value of the last `window` days"""
+        return _api.factor_ts(x, _api.TS_OPS["min"], window)
+
+    def ts_max(self, x, window):
+        """-> the largest value of the last `window` days"""
+        return _api.factor_ts(x, _api.TS_OPS["max"], window)
+
+    def ts_argmin(self, x, window):
+        """-> where the window's minimum lies: the 0-based offset from the window's OLDEST day, 0 .. window - 1, as f64 (numpy.argmin
+        of the window; ties go to the oldest day, -0 ties with +0)"""
+        return _api.factor_ts(x, _api.TS_OPS["argmin"], window)
+
+    def ts_argmax(self, x, window):
+        """-> where the window's maximum lies: the 0-based offset from the window's OLDEST day, 0 .. window - 1, as f64 (numpy.argmax
+        of the window; ties go to the oldest day); window - 1 - ts_argmax is "days since the high" """
+        return _api.factor_ts(x, _api.TS_OPS["argmax"], window)
+
+    def ts_rank(self, x, window, pct=False):
+        """-> the average rank of today's value among the last `window` days, 1 .. window (ties share the mean of their positions:
+        pandas rolling(window).rank(method="average")), pct=True: divided by the window"""
+        return _api.factor_ts(x, _api.TS_OPS["rank"], window, 1 if pct else 0)
+
+    def decay_linear(self, x, window):
+        """-> the linearly weighted mean of the last `window` days, weights 1 (oldest) .. window (today) over window (window + 1) / 2"""
+        return _api.factor_ts(x, _api.TS_OPS["decay_linear"], window)
+
+    def delay(self, x, periods=1):
+        """-> x[t - periods], NULL for t < periods and where that value is NULL or NaN (+-inf passes); 1 <= periods <= 1024"""
+        return _api.factor_ts(x, _api.TS_OPS["delay"], periods)
+
+    def delta(self, x, periods=1):
+        """-> x[t] - x[t - periods], NULL unless both are non-null and finite; 1 <= periods <= 1024"""
+        return _api.factor_ts(x, _api.TS_OPS["delta"], periods)
+
+    def ts_cov(self, x, y, window):
+        """-> the sample covariance (ddof 1) of x and y over the last `window` days (window >= 2); NULL unless both columns are
+        non-null and finite on every day of the window"""
+        return _api.factor_ts_pair(x, y, _api.TS_PAIR_OPS["cov"], window)
+
+    def ts_corr(self, x, y, window):
+        """-> the Pearson correlation of x and y over the last `window` days (window >= 2), on ts_cov's sample; NULL where either
+        column is constant over the window"""
+        return _api.factor_ts_pair(x, y, _api.TS_PAIR_OPS["corr"], window)
 
     def ic(self, factor, next_return):
         """-> (ic [T], n_valid [T]): Pearson correlation across symbols, per day"""
