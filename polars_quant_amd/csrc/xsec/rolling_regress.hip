@@ -9,22 +9,17 @@
 // ascending day order from 0.0; the L D L^T core is xsec_ols.h's.  The row's solve is the first half of xo_fit (b and the intercept,
 // no standard errors) written out here on xo_ldl / xo_forward / xo_back: through xo_fit the kernel compiled to other code and one
 // timing left the parent's range (EXPERIMENTS.md, "One fit and one window stage for the regress / rolling kernels").
-//  launch:  one workgroup of 256 threads per (symbol, tile of 256 days), walked with a grid stride, as rl_window_kernel: the tile
-//           constant, the job split, the launch shape and the overlap check are xsec_window.h's.
-//  stage:   the tile and a halo of window - 1 earlier days of all K + 1 columns go into dynamic LDS, sized by the actual window
-//           ((K + 1)(255 + window) f64 and (255 + window) i32: 6.3 KB at K = 1, window = 60; 56.3 KB at K = 4, window = 1024), loads
-//           coalesced along days.  One last[] array marks an entry unusable if any column is; xw_last_scan (xsec_window.h) turns it
-//           into "the last unusable entry at or before l", so "is the whole window usable" is one compare.
-//  rows:    each thread evaluates its own row's three passes directly out of LDS (sliding sums would not keep the order of the
-//           additions): consecutive threads read consecutive 8-byte words of one column at every step, so no bank conflict.  The kernel
-//           is templated on K: every index of the xo_* arrays is static and nothing goes to scratch (rolling_regress.resources.txt).
+//  stage:   xsec_window.h's, on all K + 1 columns in dynamic LDS sized by the actual window ((K + 1)(255 + window) f64 and (255 + window)
+//           i32: 6.3 KB at K = 1, window = 60; 56.3 KB at K = 4, window = 1024); one last[] marks an entry unusable if any column is.
+//           The kernel keeps its own copy of xw_walk's loop, as it keeps its own solve: through xw_walk<K + 1> it compiled to 77 / 117 /
+//           105 / 113 VGPRs against 77 / 91 / 125 / 134 (EXPERIMENTS.md, "One window walk for the rolling, ts and OLS kernels").
+//  rows:    three passes over the window.  The kernel is templated on K: every index of the xo_* arrays is static and nothing goes to
+//           scratch (rolling_regress.resources.txt).
 #include "xsec_ols.h"
 #include "xsec_window.h"
 
 namespace {
 
-constexpr int RR_TILE = XW_TILE;                                // days per workgroup = threads per workgroup
-constexpr int RR_MAX_W = PQ_FACTOR_ROLLING_MAX_WINDOW;
 constexpr int RR_MAX_K = PQ_ROLLING_REGRESS_MAX_K;
 
 struct RrIn {
@@ -39,15 +34,14 @@ struct RrOut {             // each may be null: not written
     double *alpha, *resid_std, *r2, *resid;
 };
 
-// one workgroup per (symbol, tile of RR_TILE days); entry l of the staged stretch is day g0 + l, row t0 + i is entry i + w - 1 and its
-// window is entries [i, i + w).  LDS: column c (0 .. K-1 the regressors, K = y) at val + c * M, then last[M].
+// xw_walk<K + 1>, written out (see above).  LDS: column c (0 .. K-1 the regressors, K = y) at val + c * M, then last[M].
 template <int K>
-__global__ __launch_bounds__(RR_TILE) void rr_window_kernel(RrIn in, RrOut out, int w, int64_t chunks, int64_t total) {
+__global__ __launch_bounds__(XW_TILE) void rr_window_kernel(RrIn in, RrOut out, int w, int64_t chunks, int64_t total) {
     extern __shared__ double rr_lds[];
-    __shared__ int wave_last[RR_TILE / 64];
+    __shared__ int wave_last[XW_TILE / 64];
     constexpr int NV = K + 1, NA = xo_tri(NV);
     const Dims d = in.d;
-    const int tid = threadIdx.x, M = RR_TILE + w - 1;
+    const int tid = threadIdx.x, M = XW_TILE + w - 1;
     double *val = rr_lds;
     int *last = (int *)(rr_lds + (size_t)NV * M);               // index of the last unusable entry <= l, -1 without one
     const int64_t plane = d.n * d.stride;
@@ -57,7 +51,7 @@ __global__ __launch_bounds__(RR_TILE) void rr_window_kernel(RrIn in, RrOut out, 
 #pragma unroll
         for (int c = 0; c < K; c++) col[c] = in.x[c] + (((in.series >> c) & 1u) ? 0 : s * d.stride);
         col[K] = in.y + s * d.stride;
-        for (int l = tid; l < M; l += RR_TILE) {
+        for (int l = tid; l < M; l += XW_TILE) {
             const int64_t g = g0 + l;
             const bool inside = g >= 0 && g < d.len;
             bool ok = inside;
@@ -156,18 +150,18 @@ pq_status pq_factor_rolling_regress(pq_ctx *ctx, const pq_batch *b, const double
     PQ_TRY(pq_check(ctx, b));
     PQ_REQUIRE(n_x >= 1 && n_x <= RR_MAX_K, "pq_factor_rolling_regress: n_x must be in [1, 4]");
     PQ_REQUIRE((series_mask >> n_x) == 0, "pq_factor_rolling_regress: series_mask names a regressor beyond n_x");
-    PQ_REQUIRE(window >= n_x + 2 && window <= RR_MAX_W, "pq_factor_rolling_regress: window must be in [n_x + 2, 1024]");
-    if (ctx->rec) { pq_set_error("pq_factor_rolling_regress cannot be recorded into a suite"); return PQ_ERR_UNSUPPORTED; }
-    PQ_REQUIRE(!b->offsets, "pq_factor_rolling_regress: ragged batches are not supported (a column is [n_series][stride])");
-    if (b->len == 0 || b->n_series == 0) return PQ_OK;
+    PQ_REQUIRE(window >= n_x + 2 && window <= XW_MAX_W, "pq_factor_rolling_regress: window must be in [n_x + 2, 1024]");
+    XwGrid g;
+    PQ_TRY(xw_prepare(ctx, b, "pq_factor_rolling_regress cannot be recorded into a suite",
+                      "pq_factor_rolling_regress: ragged batches are not supported (a column is [n_series][stride])", PQ_ERR_ARG, &g));
+    if (g.total == 0) return PQ_OK;
     PQ_REQUIRE(x && y, "pq_factor_rolling_regress: null pointer");
+    const Dims d = g.d;
     RrIn in{};
     in.y = y;
     in.series = series_mask;
-    in.d = dims_of(b);
-    const Dims d = in.d;
-    // a workgroup reads a halo of days that another workgroup writes: no output may overlap an input or another output
-    const uintptr_t colb = ((uintptr_t)(d.n - 1) * (uintptr_t)d.stride + (uintptr_t)d.len) * 8, plane = (uintptr_t)d.n * (uintptr_t)d.stride * 8;
+    in.d = d;
+    const uintptr_t plane = xw_plane_bytes(d), colb = plane - (uintptr_t)(d.stride - d.len) * 8;   // a column without its last padding
     XwSpan ins[RR_MAX_K + 1], outs[5];
     int n_in = 0, n_out = 0;
     ins[n_in++] = xw_span(y, colb);
@@ -179,19 +173,14 @@ pq_status pq_factor_rolling_regress(pq_ctx *ctx, const pq_batch *b, const double
     if (beta) outs[n_out++] = xw_span(beta, (uintptr_t)(n_x - 1) * plane + colb);
     for (double *p : {alpha, resid_std, r_squared, resid})
         if (p) outs[n_out++] = xw_span(p, colb);
-    for (int i = 0; i < n_out; i++) {
-        for (int j = 0; j < n_in; j++)
-            PQ_REQUIRE(xw_disjoint(outs[i], ins[j]), "pq_factor_rolling_regress: an output must not overlap an input");
-        for (int j = 0; j < i; j++)
-            PQ_REQUIRE(xw_disjoint(outs[i], outs[j]), "pq_factor_rolling_regress: two outputs must not overlap");
-    }
+    PQ_TRY(xw_no_overlap(outs, n_out, ins, n_in, "pq_factor_rolling_regress: an output must not overlap an input",
+                         "pq_factor_rolling_regress: two outputs must not overlap"));
     if (n_out == 0) return PQ_OK;
     const RrOut out{beta, alpha, resid_std, r_squared, resid};
     const int w = (int)window;
-    const XwGrid g = xw_grid(d);
-    const size_t M = (size_t)(RR_TILE + w - 1), lds = (size_t)(n_x + 1) * M * 8 + M * 4;
+    const size_t M = (size_t)(XW_TILE + w - 1), lds = (size_t)(n_x + 1) * M * 8 + M * 4;
     xo_with_k<RR_MAX_K>(n_x, [&](auto K) {
-        hipLaunchKernelGGL(rr_window_kernel<decltype(K)::value>, g.grid, dim3(RR_TILE), lds, ctx->stream, in, out, w, g.chunks, g.total);
+        hipLaunchKernelGGL(rr_window_kernel<decltype(K)::value>, g.grid, dim3(XW_TILE), lds, ctx->stream, in, out, w, g.chunks, g.total);
     });
     PQ_HIP_TRY(hipGetLastError());
     return PQ_OK;
