@@ -796,6 +796,34 @@ pq_status pq_factor_ts(pq_ctx *, const pq_batch *, const double *x, int32_t op, 
  * 2 <= window <= PQ_FACTOR_ROLLING_MAX_WINDOW; out must overlap neither x nor y; otherwise as pq_factor_ts. */
 pq_status pq_factor_ts_pair(pq_ctx *, const pq_batch *, const double *x, const double *y, int32_t op, int64_t window, double *out);
 
+/* ---- rank 3, continued: K tested factors into one composite score, Factor.combine (beyond the README: the step between the factor
+ * tests and portfolio_backtest; decision D-30 in DESIGN.md section 2).
+ * Weights: ic is a DEVICE array [k][len], row j the IC series of factor j (pq_factor_ic's), 1 <= k <= PQ_REGRESS_MAX_K; weights [k][len].
+ * w = window; the window of day t is the days t-lag-w+1 .. t-lag, so with lag >= 1 a weight never sees the IC of its own day.  Row t is
+ * NULL in all k weights unless the whole window lies in [0, len) and all k w values are non-NULL (pq_rolling_ic's rule, across the
+ * factors).  Every sum starts at 0.0 and adds the window in ascending day order, evaluated directly.
+ *   method 0 PQ_COMBINE_IC:       w_j = m_j = (sum ic_j) / w                                                   w >= 1
+ *   method 1 PQ_COMBINE_ICIR:     w_j = m_j / sd_j, sd_j = sqrt((sum (ic_j - m_j)^2) / (w - 1)); the row NULL unless every sd_j > 0    w >= 2
+ *   method 2 PQ_COMBINE_MAX_ICIR: w = C^-1 m, C[j][l] = (sum (ic_j - m_j)(ic_l - m_l)) / (w - 1), solved as C = L D L^T in D-17's order
+ *                                 without an intercept; the row NULL where a pivot D_j <= 1e-12 C[j][j]         w >= k + 1
+ * A weight that comes out NaN makes the row NULL.  Methods 0 and 1 are pq_rolling_ic(ic_j, w)'s rolling_ic and rolling_ir read at day
+ * t - lag, bit for bit.  window <= PQ_FACTOR_ROLLING_MAX_WINDOW, 0 <= lag <= PQ_FACTOR_ROLLING_MAX_WINDOW; k, method, window or lag out
+ * of range, a null pointer and weights overlapping ic are PQ_ERR_ARG; suite recording is refused; len = 0 launches nothing.
+ * Composite: factors is a HOST array of k device pointers, each [n_series][stride] on the batch's row pitch, as out; weights is the
+ * DEVICE array [k][len].  Per cell acc = sum_j weights[j][t] * factors[j][s][t] (j ascending from 0.0, product and sum rounded
+ * separately); normalize != 0 stores acc / D[t], D[t] = sum_j |weights[j][t]| (j ascending from 0.0), normalize == 0 stores acc.  NULL
+ * unless all k cells are non-null and finite (D-19's common sample), and where a weight of the day is NULL or NaN, where normalize is
+ * set and D[t] == 0, and where the result is NaN.  The factors are taken as given: standardise them first.  k out of range, a null
+ * pointer and out overlapping a factor or the weights are PQ_ERR_ARG; ragged batches and suite recording are refused
+ * (PQ_ERR_UNSUPPORTED); n_series = 0 or len = 0 launches nothing.  No workspace. */
+#define PQ_COMBINE_IC 0
+#define PQ_COMBINE_ICIR 1
+#define PQ_COMBINE_MAX_ICIR 2
+pq_status pq_factor_combine_weights(pq_ctx *, const double *ic /* device [k][len] */, int32_t k, int64_t len, int32_t method,
+                                    int64_t window, int64_t lag, double *weights /* [k][len] */);
+pq_status pq_factor_combine(pq_ctx *, const pq_batch *, const double *const *factors, int32_t k, const double *weights /* device [k][len] */,
+                            int32_t normalize, double *out);
+
 /* ---- suites: record many calls, replay them as a few chip-filling grids ----
  * One indicator over N symbols is only N/64 wavefronts -- far too few for 256 CUs -- but a DataFrame query asks
  * for many indicators at once (df.with_columns([...]) in the reference; Polars then calls the plugin once per

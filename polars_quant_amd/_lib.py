@@ -152,6 +152,8 @@ factor_rolling         i pBpillp
 factor_rolling_regress i pBpiuplppppp
 factor_ts              i pBpilip
 factor_ts_pair         i pBppilp
+factor_combine_weights i ppilillp
+factor_combine         i pBpipip
 suite_begin            i pB
 suite_end              i pp
 suite_abort            i p

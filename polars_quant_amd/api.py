@@ -1030,6 +1030,99 @@ def factor_ts_pair(x, y, op: int, window: int):
     return _build_call("pq_factor_ts_pair", [x, y], lambda b, dev: (int(op), int(window)))
 
 
+COMBINE_METHODS = {"ic": 0, "icir": 1, "max_icir": 2}          # pq_factor_combine_weights' method codes (PQ_COMBINE_*)
+COMBINE_MAX_LAG = ROLLING_MAX_WINDOW                           # the window's bound holds for the lag
+
+
+def combine_min_window(method: int, k: int) -> int:
+    """the shortest window of a method code for k factors: 1 (ic), 2 (icir), k + 1 (max_icir)"""
+    return (1, 2, k + 1)[method]
+
+
+def _combine_weight_args(k, method, window, lag):
+    """argument checks of factor_combine_weights that need no device: k factors, method a code of COMBINE_METHODS, window an integer in
+    the method's range, lag an integer in 0..1024"""
+    if isinstance(method, bool) or not isinstance(method, (int, np.integer)) or method not in COMBINE_METHODS.values():
+        raise ValueError(f"method must be one of the integer codes {sorted(COMBINE_METHODS.values())} ({COMBINE_METHODS}), not {method!r}")
+    if not 1 <= k <= REGRESS_MAX_K:
+        raise ValueError(f"the number of factors must be in 1..{REGRESS_MAX_K}, not {k}")
+    for nm, v in (("window", window), ("lag", lag)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{nm} must be an integer, not {v!r}")
+    lo = combine_min_window(int(method), k)
+    if not lo <= window <= ROLLING_MAX_WINDOW:
+        raise ValueError(f"window must be in {lo}..{ROLLING_MAX_WINDOW} for method {method} and {k} factors, not {window!r}")
+    if not 0 <= lag <= COMBINE_MAX_LAG:
+        raise ValueError(f"lag must be in 0..{COMBINE_MAX_LAG}, not {lag!r}")
+
+
+def factor_combine_weights(ic, method: int, window: int, lag: int = 1):
+    """D-30: the combination weights of K factors from their IC series.  ic: [K, T] (row k the daily IC of factor k, factor_ic's; a
+    [T] series is K = 1), 1 <= K <= 8 -> device tensor [K, T].  The weights of day t come from the `window` days that end at t - lag:
+    method (COMBINE_METHODS) 0 ic: the mean IC; 1 icir: mean / sample std; 2 max_icir: C^-1 mean with C the sample covariance of the K
+    series.  Day t is NULL in all K rows unless its whole window lies inside the series and holds no NULL IC, and where a std is not
+    > 0, C is singular or a weight comes out NaN.  window: 1.. / 2.. / K + 1..1024, lag: 0..1024."""
+    s = _shape(ic)
+    if len(s) not in (1, 2):
+        raise ValueError(f"ic must be [K, T] or [T], not {s}")
+    K = 1 if len(s) == 1 else s[0]
+    _combine_weight_args(K, method, window, lag)
+    if isinstance(ic, torch.Tensor) and ic.is_cuda:         # K dense series, not a batch on a row pitch: no layout to warn about
+        t = ic.to(torch.float64).reshape(K, -1).contiguous()
+    else:
+        t = _to_device(ic)[0].contiguous()
+    out = torch.empty_like(t)
+    if t.numel():
+        _call("pq_factor_combine_weights", t.device, t, K, t.shape[1], int(method), int(window), int(lag), out)
+    return out
+
+
+def _combine_args(factors, weights):
+    """argument checks of factor_combine that need no device: factors a list / tuple of 1..8 [N, T] arrays of one shape or one
+    [K, N, T] array, weights [K] or [K, T] -> (list of factor columns, (N, T))"""
+    cols = _columns(factors, "the number of factors", 1, REGRESS_MAX_K, 3, "factors must be a list of [N, T] arrays or one [K, N, T] array")
+    s0 = _shape(cols[0])
+    if len(s0) != 2:
+        raise ValueError(f"factor 0 must be [N, T], not {s0}")
+    _regress_args(cols, cols[0], False)
+    if weights is not None and _shape(weights) not in ((len(cols),), (len(cols), s0[1])):
+        raise ValueError(f"weights must be [K] or [K, T] with K = {len(cols)}, T = {s0[1]}, not {_shape(weights)}")
+    return cols, s0
+
+
+def combine_weight_rows(weights, K: int, T: int, dev):
+    """weights [K] or [K, T] -> the contiguous device f64 [K, T] that pq_factor_combine reads; [K] is broadcast along the days on the
+    device"""
+    w = weights if isinstance(weights, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(weights, dtype=np.float64)))
+    w = w.to(device=dev, dtype=torch.float64)
+    if w.dim() == 1:
+        w = w.reshape(K, 1).expand(K, T)
+    return w.contiguous()
+
+
+def factor_combine(factors, weights, normalize: bool = True):
+    """D-30: the composite of K factors (a list of K [N, T] arrays or one [K, N, T] array, 1 <= K <= 8) under per-day weights [K, T]
+    (factor_combine_weights'; or [K], the same on every day) -> device tensor [N, T]: sum_k weights[k, t] * factors[k][s, t], with
+    normalize divided by sum_k |weights[k, t]|.  NULL unless all K cells are non-null and finite, and where a weight of the day is NULL
+    or NaN, where normalize is set and the weights' absolute sum is 0, and where the result is NaN.  The factors are taken as given:
+    standardise them first (factor_normalize, factor_clean)."""
+    cols, (n, T) = _combine_args(factors, weights)
+    K = len(cols)
+    if n == 0 or T == 0:    # no cell: nothing is uploaded or launched
+        _require_gpu()
+        c0 = cols[0]
+        dev = c0.device if isinstance(c0, torch.Tensor) and c0.is_cuda else torch.device("cuda", torch.cuda.current_device())
+        return torch.empty((n, T), dtype=torch.float64, device=dev)
+    mats = _same_layout([_to_device(c)[0] for c in cols])
+    dev = mats[0].device
+    b = _batch(mats[0])
+    w = combine_weight_rows(weights, K, T, dev)
+    out = torch.empty((n, b.stride), dtype=torch.float64, device=dev)
+    fp = (C.c_void_p * K)(*[m.data_ptr() for m in mats])
+    _call("pq_factor_combine", dev, b, fp, K, w, 1 if normalize else 0, out)
+    return out[:, :T]
+
+
 ROLLING_REGRESS_MAX_K = 4                                      # PQ_ROLLING_REGRESS_MAX_K
 ROLLING_REGRESS_OUTPUTS = ("beta", "alpha", "resid_std", "r_squared", "resid")   # pq_factor_rolling_regress's output pointers, in order
 

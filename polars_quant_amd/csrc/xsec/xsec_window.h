@@ -1,5 +1,5 @@
 // xsec/xsec_window.h -- the window walk of the kernels that evaluate a window along the days of every symbol: rolling.hip (D-21),
-// rolling_regress.hip (D-28) and tsops.hip (D-29).  All launch one workgroup of XW_TILE threads per (symbol, tile of XW_TILE days), walked
+// rolling_regress.hip (D-28), tsops.hip (D-29) and combine.hip's weights (D-30: one "symbol" of K IC series).  All launch one workgroup of XW_TILE threads per (symbol, tile of XW_TILE days), walked
 // with a grid stride.
 //  stage:   a workgroup stages its tile and a halo of window - 1 earlier days in LDS, M = XW_TILE + window - 1 entries per column, loads
 //           coalesced along days, and beside them last[l] = l where entry l is unusable, -1 where it is usable.

@@ -13,6 +13,8 @@ factor and the forward return of every symbol on every day.
 `clean` is the README's factor cleaning step that comes before the evaluation (decision D-16).
 `portfolio_backtest` (decision D-27, beyond the README) holds the groups of the sorts as portfolios: rebalance days, weights, drift and
 a fee on the traded value, as value curves with the backtest report's statistics; it takes the factor and the PRICE of every symbol.
+`combine` (decision D-30, beyond the README) is the step between the two: K tested factors into the one score that `portfolio_backtest`
+takes, by equal, trailing-IC, trailing-ICIR or max-IR weights that only use ICs already known on the day the weight is used.
 """
 from __future__ import annotations
 
@@ -244,6 +246,46 @@ class Factor:
         cols = list(range(15)) + (list(range(38, 45)) if benchmark is not None else [])
         out["statistics"] = {REPORT_COLS[c]: rep[:, c] for c in cols}
         return out
+
+    # ---- D-30: K tested factors into the one score that quantile / long_short / portfolio_backtest take
+    def combine(self, factors, next_return=None, method="icir", window=60, lag=1, rank=False, weights=None, normalize=True):
+        """factors: a list of K [N, T] arrays or one [K, N, T] array (1 <= K <= 8), taken as given: standardise them first
+        (Factor.normalize, clean), or the weights mix their scales.  -> {"composite": [N, T], "weights": [K, T], "ic": [K, T] or None}.
+        composite[s, t] = sum_k weights[k, t] * factors[k][s, t], with normalize divided by sum_k |weights[k, t]|; NULL unless all K
+        factors are non-null and finite there and the day has its K weights.  method "equal": weight 1.0 on every day (no
+        next_return); "ic" / "icir" / "max_icir": from the daily IC (rank=True: Rank-IC) of each factor against next_return, over the
+        `window` days that end at day t - lag: the mean IC, mean / sample std, and C^-1 mean with C the sample covariance of the K IC
+        series (window >= 1 / 2 / K + 1; a day is NULL unless its window is complete and holds no NULL IC).  weights= ([K] or [K, T])
+        replaces the method; next_return must then be left out.
+        Look-ahead: the IC of day d uses the return that follows day d, so it is known only once that return is.  With an h-day forward
+        return (next_return[s, d] = the return over days d .. d + h) pass lag >= h: the weights of day t then use ICs up to day t - h
+        only.  lag=0 lets day t weigh itself by a return that is not known on day t."""
+        methods = ("equal",) + tuple(_api.COMBINE_METHODS)
+        if weights is None and method not in methods:
+            raise ValueError(f"method must be one of {methods}, not {method!r}")
+        if weights is not None and next_return is not None:
+            raise ValueError("weights replaces the method: leave next_return out")
+        from_ic = weights is None and method != "equal"
+        if from_ic and next_return is None:
+            raise ValueError(f"method {method!r} needs next_return")
+        cols, (n, T) = _api._combine_args(factors, weights)
+        K = len(cols)
+        if from_ic:
+            _api._combine_weight_args(K, _api.COMBINE_METHODS[method], window, lag)
+            if _api._shape(next_return) != (n, T):
+                raise ValueError(f"next_return must have the factors' shape {(n, T)}, not {_api._shape(next_return)}")
+        cols = [_api._to_device(c)[0] for c in cols]            # uploaded once for the ICs and the composite
+        dev = cols[0].device
+        ic = None
+        if from_ic:
+            r = _api._to_device(next_return)[0]
+            ic = torch.stack([_api.factor_ic(c, r, 1 if rank else 0)[0] for c in cols])
+            w = _api.factor_combine_weights(ic, _api.COMBINE_METHODS[method], window, lag)
+        elif weights is None:
+            w = torch.ones((K, T), dtype=torch.float64, device=dev)
+        else:
+            w = _api.combine_weight_rows(weights, K, T, dev)
+        return {"composite": _api.factor_combine(cols, w, normalize), "weights": w, "ic": ic}
 
     # ---- D-17: regressions and significance tests (README.md:1521-1600)
     def ic_test(self, factor, next_return, method="pearson"):
