@@ -589,6 +589,23 @@ pq_status pq_factor_coverage(pq_ctx *, const pq_batch *, const double *factor, d
 /* statistics of an IC series over its non-NaN days: out[5] = n_days, mean, std (ddof 1), ir = mean / std (not annualised),
  * win_rate = #(ic > 0) / n_days; all but n_days null below 2 days, ir null where std is 0 */
 pq_status pq_ic_stats(pq_ctx *, const double *ic, int64_t len, double *out);
+/* two-way (double) sort, Factor.double_sort (beyond the README; decision D-31 in DESIGN.md section 2): control (A) and factor (B) sorted
+ * into n_control x n_quantiles cells, both in [2, 10]; mode 0 independent, 1 dependent (B sorted inside each control bucket).  The day's
+ * sample = the symbols where control, factor and return are all non-null and finite, n its size; m of a key in a set = a + b of its tie
+ * run in that set's ascending sort, as above.  la = floor(m_A Qa / 2n) over the sample; independent: lb = floor(m_B Qb / 2n) over the
+ * sample, the day PQ_LABEL_OUT where n < max(Qa, Qb); dependent: the day PQ_LABEL_OUT where n < Qa, else inside control bucket a of n_a
+ * members lb = floor(m_{B|a} Qb / 2 n_a) with the tie runs taken among the bucket's members, and a bucket with n_a < Qb puts its members
+ * in no cell (PQ_LABEL_MID).  labels: uint8 la * Qb + lb (PQ_LABEL_OUT outside the sample), [n_series][stride], NULL: not written.  With
+ * C = Qa Qb cells: mean_return / count / turnover [C][len] by the rules above; spread_factor [Qa + 1][len]: row a = mean[a][Qb - 1] -
+ * mean[a][0] (null where either is), row Qa = the rows summed in ascending a from 0.0 and divided by Qa (null where any row is);
+ * spread_control [Qb + 1][len]: mean[Qa - 1][b] - mean[0][b] and its average over b; summary [C + Qa + Qb + 2][5]: the cells (with
+ * mean_turnover), then the spread_factor rows, then the spread_control rows (mean_turnover null).  The limits of pq_factor_quantiles;
+ * uses the context workspace (~18 bytes per cell, ~26 above 16384 series, and 16 bytes per cell of the grid, day and block of 256
+ * symbols).  No ragged batches, not recordable; len == 0 returns PQ_OK. */
+pq_status pq_factor_double_sort(pq_ctx *, const pq_batch *, const double *control, const double *factor, const double *fwd_return,
+                                int32_t n_control, int32_t n_quantiles, int32_t mode, uint8_t *labels /* NULL: not written */,
+                                double *mean_return, int32_t *count, double *turnover, double *spread_factor, double *spread_control,
+                                double *summary);
 
 /* ---- rank 3, continued: the group portfolios of D-15's labels held between rebalance days, with weights, drift and a fee on the
  * traded value, Factor.portfolio_backtest (beyond the README; decision D-27 in DESIGN.md section 2).  labels: uint8 [n_series][stride]

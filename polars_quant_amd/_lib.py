@@ -132,6 +132,7 @@ factor_ic              i pBppipp
 rolling_ic             i ppllpp
 factor_quantiles       i pBppipppppp
 factor_long_short      i pBppddpppppp
+factor_double_sort     i pBpppiiippppppp
 factor_coverage        i pBpp
 ic_stats               i pplp
 factor_portfolio       i pBpiippplddppp

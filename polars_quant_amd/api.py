@@ -490,6 +490,35 @@ def factor_long_short(factor, fwd_return, top_pct: float = 0.2, bottom_pct: floa
     return out
 
 
+def factor_double_sort(control, factor, fwd_return, n_control: int = 2, n_quantiles: int = 3, dependent: bool = True,
+                       labels: bool = False):
+    """D-31: per-day two-way sort of the symbols into Qa = n_control buckets of `control` times Qb = n_quantiles buckets of `factor`,
+    over the symbols where control, factor and return are all non-null and finite; dependent=True sorts the factor inside each
+    control bucket, False sorts both over the whole sample.  -> dict of device tensors: mean_return / count / turnover [Qa * Qb, T]
+    (cell a * Qb + b), spread_factor [Qa + 1, T] (top - bottom factor bucket inside control bucket a; last row: their average),
+    spread_control [Qb + 1, T] (the same along the other axis), summary [Qa * Qb + Qa + Qb + 2, 5] (the cells, then the rows of
+    spread_factor, then those of spread_control), and with labels=True labels uint8 [N, T] (a * Qb + b; LABEL_MID in a dependent
+    bucket with fewer than Qb members, LABEL_OUT outside the day's sample)"""
+    (a, f, r), b = _xsec_inputs([control, factor, fwd_return])
+    dev = f.device
+    n, T = f.shape
+    qa, qb = int(n_control), int(n_quantiles)
+    C = max(qa, 0) * max(qb, 0)
+    out = {
+        "mean_return": torch.empty((C, T), dtype=torch.float64, device=dev),
+        "count": torch.empty((C, T), dtype=torch.int32, device=dev),
+        "turnover": torch.empty((C, T), dtype=torch.float64, device=dev),
+        "spread_factor": torch.empty((max(qa, 0) + 1, T), dtype=torch.float64, device=dev),
+        "spread_control": torch.empty((max(qb, 0) + 1, T), dtype=torch.float64, device=dev),
+        "summary": torch.empty((C + max(qa, 0) + max(qb, 0) + 2, SUMMARY_COLS), dtype=torch.float64, device=dev),
+    }
+    lab = torch.empty((n, b.stride), dtype=torch.uint8, device=dev) if labels else None
+    _call("pq_factor_double_sort", dev, b, a, f, r, qa, qb, 1 if dependent else 0, lab, *out.values())
+    if lab is not None:
+        out["labels"] = lab[:, :T]
+    return out
+
+
 def factor_coverage(factor):
     """D-15: share of the symbols with a non-null finite factor value, per day -> device tensor [T]"""
     (f,), b = _xsec_inputs([factor])

@@ -1,5 +1,5 @@
 // xsec/xsec_dev.h -- helpers shared by the cross-sectional kernels: the summation block and its count (every file), the day-sort stage
-// of D-15 (sorts.hip, clean.hip: D-16, build.hip: D-20, and its LDS half also robust.hip: D-18) -- the prep transpose to day-major keys,
+// of D-15 (sorts.hip, double_sort.hip: D-31, clean.hip: D-16, build.hip: D-20, and its LDS half also robust.hip: D-18) -- the prep transpose to day-major keys,
 // the LDS bitonic sort of one day's keys and its launch shape, the row accessor and the tie-run search on a sorted row, and the host
 // interface of daysort.hip for rows too wide for LDS --, D-12's rank closed form (robust.hip) and the sequential summaries (sorts.hip,
 // xsec_ttest.h).  The OLS core of regress.hip (D-17) and orth.hip (D-19) is xsec_ols.h.

@@ -15,6 +15,8 @@ factor and the forward return of every symbol on every day.
 a fee on the traded value, as value curves with the backtest report's statistics; it takes the factor and the PRICE of every symbol.
 `combine` (decision D-30, beyond the README) is the step between the two: K tested factors into the one score that `portfolio_backtest`
 takes, by equal, trailing-IC, trailing-ICIR or max-IR weights that only use ICs already known on the day the weight is used.
+`double_sort` (decision D-31, beyond the README) is the two-way sort that follows a factor's single sort: a control (size, another
+factor) times the factor, independent or dependent, with the cells' returns and the bucket-averaged spread along each axis.
 """
 from __future__ import annotations
 
@@ -212,6 +214,25 @@ class Factor:
         """-> share of the non-null days with a positive (rank) IC (nan below 2 days)"""
         ic, _ = _api.factor_ic(factor, next_return, 1 if rank else 0)
         return float(_api.ic_stats(ic)[4])
+
+    # ---- D-31: the two-way (double) sort: does the factor survive controlling for size, or for another factor?
+    def double_sort(self, control, factor, next_return, n_control=2, n_quantiles=3, dependent=True):
+        """the symbols of each day in Qa = n_control buckets of `control` times Qb = n_quantiles buckets of `factor` (2 x 3: the
+        size / value grid); dependent=True sorts the factor inside each control bucket, False both over the whole day.
+        -> {"mean_return", "count", "turnover": [Qa, Qb, T], "spread": [Qa, T] (top - bottom factor bucket inside control bucket a),
+        "spread_avg": [T] (their average: the HML-style series), "control_spread": [Qb, T], "control_spread_avg": [T] (the same
+        along the control axis), "summary": {"cells": [Qa, Qb, 5], "spread": [Qa + 1, 5], "control_spread": [Qb + 1, 5]} (last row:
+        the average)}; every tensor is a view of the call's buffers"""
+        r = _api.factor_double_sort(control, factor, next_return, n_control, n_quantiles, dependent)
+        qa, qb = int(n_control), int(n_quantiles)
+        T = r["mean_return"].shape[1]
+        s = r["summary"]
+        return {"mean_return": r["mean_return"].view(qa, qb, T), "count": r["count"].view(qa, qb, T),
+                "turnover": r["turnover"].view(qa, qb, T),
+                "spread": r["spread_factor"][:qa], "spread_avg": r["spread_factor"][qa],
+                "control_spread": r["spread_control"][:qb], "control_spread_avg": r["spread_control"][qb],
+                "summary": {"cells": s[:qa * qb].view(qa, qb, s.shape[1]), "spread": s[qa * qb:qa * qb + qa + 1],
+                            "control_spread": s[qa * qb + qa + 1:]}}
 
     # ---- D-27: the sorts' groups as portfolios that are held between rebalance days, with weights, drift and a fee on the traded value
     def portfolio_backtest(self, factor, price, n_quantiles=5, top_pct=None, bottom_pct=None, rebalance=20, start=0, weight=None, lag=0,
