@@ -205,26 +205,39 @@ def _from_device(t: torch.Tensor, kind: int, squeeze: bool, name: str = ""):
 def _batch(t: torch.Tensor, dense: bool = False, lone_dense: bool = False) -> Batch:
     """the Batch that describes an [N, T] tensor: its own row pitch; dense: T (the tensor was made contiguous).  A single series has no
     pitch to keep: it passes its own where that is at least T, and T otherwise or with lone_dense (the library picks its 16-byte or
-    8-byte forms by this value, and each entry point keeps the one it always passed)"""
+    8-byte forms by this value, and each entry point keeps the one it always passed).
+    The one-row rule: the stride that a one-row tensor reports is only passed on where every argument of the call reports the same one --
+    _same_layout re-views the rows of a one-row call whose arguments disagree at stride T, so the Batch of any of its results (the first,
+    or the last as linear and the regressions take it) never describes a pitch that another argument was not allocated with.  An empty
+    tensor (N = 0 or T = 0) has no element to address, and its Batch is never launched on."""
     n, T = t.shape
     s = t.stride(0)
     return Batch(n, T, T if dense or (n <= 1 and (lone_dense or s < T)) else s)
 
 
 def _same_layout(ts):
+    """[N, T] tensors of one call -> the same tensors on one layout: inner stride 1 (wherever T > 1) and, for N > 1, one row pitch.
+    Arguments that agree already are returned as they are (no copy, the same objects).  N > 1, T > 0: an argument that disagrees with
+    the first one's pitch is made dense, and so are all of them unless the first one is dense already.
+    One row (N = 1) and empty tensors (N = 0 or T = 0) have no pitch to agree on -- torch ignores the stride of a size-1 dimension and
+    calls every zero-element tensor contiguous, so contiguous() would hand them back unchanged.  One-row arguments that report one
+    stride(0) and inner stride 1 pass as they are; where they disagree, every one is re-viewed at stride(0) = T without a copy (a row with
+    an inner stride other than 1 is copied), so that no batch stride taken from one argument makes a kernel address another beyond the T
+    elements of its row.  Empty arguments pass as they are for N <= 1; for N > 1 those that disagree are replaced by fresh empty [N, 0]
+    tensors of one stride."""
     n, T = ts[0].shape
-    s0 = ts[0].stride(0)
-    out = []
     for t in ts:
         if t.shape != (n, T):
             raise PqError(f"input shapes differ: {tuple(t.shape)} vs {(n, T)}")
-        if t.stride(0) != s0 or t.stride(1) != 1:
-            t = t.contiguous()
-            if s0 != T:
-                ts0 = ts[0].contiguous()
-                return _same_layout([ts0] + [x.contiguous() for x in ts[1:]])
-        out.append(t)
-    return out
+    s0 = ts[0].stride(0)
+    if n <= 1 or T == 0:
+        if n == 0 or all(t.stride(0) == s0 and (t.stride(1) == 1 or T <= 1) for t in ts):
+            return list(ts)
+        if T == 0:
+            return [t.new_empty((n, 0)) for t in ts]
+        return [t.as_strided((1, T), (T, 1)) if t.stride(1) == 1 or T == 1 else t.contiguous() for t in ts]
+    dense = s0 != T and any(t.stride(0) != s0 or t.stride(1) != 1 for t in ts)
+    return [t.contiguous() if dense or t.stride(0) != s0 or t.stride(1) != 1 else t for t in ts]
 
 
 def count_nulls(t: torch.Tensor) -> int:
@@ -644,8 +657,8 @@ def factor_clean(factor, winsorize=None, winsorize_n=None, cap=None, log_cap: bo
         z = _to_device(cap)[0]
         if z.shape != f.shape:
             raise ValueError(f"cap must have the factor's shape {tuple(f.shape)}, not {tuple(z.shape)}")
-        if log_cap:      # into a column on the factor's row pitch, so that both keep it
-            zl = torch.empty_strided(f.shape, f.stride(), dtype=torch.float64, device=f.device)
+        if log_cap:      # into a column on the factor's row pitch, so that both keep it (whole rows: a lone row owns the pitch it reports)
+            zl = torch.empty((n, max(f.stride(0), T)), dtype=torch.float64, device=f.device)[:, :T]
             torch.log(z, out=zl)
             z = zl
         ts.append(z)
