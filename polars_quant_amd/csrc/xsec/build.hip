@@ -3,7 +3,8 @@
 //
 // Columns are symbol-major [n_series][stride]; a day's cross-section is a strided column.  Every output is a full [n_series][stride] f64
 // column, NULL outside the day's sample.
-//  rank family: D-15's day-sort stage (xsec_dev.h, daysort.hip) with the key "the factor where it is non-null and finite, +0 for -0";
+//  rank family: D-15's day-sort stage (xsec_dev.h, daysort.hip) with the key "the factor where it is non-null and finite, +0 for -0" and
+//               its sort-then-look-up pair with BdRankOp:
 //               every symbol finds the tie run [a, b) of its own key (xs_tie_run) and overwrites its key by the finished value (rank,
 //               reversed rank, pct or mid-rank position), still day-major; a second tiled transpose brings the values symbol-major, so the
 //               final stores run along days, 256 contiguous bytes per half-wave.
@@ -27,9 +28,9 @@ enum BdOp { BD_RATIO = 0, BD_DIFF = 1, BD_RELDIFF = 2 };
 // the key of xs_prep_kernel: the factor where it is valid, +0 for -0
 struct BdKey {
     const double *f;
-    __device__ double operator()(int64_t o) const {
+    __device__ void operator()(int64_t o, double (&k)[1]) const {
         const double x = f[o];
-        return xs_valid(x) ? (x == 0.0 ? 0.0 : x) : xs_inf();
+        if (xs_valid(x)) k[0] = x == 0.0 ? 0.0 : x;
     }
 };
 
@@ -42,36 +43,20 @@ __device__ __forceinline__ double bd_value(int64_t m, int nv, int mode, int desc
     return r;
 }
 
-// one workgroup per day, n <= XS_LDS_MAX: sort the day's keys in LDS; every symbol replaces its key by its value (day-major, in place)
-__global__ __launch_bounds__(1024) void bd_rank_lds_kernel(double *key, const int32_t *n_valid, int64_t n, int P, int mode, int desc) {
-    extern __shared__ __align__(16) unsigned char bd_lds[];
-    double *S = (double *)bd_lds;
-    const int64_t t = blockIdx.x;
-    double *row = key + t * n;
-    const int tid = threadIdx.x, nthr = blockDim.x, nv = n_valid[t];
-    if (nv == 0) { // uniform across the workgroup
-        for (int s = tid; s < n; s += nthr) row[s] = pq_null();
-        return;
+// the operation of xsec_dev.h's sort-then-look-up pair: one sort; every symbol replaces its key by its value (day-major, in place)
+struct BdRankOp {
+    static constexpr int MAX_STEPS = 1;
+    double *key;
+    int mode, desc;
+    __host__ __device__ int steps() const { return 1; }
+    __host__ __device__ const double *row(int) const { return key; }
+    __device__ bool unsorted(int nv) const { return nv == 0; }
+    __device__ void fill(int64_t i) const { key[i] = pq_null(); }
+    template <bool PAD> __device__ void at(int, XsRow<PAD> S, int nv, int64_t i) const {
+        const double k = key[i];
+        key[i] = k == xs_inf() ? pq_null() : bd_value(xs_tie_run(S, nv, k), nv, mode, desc);
     }
-    xs_load_sort_row(S, row, n, P, tid, nthr);
-    for (int s = tid; s < n; s += nthr) {
-        const double k = row[s];
-        row[s] = k == xs_inf() ? pq_null() : bd_value(xs_tie_run(XsRow<true>{S}, nv, k), nv, mode, desc);
-    }
-}
-
-// n > XS_LDS_MAX: the day's row was sorted by rocPRIM (sorted); values from the original row, in place
-__global__ __launch_bounds__(256) void bd_rank_sorted_kernel(double *key, const double *sorted, const int32_t *n_valid, int64_t n, int mode,
-                                                             int desc) {
-    const int64_t t = blockIdx.x;
-    double *row = key + t * n;
-    const double *S = sorted + t * n;
-    const int nv = n_valid[t];
-    for (int64_t s = threadIdx.x; s < n; s += 256) {
-        const double k = row[s];
-        row[s] = k == xs_inf() ? pq_null() : bd_value(xs_tie_run(XsRow<false>{S}, nv, k), nv, mode, desc);
-    }
-}
+};
 
 // day-major [len][n] values -> symbol-major [n][stride]: 32 x 32 tiles, reads along symbols, stores along days
 __global__ __launch_bounds__(256) void bd_transpose_kernel(const double *dm, int64_t n, int64_t len, double *out, int64_t stride) {
@@ -253,17 +238,8 @@ pq_status pq_factor_rank(pq_ctx *ctx, const pq_batch *b, const double *factor, i
     hipStream_t st = ctx->stream;
     const dim3 gt((unsigned)((d.len + 31) / 32), (unsigned)((d.n + 31) / 32));
     PQ_HIP_TRY(hipMemsetAsync(nv, 0, len * 4, st));
-    hipLaunchKernelGGL(xs_prep_kernel<BdKey>, gt, dim3(256), 0, st, BdKey{factor}, d, key, nv);
-    if (!plan.wide) {
-        const XsLds L = xs_lds_shape(d.n);
-        PQ_HIP_TRY(hipFuncSetAttribute((const void *)bd_rank_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.bytes));
-        hipLaunchKernelGGL(bd_rank_lds_kernel, dim3((unsigned)d.len), dim3(L.nthr), L.bytes, st, key, (const int32_t *)nv, d.n, L.P, mode,
-                           descending);
-    } else {
-        const double *srt;
-        PQ_TRY(xs_day_sort_wide(ctx, d, plan, ws + o_srt, key, &srt));
-        hipLaunchKernelGGL(bd_rank_sorted_kernel, dim3((unsigned)d.len), dim3(256), 0, st, key, srt, (const int32_t *)nv, d.n, mode, descending);
-    }
+    hipLaunchKernelGGL((xs_prep_kernel<1, BdKey>), gt, dim3(256), 0, st, BdKey{factor}, d, key, (int64_t)0, nv);
+    PQ_TRY(xs_sort_lookup(ctx, d, plan, ws + o_srt, BdRankOp{key, mode, descending}, nv));
     hipLaunchKernelGGL(bd_transpose_kernel, gt, dim3(256), 0, st, (const double *)key, d.n, d.len, out, d.stride);
     PQ_HIP_TRY(hipGetLastError());
     return PQ_OK;

@@ -65,9 +65,9 @@ __device__ __forceinline__ double cl_clip(double x, double lo, double hi) {
 // the key of xs_prep_kernel: the factor where the symbol is in the cross-section, +0 for -0
 struct ClKey {
     ClIn in;
-    __device__ double operator()(int64_t o) const {
+    __device__ void operator()(int64_t o, double (&k)[1]) const {
         const double x = in.f[o];
-        return cl_member(in, x, in.z ? in.z[o] : 0.0, in.ind ? in.ind[o] : 0) ? (x == 0.0 ? 0.0 : x) : xs_inf();
+        if (cl_member(in, x, in.z ? in.z[o] : 0.0, in.ind ? in.ind[o] : 0)) k[0] = x == 0.0 ? 0.0 : x;
     }
 };
 
@@ -344,8 +344,8 @@ pq_status pq_factor_clean(pq_ctx *ctx, const pq_batch *b, const double *factor, 
     } else if (sorted) {
         double *key = (double *)(ws + o_key);
         PQ_HIP_TRY(hipMemsetAsync(day.n, 0, len * 4, st));
-        hipLaunchKernelGGL(xs_prep_kernel<ClKey>, dim3((unsigned)((d.len + 31) / 32), (unsigned)((d.n + 31) / 32)), dim3(256), 0, st,
-                           ClKey{in}, d, key, day.n);
+        hipLaunchKernelGGL((xs_prep_kernel<1, ClKey>), dim3((unsigned)((d.len + 31) / 32), (unsigned)((d.n + 31) / 32)), dim3(256), 0, st,
+                           ClKey{in}, d, key, (int64_t)0, day.n);
         if (!plan.wide) {
             const XsLds L = xs_lds_shape(d.n);
             PQ_HIP_TRY(hipFuncSetAttribute((const void *)cl_bounds_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.bytes));

@@ -1,7 +1,8 @@
 // xsec/daysort.hip -- the wide half of the day-sort stage (D-15): cross-sections above XS_LDS_MAX symbols are sorted by rocPRIM's segmented
 // radix sort (keys only) in global memory, one segment per day.  The only xsec file that includes rocPRIM; sorts.hip, double_sort.hip,
-// clean.hip and build.hip plan the sort, lay the tail out at the end of their own workspace and launch their own consumer on the sorted rows.  The LDS
-// half of the stage is in xsec_dev.h; robust.hip uses that half alone and has no wide sort (above XS_LDS_MAX it calls pq_factor_ic).
+// clean.hip and build.hip plan the sort and lay the tail out at the end of their own workspace; the consumer on the sorted rows is
+// xs_sort_wide_kernel<Op> (xsec_dev.h: sorts.hip, double_sort.hip, build.hip) or the caller's own (clean.hip).  The LDS half of the
+// stage is in xsec_dev.h; robust.hip uses that half alone and has no wide sort (above XS_LDS_MAX it calls pq_factor_ic).
 #include "xsec_dev.h"
 #include <rocprim/rocprim.hpp>
 

@@ -3,19 +3,23 @@
 // README.md:1479-1487, :1535-1545, :1589-1599; README-only => decision D-15).
 //
 // Columns are symbol-major [n_series][stride]; a day's cross-section is a strided column.
-//  1. prep:      the day-sort stage of xsec_dev.h (also clean.hip's and build.hip's): xs_prep_kernel, a tiled transpose, turns the
-//                factor column into day-major key rows (+inf where the (factor, return) pair is not in the cross-section) and counts
-//                each day's cross-section n.
-//  2. label:     up to XS_LDS_MAX symbols one workgroup per day sorts its key row in LDS (xs_load_sort_row: bitonic, keys only); wider
-//                cross-sections go through daysort.hip (rocPRIM's segmented radix sort, keys only, in global memory).  Each symbol then
-//                finds its tie run [a, b) by binary searches of its own key in the sorted row (xs_tie_run) -- m = a + b, so ties share
-//                a label and nothing depends on sort stability -- and writes one uint8 label per cell, day-major.
+//  1. prep:      the day-sort stage of xsec_dev.h (also double_sort.hip's, clean.hip's and build.hip's): xs_prep_kernel, a tiled
+//                transpose, turns the factor column into day-major key rows (+inf where the (factor, return) pair is not in the
+//                cross-section) and counts each day's cross-section n.
+//  2. label:     xsec_dev.h's sort-then-look-up pair with XsLabelOp.  Up to XS_LDS_MAX symbols one workgroup per day sorts its key row
+//                in LDS (xs_load_sort_row: bitonic, keys only); wider cross-sections go through daysort.hip (rocPRIM's segmented radix
+//                sort, keys only, in global memory).  Each symbol then finds its tie run [a, b) by binary searches of its own key in the
+//                sorted row (xs_tie_run) -- m = a + b, so ties share a label and nothing depends on sort stability -- and writes one
+//                uint8 label per cell, day-major.
+// The cells stage, from day-major labels on, is defined here once for this file and double_sort.hip (D-31; interface in xsec_dev.h):
 //  3. transpose: labels day-major -> symbol-major, 64 x 64 byte tiles.
-//  4. aggregate: one thread per (day, block of 256 symbols), consecutive threads on consecutive days (coalesced); the per-group sums
-//                are D-12's order (ascending symbols inside a block, from 0.0), counts and "new member" counts are integers.  A per-day
-//                combine adds the block sums in ascending block order and writes mean / count / turnover / spread.
-//  5. summary:   one 64-lane workgroup per output row; chunks of the series are staged in LDS and summed by one lane in ascending day
-//                order (the stated sequential order), two-pass sample std.
+//  4. aggregate: one thread per (day, block of 256 symbols), consecutive threads on consecutive days (coalesced); the per-cell sums
+//                are D-12's order (ascending symbols inside a block, from 0.0), counts and "new member" counts are integers.  Up to 20
+//                cells the accumulators are registers (<2 | 5 | 10 | 20>), above that LDS tiles of XS_CT cells, one column per lane
+//                (robust.hip's group tiles), with blockIdx.z walking the tiles.  One thread per (day, cell) then adds the block sums in
+//                ascending block order and writes mean / count / turnover; the single sorts' spread is one more row from the means.
+//  5. summary:   one 64-lane workgroup per output row (the cells with their turnover, then the caller's spread rows); chunks of the
+//                series are staged in LDS and summed by one lane in ascending day order (the stated sequential order), two-pass sample std.
 #include "xsec_dev.h"
 
 namespace {
@@ -30,9 +34,9 @@ struct XsRule {
 // the key of xs_prep_kernel: the factor, as it is, where the (factor, return) pair is valid
 struct XsKey {
     const double *f, *r;
-    __device__ double operator()(int64_t o) const {
+    __device__ void operator()(int64_t o, double (&k)[1]) const {
         const double a = f[o], b = r[o];
-        return (xs_valid(a) & xs_valid(b)) ? a : xs_inf(); // &, not &&: both loads are issued before either test
+        if (xs_valid(a) & xs_valid(b)) k[0] = a; // &, not &&: both loads are issued before either test
     }
 };
 
@@ -44,38 +48,24 @@ __device__ __forceinline__ uint8_t xs_label(int64_t m, int64_t nv, const XsRule 
     return PQ_LABEL_MID;
 }
 
-// one workgroup per day, n <= XS_LDS_MAX: sort the day's keys in LDS, label every symbol (day-major)
-__global__ __launch_bounds__(1024) void xs_label_lds_kernel(const double *key, const int32_t *n_valid, int64_t n, int P, XsRule rule,
-                                                            uint8_t *lab) {
-    extern __shared__ __align__(16) unsigned char xs_lds[];
-    double *S = (double *)xs_lds;
-    const int64_t t = blockIdx.x;
-    const double *row = key + t * n;
-    uint8_t *out = lab + t * n;
-    const int tid = threadIdx.x, nthr = blockDim.x, nv = n_valid[t];
-    if (nv < rule.min_n) { // uniform across the workgroup
-        for (int s = tid; s < n; s += nthr) out[s] = PQ_LABEL_OUT;
-        return;
+// the operation of xsec_dev.h's sort-then-look-up pair: one sort, the symbol's label from its tie run (day-major)
+struct XsLabelOp {
+    static constexpr int MAX_STEPS = 1;
+    const double *key;
+    XsRule rule;
+    uint8_t *lab;
+    __host__ __device__ int steps() const { return 1; }
+    __host__ __device__ const double *row(int) const { return key; }
+    __device__ bool unsorted(int nv) const { return nv < rule.min_n; }
+    __device__ void fill(int64_t i) const { lab[i] = PQ_LABEL_OUT; }
+    template <bool PAD> __device__ void at(int, XsRow<PAD> S, int nv, int64_t i) const {
+        const double k = key[i];
+        lab[i] = k == xs_inf() ? (uint8_t)PQ_LABEL_OUT : xs_label(xs_tie_run(S, nv, k), nv, rule);
     }
-    xs_load_sort_row(S, row, n, P, tid, nthr);
-    for (int s = tid; s < n; s += nthr) {
-        const double k = row[s];
-        out[s] = k == xs_inf() ? (uint8_t)PQ_LABEL_OUT : xs_label(xs_tie_run(XsRow<true>{S}, nv, k), nv, rule);
-    }
-}
+};
 
-// n > XS_LDS_MAX: the day's row was sorted by rocPRIM (sorted); label from the original row
-__global__ __launch_bounds__(256) void xs_label_sorted_kernel(const double *key, const double *sorted, const int32_t *n_valid, int64_t n,
-                                                              XsRule rule, uint8_t *lab) {
-    const int64_t t = blockIdx.x;
-    const double *row = key + t * n, *S = sorted + t * n;
-    uint8_t *out = lab + t * n;
-    const int nv = n_valid[t];
-    for (int64_t s = threadIdx.x; s < n; s += 256) {
-        const double k = row[s];
-        out[s] = (nv < rule.min_n || k == xs_inf()) ? (uint8_t)PQ_LABEL_OUT : xs_label(xs_tie_run(XsRow<false>{S}, nv, k), nv, rule);
-    }
-}
+// ---------------------------------------------------------------- the cells stage
+constexpr int XS_CT = 32; // cells per LDS tile of the partial sums: 32 x 64 lanes x (8 + 4 + 4) bytes = 32 KiB of LDS
 
 // day-major [len][n] labels -> symbol-major [n][ostride]
 __global__ __launch_bounds__(256) void xs_label_transpose_kernel(const uint8_t *dm, int64_t n, int64_t len, uint8_t *sm, int64_t ostride) {
@@ -93,11 +83,24 @@ __global__ __launch_bounds__(256) void xs_label_transpose_kernel(const uint8_t *
     }
 }
 
-// one thread per (day, block of 256 symbols): per group the sum of the members' returns (ascending symbols, from 0.0), the member count
-// and the count of members that were not in the group the day before.  G >= ng groups live in registers (static indices).
+// The partial sums, one thread per (day, block of 256 symbols): per cell the sum of the members' returns (ascending symbols, from 0.0),
+// the member count and the count of new members.  Both kernels walk the block eight symbols s0 .. s0 + 7 (clamped to s_hi - 1) at a
+// time, all loads issued before the first add, and apply one rule, whose loads are xs_cell_load: on day t symbol s is a member of cell
+// l, and a new one when lp, its label the day before (PQ_LABEL_OUT before day 0), is another.  The comparison stays at the
+// accumulation: made at the load it waits for every label before the first add (the <10> kernel took 0.173 ms against 0.154 at
+// 10 000 x 5 040), and the eight loads stay a loop of the kernel (as a helper of their own they cost the register kernels 1 - 4 VGPRs).
+constexpr int XS_B = 8;
+__device__ __forceinline__ void xs_cell_load(const uint8_t *lab, int64_t lstride, const double *ret, int64_t rstride, int64_t t, int64_t s,
+                                             int &l, int &lp, double &v) {
+    l = lab[s * lstride + t];
+    lp = t > 0 ? lab[s * lstride + t - 1] : PQ_LABEL_OUT;
+    v = ret[s * rstride + t];
+}
+
+// C <= G cells in registers (static indices)
 template <int G>
-__global__ __launch_bounds__(64) void xs_group_partial_kernel(const uint8_t *lab, int64_t lstride, const double *ret, Dims d, int ng,
-                                                              double *psum, int32_t *pcnt, int32_t *pnew) {
+__global__ __launch_bounds__(64) void xs_cell_partial_reg_kernel(const uint8_t *lab, int64_t lstride, const double *ret, Dims d, int C,
+                                                                 double *psum, int32_t *pcnt, int32_t *pnew) {
     const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (t >= d.len) return;
     const int64_t s_lo = (int64_t)blockIdx.y * XS_BLOCK, s_hi = s_lo + XS_BLOCK < d.n ? s_lo + XS_BLOCK : d.n;
@@ -105,19 +108,13 @@ __global__ __launch_bounds__(64) void xs_group_partial_kernel(const uint8_t *lab
     int cnt[G], nw[G];
 #pragma unroll
     for (int g = 0; g < G; g++) { sum[g] = 0.0; cnt[g] = 0; nw[g] = 0; }
-    constexpr int B = 8;
-    for (int64_t s0 = s_lo; s0 < s_hi; s0 += B) {
-        int l[B], lp[B];
-        double v[B];
+    for (int64_t s0 = s_lo; s0 < s_hi; s0 += XS_B) {
+        int l[XS_B], lp[XS_B];
+        double v[XS_B];
 #pragma unroll
-        for (int k = 0; k < B; k++) {
-            const int64_t s = s0 + k < s_hi ? s0 + k : s_hi - 1;
-            l[k] = lab[s * lstride + t];
-            lp[k] = t > 0 ? lab[s * lstride + t - 1] : PQ_LABEL_OUT;
-            v[k] = ret[s * d.stride + t];
-        }
+        for (int k = 0; k < XS_B; k++) xs_cell_load(lab, lstride, ret, d.stride, t, s0 + k < s_hi ? s0 + k : s_hi - 1, l[k], lp[k], v[k]);
 #pragma unroll
-        for (int k = 0; k < B; k++) {
+        for (int k = 0; k < XS_B; k++) {
             if (s0 + k >= s_hi) break;
 #pragma unroll
             for (int g = 0; g < G; g++)
@@ -126,49 +123,72 @@ __global__ __launch_bounds__(64) void xs_group_partial_kernel(const uint8_t *lab
     }
 #pragma unroll
     for (int g = 0; g < G; g++)
-        if (g < ng) {
-            const int64_t o = ((int64_t)blockIdx.y * ng + g) * d.len + t;
+        if (g < C) {
+            const int64_t o = ((int64_t)blockIdx.y * C + g) * d.len + t;
             psum[o] = sum[g]; pcnt[o] = cnt[g]; pnew[o] = nw[g];
         }
 }
 
-// one thread per day: block sums in ascending block order (from 0.0); mean, count, turnover per group; top - bottom spread
-__global__ __launch_bounds__(64) void xs_group_combine_kernel(const double *psum, const int32_t *pcnt, const int32_t *pnew, int64_t nblk,
-                                                              int64_t len, int ng, double *mean, int32_t *count, double *tov,
-                                                              double *spread) {
-    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
-    if (t >= len) return;
-    double lo = pq_null(), hi = pq_null();
-    for (int g = 0; g < ng; g++) {
-        double s = 0.0;
-        int64_t c = 0, nw = 0, cp = 0;
-        for (int64_t k = 0; k < nblk; k++) {
-            const int64_t o = (k * ng + g) * len + t;
-            s += psum[o]; c += pcnt[o]; nw += pnew[o];
-            if (t > 0) cp += pcnt[o - 1];
+// more cells than fit registers: blockIdx.z = the tile of XS_CT cells, whose sums and counts live in LDS, one column per lane
+__global__ __launch_bounds__(64) void xs_cell_partial_lds_kernel(const uint8_t *lab, int64_t lstride, const double *ret, Dims d, int C,
+                                                                 double *psum, int32_t *pcnt, int32_t *pnew) {
+    __shared__ double sum[XS_CT][64];
+    __shared__ int cnt[XS_CT][64], nw[XS_CT][64];
+    const int lane = threadIdx.x;
+    const int64_t t = (int64_t)blockIdx.x * 64 + lane;
+    if (t >= d.len) return; // no workgroup barrier below: every lane only touches its own column
+    const int c0 = (int)blockIdx.z * XS_CT, nc = C - c0 < XS_CT ? C - c0 : XS_CT;
+    const int64_t s_lo = (int64_t)blockIdx.y * XS_BLOCK, s_hi = s_lo + XS_BLOCK < d.n ? s_lo + XS_BLOCK : d.n;
+    for (int j = 0; j < XS_CT; j++) { sum[j][lane] = 0.0; cnt[j][lane] = 0; nw[j][lane] = 0; }
+    for (int64_t s0 = s_lo; s0 < s_hi; s0 += XS_B) {
+        int l[XS_B], lp[XS_B];
+        double v[XS_B];
+#pragma unroll
+        for (int k = 0; k < XS_B; k++) xs_cell_load(lab, lstride, ret, d.stride, t, s0 + k < s_hi ? s0 + k : s_hi - 1, l[k], lp[k], v[k]);
+#pragma unroll
+        for (int k = 0; k < XS_B; k++) {
+            if (s0 + k >= s_hi) break;
+            const int j = l[k] - c0;
+            if (j < 0 || j >= nc) continue; // another tile's cell, PQ_LABEL_MID or PQ_LABEL_OUT
+            sum[j][lane] += v[k]; cnt[j][lane] += 1; nw[j][lane] += lp[k] != l[k];
         }
-        const double m = c > 0 ? s / (double)c : pq_null();
-        mean[g * len + t] = m;
-        count[g * len + t] = (int32_t)c;
-        tov[g * len + t] = (t > 0 && c > 0 && cp > 0) ? (double)nw / (double)c : pq_null();
-        if (g == 0) lo = m;
-        if (g == ng - 1) hi = m;
     }
-    spread[t] = (pq_isnull(lo) || pq_isnull(hi)) ? pq_null() : hi - lo;
+    for (int j = 0; j < nc; j++) {
+        const int64_t o = ((int64_t)blockIdx.y * C + c0 + j) * d.len + t;
+        psum[o] = sum[j][lane]; pcnt[o] = cnt[j][lane]; pnew[o] = nw[j][lane];
+    }
 }
 
-// one 64-lane workgroup per row: rows 0 .. ng-1 = the groups (mean_return[g], turnover[g]), row ng = the spread / long-short series
-__global__ __launch_bounds__(64) void xs_summary_kernel(const double *mean, const double *tov, const double *spread, int64_t len, int ng,
+// one thread per (day, cell): block sums in ascending block order (from 0.0); mean, count, turnover
+__global__ __launch_bounds__(64) void xs_cell_combine_kernel(const double *psum, const int32_t *pcnt, const int32_t *pnew, int64_t nblk,
+                                                             int64_t len, int C, double *mean, int32_t *count, double *tov) {
+    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x, g = blockIdx.y;
+    if (t >= len) return;
+    double s = 0.0;
+    int64_t c = 0, nw = 0, cp = 0;
+    for (int64_t k = 0; k < nblk; k++) {
+        const int64_t o = (k * C + g) * len + t;
+        s += psum[o]; c += pcnt[o]; nw += pnew[o];
+        if (t > 0) cp += pcnt[o - 1];
+    }
+    mean[g * len + t] = c > 0 ? s / (double)c : pq_null();
+    count[g * len + t] = (int32_t)c;
+    tov[g * len + t] = (t > 0 && c > 0 && cp > 0) ? (double)nw / (double)c : pq_null();
+}
+
+// one 64-lane workgroup per row: rows 0 .. C-1 = the cells (mean_return, turnover), then the e0.n and the e1.n extra rows
+__global__ __launch_bounds__(64) void xs_summary_kernel(const double *mean, const double *tov, XsRows e0, XsRows e1, int64_t len, int C,
                                                         double *summary) {
     __shared__ double buf[XS_CHUNK];
     const int g = blockIdx.x;
-    const double *x = g < ng ? mean + g * len : spread;
-    double s, ss, ts;
-    int64_t n, nt, pos;
+    const bool cell = g < C;
+    const double *x = cell ? mean + g * len : (g < C + e0.n ? e0.x + (int64_t)(g - C) * len : e1.x + (int64_t)(g - C - e0.n) * len);
+    double s, ss, ts = 0.0;
+    int64_t n, nt = 0, pos;
     xs_seq<false>(x, len, 0.0, buf, s, n, pos);
     const double m = n > 0 ? s / (double)n : pq_null();
     xs_seq<true>(x, len, n > 0 ? m : 0.0, buf, ss, n, pos);
-    if (g < ng) xs_seq<false>(tov + g * len, len, 0.0, buf, ts, nt, pos);
+    if (cell) xs_seq<false>(tov + g * len, len, 0.0, buf, ts, nt, pos); // uniform across the workgroup
     if (threadIdx.x == 0) {
         const double sd = n >= 2 ? sqrt(ss / (double)(n - 1)) : pq_null();
         double *o = summary + (int64_t)g * PQ_GROUP_SUMMARY_COLS;
@@ -176,8 +196,16 @@ __global__ __launch_bounds__(64) void xs_summary_kernel(const double *mean, cons
         o[1] = m;
         o[2] = sd;
         o[3] = (n >= 2 && sd > 0.0) ? m / sd * sqrt(252.0) : pq_null();
-        o[4] = (g < ng && nt > 0) ? ts / (double)nt : pq_null();
+        o[4] = (cell && nt > 0) ? ts / (double)nt : pq_null();
     }
+}
+
+// the single sorts' spread: mean[ng - 1] - mean[0], NULL where either is
+__global__ __launch_bounds__(64) void xs_spread_kernel(const double *mean, int64_t len, int ng, double *spread) {
+    const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (t >= len) return;
+    const double lo = mean[t], hi = mean[(int64_t)(ng - 1) * len + t];
+    spread[t] = (pq_isnull(lo) || pq_isnull(hi)) ? pq_null() : hi - lo;
 }
 
 // n_days, mean, std, ir = mean / std (not annualised), win_rate = #(ic > 0) / n_days
@@ -223,70 +251,77 @@ __global__ __launch_bounds__(256) void xs_coverage_final_kernel(const int32_t *c
     if (t < len) coverage[t] = n > 0 ? (double)cnt[t] / (double)n : pq_null();
 }
 
-// labels -> group statistics -> summary: the body shared by pq_factor_quantiles (ng = Q) and pq_factor_long_short (ng = 2)
-pq_status xs_groups(pq_ctx *ctx, const pq_batch *b, const double *factor, const double *fwd_return, const XsRule &rule, int ng,
-                    uint8_t *labels, double *mean, int32_t *count, double *tov, double *spread, double *summary) {
-    if (b->len == 0) return PQ_OK;
-    const Dims d = dims_of(b);
-    const size_t cells = (size_t)d.len * (size_t)d.n, len = (size_t)d.len;
-    const int64_t nblk = xs_nblk(d.n);
-    XsDaySort plan;
-    PQ_TRY(xs_day_sort_plan(ctx, d, "factor sorts", &plan));
-    // workspace: keys (f64, day-major) | n per day (i32) | labels day-major (u8) | labels symbol-major (u8, when the caller passes
-    // none) | block partials: sums (f64), counts, new members (i32) | wide: sorted keys (f64), offsets (u32), rocPRIM temp
-    const size_t part = (size_t)nblk * (size_t)ng * len;
-    const size_t o_cnt = xs_al(cells * 8), o_ldm = o_cnt + xs_al(len * 4), o_lsm = o_ldm + xs_al(cells),
-                 o_ps = o_lsm + (labels ? 0 : xs_al(cells)), o_pc = o_ps + xs_al(part * 8), o_pn = o_pc + xs_al(part * 4),
-                 o_srt = o_pn + xs_al(part * 4);
-    PQ_TRY(pq_ws_reserve(ctx, o_srt + plan.bytes));
+} // namespace
+
+// ---------------------------------------------------------------- host side of the cells stage (declared in xsec_dev.h)
+XsCellsWs xs_cells_layout(const Dims &d, int nkey, int ncell, bool caller_labels, const XsDaySort &plan) {
+    const size_t cells = (size_t)d.len * (size_t)d.n, len = (size_t)d.len, part = (size_t)xs_nblk(d.n) * (size_t)ncell * len;
+    XsCellsWs ws;
+    ws.key_pitch = xs_al(cells * 8) / 8;
+    ws.o_nv = (size_t)nkey * ws.key_pitch * 8;
+    ws.o_ldm = ws.o_nv + xs_al(len * 4);
+    ws.o_lsm = ws.o_ldm + xs_al(cells);
+    ws.o_ps = ws.o_lsm + (caller_labels ? 0 : xs_al(cells));
+    ws.o_pc = ws.o_ps + xs_al(part * 8);
+    ws.o_pn = ws.o_pc + xs_al(part * 4);
+    ws.o_tail = ws.o_pn + xs_al(part * 4);
+    ws.bytes = ws.o_tail + plan.bytes;
+    return ws;
+}
+
+pq_status xs_cells_stats(pq_ctx *ctx, const Dims &d, const XsCellsWs &ws, int ncell, uint8_t *labels, const double *ret, double *mean,
+                         int32_t *count, double *tov) {
     unsigned char *w = (unsigned char *)ctx->ws;
-    double *key = (double *)w;
-    int32_t *nv = (int32_t *)(w + o_cnt);
-    uint8_t *ldm = w + o_ldm;
-    uint8_t *lsm = labels ? labels : w + o_lsm;
-    const int64_t lstride = labels ? d.stride : d.len;
-    double *psum = (double *)(w + o_ps);
-    int32_t *pcnt = (int32_t *)(w + o_pc), *pnew = (int32_t *)(w + o_pn);
-    if (d.n > 0) {
-        PQ_HIP_TRY(hipMemsetAsync(nv, 0, len * 4, ctx->stream));
-        hipLaunchKernelGGL(xs_prep_kernel<XsKey>, dim3((unsigned)((d.len + 31) / 32), (unsigned)((d.n + 31) / 32)), dim3(256), 0,
-                           ctx->stream, XsKey{factor, fwd_return}, d, key, nv);
-        if (!plan.wide) {
-            const XsLds L = xs_lds_shape(d.n);
-            PQ_HIP_TRY(hipFuncSetAttribute((const void *)xs_label_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.bytes));
-            hipLaunchKernelGGL(xs_label_lds_kernel, dim3((unsigned)d.len), dim3(L.nthr), L.bytes, ctx->stream, (const double *)key,
-                               (const int32_t *)nv, d.n, L.P, rule, ldm);
-        } else {
-            const double *srt;
-            PQ_TRY(xs_day_sort_wide(ctx, d, plan, w + o_srt, key, &srt));
-            hipLaunchKernelGGL(xs_label_sorted_kernel, dim3((unsigned)d.len), dim3(256), 0, ctx->stream, (const double *)key, srt,
-                               (const int32_t *)nv, d.n, rule, ldm);
-        }
-        hipLaunchKernelGGL(xs_label_transpose_kernel, dim3((unsigned)((d.len + 63) / 64), (unsigned)((d.n + 63) / 64)), dim3(256), 0,
-                           ctx->stream, (const uint8_t *)ldm, d.n, d.len, lsm, lstride);
-    }
-    const dim3 gp((unsigned)((d.len + 63) / 64), (unsigned)nblk), gc((unsigned)((d.len + 63) / 64));
-    if (ng <= 2)
-        hipLaunchKernelGGL(xs_group_partial_kernel<2>, gp, dim3(64), 0, ctx->stream, (const uint8_t *)lsm, lstride, fwd_return, d, ng, psum,
-                           pcnt, pnew);
-    else if (ng <= 5)
-        hipLaunchKernelGGL(xs_group_partial_kernel<5>, gp, dim3(64), 0, ctx->stream, (const uint8_t *)lsm, lstride, fwd_return, d, ng, psum,
-                           pcnt, pnew);
-    else if (ng <= 10)
-        hipLaunchKernelGGL(xs_group_partial_kernel<10>, gp, dim3(64), 0, ctx->stream, (const uint8_t *)lsm, lstride, fwd_return, d, ng,
-                           psum, pcnt, pnew);
-    else
-        hipLaunchKernelGGL(xs_group_partial_kernel<20>, gp, dim3(64), 0, ctx->stream, (const uint8_t *)lsm, lstride, fwd_return, d, ng,
-                           psum, pcnt, pnew);
-    hipLaunchKernelGGL(xs_group_combine_kernel, gc, dim3(64), 0, ctx->stream, (const double *)psum, (const int32_t *)pcnt,
-                       (const int32_t *)pnew, nblk, d.len, ng, mean, count, tov, spread);
-    hipLaunchKernelGGL(xs_summary_kernel, dim3((unsigned)(ng + 1)), dim3(64), 0, ctx->stream, (const double *)mean, (const double *)tov,
-                       (const double *)spread, d.len, ng, summary);
+    const uint8_t *lsm = labels ? labels : w + ws.o_lsm;
+    const int64_t lstride = labels ? d.stride : d.len, nblk = xs_nblk(d.n);
+    double *psum = (double *)(w + ws.o_ps);
+    int32_t *pcnt = (int32_t *)(w + ws.o_pc), *pnew = (int32_t *)(w + ws.o_pn);
+    const unsigned gx = (unsigned)((d.len + 63) / 64);
+    if (d.n > 0)
+        hipLaunchKernelGGL(xs_label_transpose_kernel, dim3(gx, (unsigned)((d.n + 63) / 64)), dim3(256), 0, ctx->stream,
+                           (const uint8_t *)(w + ws.o_ldm), d.n, d.len, (uint8_t *)lsm, lstride);
+    // the accumulator form belongs to the cell count: registers while the cells fit them, LDS tiles above
+    const auto partial = ncell <= 2 ? xs_cell_partial_reg_kernel<2> : ncell <= 5 ? xs_cell_partial_reg_kernel<5>
+                       : ncell <= 10 ? xs_cell_partial_reg_kernel<10> : ncell <= 20 ? xs_cell_partial_reg_kernel<20>
+                       : xs_cell_partial_lds_kernel;
+    hipLaunchKernelGGL(partial, dim3(gx, (unsigned)nblk, ncell <= 20 ? 1u : (unsigned)((ncell + XS_CT - 1) / XS_CT)), dim3(64), 0,
+                       ctx->stream, lsm, lstride, ret, d, ncell, psum, pcnt, pnew);
+    hipLaunchKernelGGL(xs_cell_combine_kernel, dim3(gx, (unsigned)ncell), dim3(64), 0, ctx->stream, (const double *)psum,
+                       (const int32_t *)pcnt, (const int32_t *)pnew, nblk, d.len, ncell, mean, count, tov);
     PQ_HIP_TRY(hipGetLastError());
     return PQ_OK;
 }
 
-} // namespace
+pq_status xs_cells_summary(pq_ctx *ctx, int64_t len, int ncell, const double *mean, const double *tov, XsRows e0, XsRows e1, double *summary) {
+    hipLaunchKernelGGL(xs_summary_kernel, dim3((unsigned)(ncell + e0.n + e1.n)), dim3(64), 0, ctx->stream, mean, tov, e0, e1, len, ncell,
+                       summary);
+    PQ_HIP_TRY(hipGetLastError());
+    return PQ_OK;
+}
+
+// labels -> group statistics -> summary: the body shared by pq_factor_quantiles (ng = Q) and pq_factor_long_short (ng = 2)
+static pq_status xs_groups(pq_ctx *ctx, const pq_batch *b, const double *factor, const double *fwd_return, const XsRule &rule, int ng,
+                           uint8_t *labels, double *mean, int32_t *count, double *tov, double *spread, double *summary) {
+    if (b->len == 0) return PQ_OK;
+    const Dims d = dims_of(b);
+    XsDaySort plan;
+    PQ_TRY(xs_day_sort_plan(ctx, d, "factor sorts", &plan));
+    const XsCellsWs ws = xs_cells_layout(d, 1, ng, labels != nullptr, plan);
+    PQ_TRY(pq_ws_reserve(ctx, ws.bytes));
+    unsigned char *w = (unsigned char *)ctx->ws;
+    double *key = (double *)w;
+    int32_t *nv = (int32_t *)(w + ws.o_nv);
+    if (d.n > 0) {
+        PQ_HIP_TRY(hipMemsetAsync(nv, 0, (size_t)d.len * 4, ctx->stream));
+        hipLaunchKernelGGL((xs_prep_kernel<1, XsKey>), dim3((unsigned)((d.len + 31) / 32), (unsigned)((d.n + 31) / 32)), dim3(256), 0,
+                           ctx->stream, XsKey{factor, fwd_return}, d, key, (int64_t)ws.key_pitch, nv);
+        PQ_TRY(xs_sort_lookup(ctx, d, plan, w + ws.o_tail, XsLabelOp{key, rule, w + ws.o_ldm}, nv));
+    }
+    PQ_TRY(xs_cells_stats(ctx, d, ws, ng, labels, fwd_return, mean, count, tov));
+    hipLaunchKernelGGL(xs_spread_kernel, dim3((unsigned)((d.len + 63) / 64)), dim3(64), 0, ctx->stream, (const double *)mean, d.len, ng,
+                       spread);
+    return xs_cells_summary(ctx, d.len, ng, mean, tov, XsRows{spread, 1}, XsRows{nullptr, 0}, summary);
+}
 
 extern "C" {
 

@@ -1,8 +1,10 @@
 // xsec/xsec_dev.h -- helpers shared by the cross-sectional kernels: the summation block and its count (every file), the day-sort stage
 // of D-15 (sorts.hip, double_sort.hip: D-31, clean.hip: D-16, build.hip: D-20, and its LDS half also robust.hip: D-18) -- the prep transpose to day-major keys,
-// the LDS bitonic sort of one day's keys and its launch shape, the row accessor and the tie-run search on a sorted row, and the host
-// interface of daysort.hip for rows too wide for LDS --, D-12's rank closed form (robust.hip) and the sequential summaries (sorts.hip,
-// xsec_ttest.h).  The OLS core of regress.hip (D-17) and orth.hip (D-19) is xsec_ols.h.
+// the LDS bitonic sort of one day's keys and its launch shape, the row accessor and the tie-run search on a sorted row, the
+// sort-then-look-up kernel pair with its host dispatch (sorts.hip, double_sort.hip, build.hip), and the host interface of daysort.hip for
+// rows too wide for LDS --, the host interface of the cells stage of sorts.hip (labels -> per-cell statistics -> summary; also
+// double_sort.hip), D-12's rank closed form (robust.hip) and the sequential summaries (sorts.hip, xsec_ttest.h).  The OLS core of
+// regress.hip (D-17) and orth.hip (D-19) is xsec_ols.h.
 #pragma once
 #include "../pq_dev.h"
 
@@ -86,25 +88,32 @@ __device__ __forceinline__ void xs_load_sort_row(double *S, const double *row, i
     xs_sort_lds(S, P, (int)n, tid, nthr);
 }
 
-// [n][stride] columns -> day-major [len][n] keys and n per day.  key(o) is the key of the cell at offset o = s * stride + t, or +inf where
-// the cell is not in the day's sample; the callers differ only in it.  32 x 32 tiles, LDS rows padded to 33 words.
-template <class Key> __global__ __launch_bounds__(256) void xs_prep_kernel(Key key, Dims d, double *out, int32_t *n_valid) {
-    __shared__ double tile[32][33];
+// [n][stride] columns -> NK day-major [len][n] key rows, `pitch` doubles apart, and n per day.  key(o, k) sets k[0 .. NK) to the keys of the
+// cell at offset o = s * stride + t and leaves them +inf where the cell is not in the day's sample (the same sample for every row: it is
+// counted on row 0); the callers differ only in it.  32 x 32 tiles, LDS rows padded to 33 words.
+template <int NK, class Key>
+__global__ __launch_bounds__(256) void xs_prep_kernel(Key key, Dims d, double *out, int64_t pitch, int32_t *n_valid) {
+    __shared__ double tile[NK][32][33];
     __shared__ int cnt[32];
     const int64_t t0 = (int64_t)blockIdx.x * 32, s0 = (int64_t)blockIdx.y * 32;
     const int lx = threadIdx.x & 31, ly = threadIdx.x >> 5; // 32 x 8
     if (threadIdx.x < 32) cnt[threadIdx.x] = 0;
     for (int i = ly; i < 32; i += 8) { // rows = symbols, lanes along days (coalesced reads)
         const int64_t s = s0 + i, t = t0 + lx;
-        tile[i][lx] = (s < d.n && t < d.len) ? key(s * d.stride + t) : xs_inf();
+        double k[NK];
+#pragma unroll
+        for (int j = 0; j < NK; j++) k[j] = xs_inf();
+        if (s < d.n && t < d.len) key(s * d.stride + t, k);
+#pragma unroll
+        for (int j = 0; j < NK; j++) tile[j][i][lx] = k[j];
     }
     __syncthreads();
     for (int i = ly; i < 32; i += 8) { // rows = days, lanes along symbols (coalesced writes)
         const int64_t t = t0 + i, s = s0 + lx;
-        const double k = tile[lx][i];
         if (t < d.len && s < d.n) {
-            out[t * d.n + s] = k;
-            if (k != xs_inf()) atomicAdd(&cnt[i], 1);
+#pragma unroll
+            for (int j = 0; j < NK; j++) out[j * pitch + t * d.n + s] = tile[j][lx][i];
+            if (tile[0][lx][i] != xs_inf()) atomicAdd(&cnt[i], 1);
         }
     }
     __syncthreads();
@@ -131,6 +140,44 @@ template <bool PAD> __device__ __forceinline__ int64_t xs_tie_run(XsRow<PAD> S, 
         b = lo;
     }
     return (int64_t)a + (int64_t)b;
+}
+
+// The sort-then-look-up kernel pair: sort one day's key row, then let every symbol look itself up in the sorted row.  What is looked
+// up and where it goes is the file's operation Op:
+//   MAX_STEPS, steps()     1 .. 3 sorts per day, each followed by one look-up per symbol; steps() <= MAX_STEPS may depend on the call
+//   row(step)              the day-major [len][n] key rows that step sorts
+//   unsorted(nv)           the day is not sorted at all (uniform across the workgroup); fill(i) is what cell i = t * n + s gets then
+//   at(step, S, nv, i)     the look-up of cell i in the sorted row S[0 .. nv); a later step may read what an earlier one wrote to cell i
+// one workgroup per day, n <= XS_LDS_MAX: every step sorts its row in the same LDS row
+template <class Op> __global__ __launch_bounds__(1024) void xs_sort_lds_kernel(Op op, const int32_t *n_valid, int64_t n, int P) {
+    extern __shared__ __align__(16) unsigned char xs_lds[];
+    double *S = (double *)xs_lds;
+    const int64_t o = (int64_t)blockIdx.x * n;
+    const int tid = threadIdx.x, nthr = blockDim.x, nv = n_valid[blockIdx.x];
+    if (op.unsorted(nv)) {
+        for (int s = tid; s < n; s += nthr) op.fill(o + s);
+        return;
+    }
+#pragma unroll
+    for (int step = 0; step < Op::MAX_STEPS; step++) {
+        if (step >= op.steps()) break;
+        if (step) __syncthreads(); // every search of the row before is done before the LDS row is loaded again
+        xs_load_sort_row(S, op.row(step) + o, n, P, tid, nthr); // thread tid loads the cells tid, tid + nthr, ...: the ones it writes below
+        for (int s = tid; s < n; s += nthr) op.at(step, XsRow<true>{S}, nv, o + s);
+    }
+}
+// n > XS_LDS_MAX: step's rows were sorted by rocPRIM (sorted); one launch per step.  A day that is not sorted is filled by step 0 and
+// left alone by the later steps.
+template <class Op>
+__global__ __launch_bounds__(256) void xs_sort_wide_kernel(Op op, int step, const double *sorted, const int32_t *n_valid, int64_t n) {
+    const int64_t o = (int64_t)blockIdx.x * n;
+    const int nv = n_valid[blockIdx.x];
+    if (op.unsorted(nv)) {
+        if (step == 0)
+            for (int64_t s = threadIdx.x; s < n; s += 256) op.fill(o + s);
+        return;
+    }
+    for (int64_t s = threadIdx.x; s < n; s += 256) op.at(step, XsRow<false>{sorted + o}, nv, o + s);
 }
 
 // Sequential statistics of a series x[0 .. len) over its non-NaN entries, in ascending order from 0.0.  SQ = false: count, sum and
@@ -209,3 +256,38 @@ struct XsDaySort { bool wide; size_t tmp_bytes, o_off, o_tmp, bytes; };
 pq_status xs_day_sort_plan(pq_ctx *ctx, const Dims &d, const char *who, XsDaySort *plan);
 // sorts every day-major row of key[len][n] on ctx->stream; *sorted = the sorted rows (inside the tail)
 pq_status xs_day_sort_wide(pq_ctx *ctx, const Dims &d, const XsDaySort &plan, unsigned char *tail, const double *key, const double **sorted);
+
+namespace {
+// the host side of the sort-then-look-up pair: one workgroup per day in LDS, or one rocPRIM sort and one look-up launch per step.
+// `tail` is the wide tail of the caller's workspace, nv the n per day of xs_prep_kernel.
+template <class Op>
+pq_status xs_sort_lookup(pq_ctx *ctx, const Dims &d, const XsDaySort &plan, unsigned char *tail, const Op &op, const int32_t *nv) {
+    const dim3 grid((unsigned)d.len);
+    if (!plan.wide) {
+        const XsLds L = xs_lds_shape(d.n);
+        PQ_HIP_TRY(hipFuncSetAttribute((const void *)xs_sort_lds_kernel<Op>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)L.bytes));
+        hipLaunchKernelGGL(xs_sort_lds_kernel<Op>, grid, dim3(L.nthr), L.bytes, ctx->stream, op, nv, d.n, L.P);
+        return PQ_OK;
+    }
+    for (int step = 0; step < op.steps(); step++) {
+        const double *srt;
+        PQ_TRY(xs_day_sort_wide(ctx, d, plan, tail, op.row(step), &srt));
+        hipLaunchKernelGGL(xs_sort_wide_kernel<Op>, grid, dim3(256), 0, ctx->stream, op, step, srt, nv, d.n);
+    }
+    return PQ_OK;
+}
+} // namespace
+
+// ---------------------------------------------------------------- host side of the cells stage (sorts.hip)
+// workspace of a sort into cells, offsets in bytes: nkey key rows (f64, day-major, key_pitch doubles apart, from 0) | n per day (i32) |
+// labels day-major (u8) | labels symbol-major (u8, only when the caller passes none) | block partials: sums (f64), counts, new members
+// (i32) | the wide tail of xs_day_sort_plan
+struct XsCellsWs { size_t key_pitch, o_nv, o_ldm, o_lsm, o_ps, o_pc, o_pn, o_tail, bytes; };
+XsCellsWs xs_cells_layout(const Dims &d, int nkey, int ncell, bool caller_labels, const XsDaySort &plan);
+// day-major labels at ctx->ws + ws.o_ldm (cells 0 .. ncell-1, PQ_LABEL_MID, PQ_LABEL_OUT) -> labels symbol-major (into `labels`, or the
+// workspace) -> mean / count / turnover [ncell][len] of `ret`, on ctx->stream
+pq_status xs_cells_stats(pq_ctx *ctx, const Dims &d, const XsCellsWs &ws, int ncell, uint8_t *labels, const double *ret, double *mean,
+                         int32_t *count, double *tov);
+// summary rows: the ncell cells (mean, turnover), then e0.n and e1.n rows of further [.][len] series without turnover
+struct XsRows { const double *x; int n; };
+pq_status xs_cells_summary(pq_ctx *ctx, int64_t len, int ncell, const double *mean, const double *tov, XsRows e0, XsRows e1, double *summary);

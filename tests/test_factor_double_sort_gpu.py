@@ -141,11 +141,13 @@ def test_wide_cross_section_segmented_sort(pq, n):
         check(a, b, r, 3, 4, dependent)
 
 
-@pytest.mark.parametrize("grid", [(2, 2), (4, 8), (5, 7), (8, 8), (7, 10), (9, 10), (10, 10)], ids=lambda g: f"C{g[0] * g[1]}")
+@pytest.mark.parametrize("grid", [(2, 2), (2, 3), (2, 5), (3, 4), (4, 5), (3, 7), (4, 8), (5, 7), (8, 8), (7, 10), (9, 10), (10, 10)],
+                         ids=lambda g: f"C{g[0] * g[1]}")
 def test_cell_tiles(pq, grid):
-    """the aggregate holds DS_CT = 32 cells per LDS tile and walks the tiles with blockIdx.z: C = 32 | 35, 64 | 70, 90 | 100 lie on
-    both sides of every tile count 1 | 2 | 3 | 4 that a Qa x Qb grid can reach (33, 65 and 97 are no products of two numbers in
-    [2, 10]); C = 4 and C = 100 are the ends; two blocks of symbols"""
+    """the cells stage picks the accumulator form by the cell count.  Up to 20 cells they are registers: C = 4 in <5>, C = 6 and 10 in
+    <10>, C = 12 and 20 in <20> (<2> has no Qa x Qb grid).  C = 21 is the first count in LDS tiles of XS_CT = 32 cells, walked with
+    blockIdx.z: C = 32 | 35, 64 | 70, 90 | 100 lie on both sides of every tile count 1 | 2 | 3 | 4 that a Qa x Qb grid can reach (33,
+    65 and 97 are no products of two numbers in [2, 10]); C = 4 and C = 100 are the ends; two blocks of symbols"""
     a, b, r = make("nulls", 300, 20, 9)
     for dependent in MODES:
         check(a, b, r, *grid, dependent)
@@ -171,6 +173,26 @@ def test_odd_row_pitch(pq):
     for dependent in MODES:
         got, _ = check(a, b, r, 2, 3, dependent, pitch=139)
         assert got["labels"].stride(0) == 139
+
+
+def test_labels_omitted_against_labels_given(pq):
+    """labels=False: the cells stage keeps the symbol-major labels in its workspace at row pitch len (the turnover reads day t - 1
+    there); labels=True: in the caller's matrix at the inputs' pitch.  n = 257 (a second block of one symbol), T = 65 (a second day
+    tile of one day), inputs at pitch 71: every other output of the single sorts and of the double sort is the same, bit for bit"""
+    from polars_quant_amd import api
+    a, b, r = make("nulls", 257, 65, 15)
+    ad, bd, rd = (to_dev(x, 71) for x in (a, b, r))
+    calls = {"quantiles": lambda lab: api.factor_quantiles(bd, rd, 7, labels=lab),
+             "long_short": lambda lab: api.factor_long_short(bd, rd, 0.3, 0.2, labels=lab),
+             "double independent": lambda lab: api.factor_double_sort(ad, bd, rd, 3, 4, False, labels=lab),
+             "double dependent": lambda lab: api.factor_double_sort(ad, bd, rd, 3, 4, True, labels=lab)}
+    for name, call in calls.items():
+        without, given = call(False), call(True)
+        assert "labels" not in without and given["labels"].stride(0) == 71
+        assert set(without) == set(given) - {"labels"}
+        for k, v in without.items():
+            identical(f"{name} {k}", v, given[k])
+        assert int(given["count"].sum()) > 0 and bool((given["turnover"][:, 1:] > 0.0).any())     # the calls compared something
 
 
 def test_factor_method_shapes_and_defaults(pq):

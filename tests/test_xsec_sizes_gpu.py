@@ -10,7 +10,7 @@ Where each branch is reached (the failure tags name function, shape, Q / K / L /
 |   max(16, n), xs_groups / cl_bounds_lds_kernel  |   256 [n255, n256], 1 024 [n1024], 2 048 [n1025, n2048], 8 192 [n4097, n8192] |
 | n = P: a row without a +inf tail                |   [n16, n32, n128, n256, n1024, n2048, n8192, n16384] (days 0, 1, 3)          |
 | n = 16 384, the largest LDS row (136 KiB)       |   [n16384], with [n16383] and [n8193] below it                                |
-| xs_group_partial_kernel<G> with ng < G          | test_every_group_count: G = 5 [q3, q4], G = 10 [q6 .. q9], G = 20 [q11 .. q19] |
+| xs_cell_partial_reg_kernel<G> with C < G        | test_every_group_count: G = 5 [q3, q4], G = 10 [q6 .. q9], G = 20 [q11 .. q19] |
 | rg_dispatch<K, false>, K = 4, 5, 6, 7           | test_xsec_regress_every_k[K4-*, K5-*, K6-*, K7-*]                             |
 | rg_dispatch<K, true>, K = 4, 5, 6, 7            | test_ts_regress_every_k[K4-*, K5-*, K6-*, K7-*]                               |
 | CPU pin of K = 4 .. 7 against lstsq             | test_factor_regress_ref.py: test_against_lstsq_and_inverse_normal_equations,  |
@@ -64,15 +64,15 @@ Where each branch is reached (the failure tags name function, shape, Q / K / L /
 | CPU pin of K = 2 .. 8 against lstsq             | test_factor_orth_ref.py: test_against_lstsq_and_orthogonal,                   |
 |                                                 |   test_sample_size_thresholds, test_every_solved_level_count                  |
 | D-20, build.hip                                 |                                                                               |
-| bd_rank_lds_kernel at every P = 16 .. 16 384    | test_build_rank_sort_sizes: P = 16 [n16], 32 [n17 .. n32], 64 [n33], 128      |
-|   (64 .. 1 024 threads); xs_tie_run's last slot |   [n65, n128], 256 [n255, n256], 512 [n257 .. n512], 1 024 [n513, n1024],     |
-|   on a row with n == P and no +inf tail         |   2 048 [n1025, n2048], 4 096 [n2049], 8 192 [n4097, n8192], 16 384 [n8193 .. |
+| xs_sort_lds_kernel<BdRankOp> at every P = 16 .. | test_build_rank_sort_sizes: P = 16 [n16], 32 [n17 .. n32], 64 [n33], 128      |
+|   16 384 (64 .. 1 024 threads); xs_tie_run's    |   [n65, n128], 256 [n255, n256], 512 [n257 .. n512], 1 024 [n513, n1024],     |
+|   last slot on a row with n == P, no +inf tail  |   2 048 [n1025, n2048], 4 096 [n2049], 8 192 [n4097, n8192], 16 384 [n8193 .. |
 |                                                 |   n16384]; days 0, 1, 3 have n_valid == n (asserted on the input's sample)    |
 | nv == 0 (the return before the barrier), nv of  |   day 5 has no member, day 4 has 1 - 3, day 0 is one tie run of length n      |
 |   1 - 3 under a +inf tail, one tie run of n     |   (up to n = 16 384)                                                          |
 | pq_factor_rank(mode = 2, descending = 1), which |   every case, and test_build_wide_path, through the C ABI against             |
 |   the Python layer refuses                      |   rank(f, "quantile", True)                                                   |
-| wide (rocPRIM) rank: bd_rank_sorted_kernel on   | test_build_wide_path[n16385, n100000]: days all equal / all NULL / one member |
+| wide (rocPRIM) rank: xs_sort_wide_kernel on     | test_build_wide_path[n16385, n100000]: days all equal / all NULL / one member |
 |   an all-NULL day, a one-member day, one tie    |   / ties, signed zeros and ~5 % NULL, NaN, +-inf; n = 16 385 also at pitch 5  |
 |   run of n; the limit and above it              | test_build_above_the_limit: n = 100 001, the rank family raises and writes    |
 |                                                 |   nothing, minmax / zscore / weighted (G = 6, 256) / ratio / diff compute     |
@@ -90,6 +90,8 @@ Where each branch is reached (the failure tags name function, shape, Q / K / L /
 |   range, a range that overflows; W = +inf       |   overflowing range and W = +inf compare non-NULL NaN with non-NULL NaN       |
 | ctx->ws reuse: wide rank, LDS rank, grouped     | test_build_workspace_reuse: one context, five calls, the last bitwise equal   |
 |   weighted, minmax, wide rank again             |   to the first                                                                |
+| ctx->ws reuse across xs_cells_layout: 1 and 2   | test_sorts_workspace_reuse: quantiles, 5 x 5 dependent, long-short, 2 x 3     |
+|   key rows, register and LDS cells, wide tail   |   independent at n = 16 385, rank, quantiles again bitwise equal to the first  |
 
 Every size family has one case at an odd row pitch: n = 257 (sorts, rank sort sizes, lag tiles, group tiles, every orth K, the D-20 rank
 sizes), q = 7, n = 257 (xsec K), T = 257 (ts K), T = 2 049 (summaries, robust summaries), the wide percentile clean, the wide rank
@@ -101,6 +103,7 @@ import pytest
 
 import test_factor_build_gpu as BG
 import test_factor_clean_gpu as CL
+import test_factor_double_sort_gpu as DS
 import test_factor_orth_gpu as OG
 import test_factor_orth_ref as OR
 import test_factor_regress_gpu as RG
@@ -183,7 +186,7 @@ def discrete3000():
 
 @pytest.mark.parametrize("q", range(2, 21), ids=[f"q{q}" for q in range(2, 21)])
 def test_every_group_count(pq, q, discrete3000):
-    """every Q: ng < G in each xs_group_partial_kernel<G> bucket (G = 5: Q 3, 4; G = 10: Q 6 .. 9; G = 20: Q 11 .. 19)"""
+    """every Q: C < G in each xs_cell_partial_reg_kernel<G> bucket (G = 5: Q 3, 4; G = 10: Q 6 .. 9; G = 20: Q 11 .. 19)"""
     f, r = S.make("nulls", 300, 131, 50 + q)
     S.check_groups(pq, f, r, 0, q, pitch=139 if q == 7 else None)
     S.check_groups(pq, *discrete3000, 0, q)
@@ -614,7 +617,7 @@ def wide_days(n, seed):
 
 @pytest.mark.parametrize("n", [16385, 100000], ids=["n16385", "n100000"])
 def test_build_wide_path(pq, n):
-    """n > 16 384: ranks from rocPRIM's segmented sort and bd_rank_sorted_kernel, one symbol above the LDS limit and at the documented
+    """n > 16 384: ranks from rocPRIM's segmented sort and xs_sort_wide_kernel, one symbol above the LDS limit and at the documented
     limit; n = 16 385 also at an odd row pitch"""
     f = wide_days(n, n)
     nv = R.valid(f).sum(axis=0)
@@ -822,3 +825,19 @@ def test_build_workspace_reuse(pq):
     again = F.rank(fwd, ascending=False, pct=True).cpu().numpy()
     BG.same("wide rank, again", again, exp_w)
     BG.same("wide rank, again against first", again, first)
+
+
+def test_sorts_workspace_reuse(pq):
+    """one context, six calls through the one workspace layout of the cells stage: one key row and five cells, two key rows and 25
+    cells in LDS tiles, two cells, the wide tail behind two key rows and six register cells, the rank's own layout, then the first
+    call again; every call against its reference, and no result depends on what the call before left in the workspace"""
+    f, r = S.make("nulls", 300, 131, 81)
+    first = S.check_groups(pq, f, r, 0, 5)
+    a, b, r2 = DS.make("nulls", 300, 131, 82)
+    DS.check(a, b, r2, 5, 5, True)
+    S.check_groups(pq, f, r, 1, 0, 0.3, 0.3)
+    DS.check(*DS.sized(16385, 4, 83), 2, 3, False)
+    BG.check_rank(pq, build_days(300, 84), tag="after the wide double sort")
+    again = S.check_groups(pq, f, r, 0, 5)
+    for k, v in first.items():
+        assert again[k].shape == v.shape and torch.equal(DS.bits(again[k]), DS.bits(v)), k
