@@ -663,6 +663,25 @@ pq_status pq_factor_clean(pq_ctx *, const pq_batch *, const double *factor, int3
  * [len]; summary (Fama-MacBeth, NULL: not written): [k + 1][PQ_REGRESS_SUMMARY_COLS] over the days with a solution */
 pq_status pq_xsec_regress(pq_ctx *, const pq_batch *, const double *const *factors, int32_t k, const double *fwd_return, double *coef,
                           double *t_stat, double *p_value, double *r2, int32_t *n_obs, double *summary);
+/* D-32: the weighted per-day cross-sectional regression on k factors AND n_groups industry dummies, r_i = g_ind(i) + sum_j b_j f_ij + e_i
+ * minimising sum_i w_i e_i^2 -- the pure factor returns, the industry returns and the specific (residual) returns.  No separate
+ * intercept (the dummies span it); group NULL puts every symbol in group 0 (n_groups must be 1), whose row is the intercept.  weight: f64
+ * on the batch's row pitch, NULL = 1.0; group: int32 codes, [n_series] (group_stride 0) or [n_series][group_stride] (group_stride >=
+ * len).  A day's sample: return and all k factors non-null and finite, the weight non-null, finite and > 0, the code in [0, n_groups).
+ * The dummies are eliminated exactly (weighted demeaning within each industry), the k x k system is D-17's; every sum is D-12's blocked
+ * sum, so coef / t / R^2 / n / resid are bit-exact (DESIGN.md D-32 has the order; with weights of 1.0 and one group the results are
+ * pq_xsec_regress's bit for bit).  coef / t_stat / p_value: [k + n_groups][len], the factors, then the industries; r2: [2][len], total
+ * (against the day's weighted mean return) and within (against the industry means); n_obs: the sample; n_groups_present: the industries
+ * with a member; resid (NULL: not written): [n_series][stride], e on the sample's cells of solved days, NULL elsewhere; summary (NULL:
+ * not written): [k + n_groups][PQ_REGRESS_SUMMARY_COLS], D-17's Fama-MacBeth row of every coefficient row.  No solution (every output
+ * but n_obs and n_groups_present NULL) where a pivot is singular or n < k + n_groups_present + 1; an industry's rows are NULL on a day it
+ * has no member; p on n - k - n_groups_present degrees of freedom; t and p NULL where se == 0, each R^2 where its denominator is 0.
+ * len = 0 launches nothing; n_series = 0 is allowed.  Ragged batches and suite recording are refused.  Uses the context workspace (~8
+ * (k + 3) n_groups bytes per day, plus at most 8 * 128 bytes (8 n_groups above 128 groups) per (day, block of 256 symbols)). */
+pq_status pq_xsec_regress_wls(pq_ctx *, const pq_batch *, const double *const *factors, int32_t k, const double *fwd_return,
+                              const double *weight, const int32_t *group, int64_t group_stride, int32_t n_groups, double *coef,
+                              double *t_stat, double *p_value, double *r2, int32_t *n_obs, int32_t *n_groups_present, double *resid,
+                              double *summary);
 /* per-symbol time-series regression over the days.  Bit j of series_mask: factors[j] is one [len] series shared by every symbol (e.g. a
  * market return).  coef / t_stat / p_value: [n_series][k + 1] (column k = the intercept); r2 / n_obs: [n_series] */
 pq_status pq_ts_regress(pq_ctx *, const pq_batch *, const double *const *factors, int32_t k, uint32_t series_mask, const double *ret,

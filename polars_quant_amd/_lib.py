@@ -138,6 +138,7 @@ ic_stats               i pplp
 factor_portfolio       i pBpiippplddppp
 factor_clean           i pBpidppiip
 xsec_regress           i pBpippppppp
+xsec_regress_wls       i pBpippplipppppppp
 ts_regress             i pBpiupppppp
 corr_t_test            i ppplpp
 linear                 i pBpipppppppp

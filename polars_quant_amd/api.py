@@ -757,6 +757,46 @@ def xsec_regress(factors, fwd_return, summary: bool = True):
     return out
 
 
+def xsec_regress_wls(factors, fwd_return, weight=None, industry=None, summary: bool = True, resid: bool = False):
+    """D-32: per-day weighted cross-sectional regression of the forward return on K factors (each [N, T]; a list or a [K, N, T] array)
+    and G industry dummies, without a separate intercept.  weight [N, T] (None: 1.0; a symbol needs a finite weight > 0), industry int
+    codes [N] or [N, T] (negative = unclassified, at most 256 industries, G = max code + 1; None: one group, whose row is the intercept)
+    -> dict of device tensors: coef / t_stat / p_value [K + G, T] (the factors, then the industries), r_squared / r_squared_within
+    [T], n / n_industries [T] (int32), with summary=True the Fama-MacBeth summary [K + G, 5], with resid=True resid [N, T]"""
+    cols, (n, T) = _regress_args(factors, fwd_return, False)
+    K = len(cols)
+    ind, G = None, 1
+    if industry is not None:
+        ind = _int_codes(industry, "industry")
+        if tuple(ind.shape) not in ((n,), (n, T)):
+            raise ValueError(f"industry must be [N] or [N, T] with N = {n}, T = {T}, not {tuple(ind.shape)}")
+        G = _n_codes(ind, "industry", MAX_INDUSTRIES)
+    if weight is not None and _shape(weight) != (n, T):
+        raise ValueError(f"weight must have the return's shape {(n, T)}, not {_shape(weight)}")
+    # the weight rides in front of the return, so that _regress_upload puts it on the common pitch with the factors
+    fs, _, r, _ = _regress_upload(cols + ([weight] if weight is not None else []), fwd_return, False)
+    w = fs.pop() if weight is not None else None
+    ptrs = (C.c_void_p * K)(*[f.data_ptr() for f in fs]) if r.numel() else None
+    dev = r.device
+    b = _batch(r)
+    gp, gs = (None, 0) if ind is None else _codes_on_pitch(ind, b, dev)
+    f64 = dict(dtype=torch.float64, device=dev)
+    coef, t, p = (torch.empty((K + G, T), **f64) for _ in range(3))
+    r2 = torch.empty((2, T), **f64)
+    nobs, gt = (torch.empty(T, dtype=torch.int32, device=dev) for _ in range(2))
+    res = torch.empty_strided((n, T), (b.stride, 1), **f64) if resid else None
+    summ = torch.empty((K + G, REGRESS_SUMMARY_COLS), **f64) if summary else None
+    _call("pq_xsec_regress_wls", dev, b, ptrs, K, r, w, gp, gs, G, coef, t, p, r2, nobs, gt, res, summ)
+    out = {"coef": coef, "t_stat": t, "p_value": p, "r_squared": r2[0], "r_squared_within": r2[1], "n": nobs, "n_industries": gt}
+    if summ is not None:
+        if T == 0:      # no day: nothing was launched
+            summ.copy_(torch.tensor([[0.0] + [float("nan")] * 4] * (K + G), dtype=torch.float64))
+        out["summary"] = summ
+    if res is not None:
+        out["resid"] = res
+    return out
+
+
 def ts_regress(factors, returns):
     """D-17: per-symbol time-series OLS of returns [N, T] on K factors, each [N, T] or a [T] series shared by every symbol (a list, or a
     [K, N, T] array), with an intercept -> dict of device tensors: coef / t_stat / p_value [N, K + 1] (column K = the intercept),

@@ -333,6 +333,34 @@ class Factor:
         s = r.pop("summary")
         return {"mean_coef": s[:, 1], "std_coef": s[:, 2], "t_stat": s[:, 3], "p_value": s[:, 4], "n_days": s[:, 0], "daily": r}
 
+    # ---- D-32: weighted cross-sectional regression with industry dummies
+    def pure_factor_return(self, factors, next_return, weight=None, industry=None, specific_return=False):
+        """The per-day weighted regression of the next return on K style factors and the industry dummies (no separate intercept).
+        factors: a list of [N, T] arrays or one [K, N, T] array; weight [N, T] (e.g. sqrt(cap); None: equal); industry int codes [N] or
+        [N, T] (negative = unclassified, G = max code + 1 <= 256; None: no industries, and "intercept" replaces "industry_return").
+        -> {"factor_return", "t_stat", "p_value": [K, T]; "industry_return", "industry_t_stat", "industry_p_value": [G, T] (or
+        "intercept", "intercept_t_stat", "intercept_p_value": [T]); "r_squared", "r_squared_within", "n", "n_industries": [T];
+        "summary": {"factor" / "industry" (or "intercept"): {"mean_coef", "std_coef", "t_stat", "p_value", "n_days"}}, the
+        Fama-MacBeth rows; with specific_return=True "specific_return" [N, T], the residual (NULL outside the day's sample)}"""
+        r = _api.xsec_regress_wls(factors, next_return, weight, industry, summary=True, resid=specific_return)
+        K = len(factors) if isinstance(factors, (list, tuple)) else _api._shape(factors)[0]
+        s = r["summary"]
+
+        def fm(rows):
+            return {"mean_coef": rows[:, 1], "std_coef": rows[:, 2], "t_stat": rows[:, 3], "p_value": rows[:, 4], "n_days": rows[:, 0]}
+        out = {"factor_return": r["coef"][:K], "t_stat": r["t_stat"][:K], "p_value": r["p_value"][:K]}
+        if industry is not None:
+            out.update({"industry_return": r["coef"][K:], "industry_t_stat": r["t_stat"][K:], "industry_p_value": r["p_value"][K:]})
+            summ = {"factor": fm(s[:K]), "industry": fm(s[K:])}
+        else:
+            out.update({"intercept": r["coef"][K], "intercept_t_stat": r["t_stat"][K], "intercept_p_value": r["p_value"][K]})
+            summ = {"factor": fm(s[:K]), "intercept": fm(s[K:])}
+        out.update({"r_squared": r["r_squared"], "r_squared_within": r["r_squared_within"], "n": r["n"],
+                    "n_industries": r["n_industries"], "summary": summ})
+        if specific_return:
+            out["specific_return"] = r["resid"]
+        return out
+
     def time_series_regression(self, factors, returns):
         """factors: a list of [N, T] or [T] arrays (a [T] series, e.g. a market return, is shared by every symbol) or one [K, N, T]
         array -> {"coefficient", "t_stat", "p_value": [N, K + 1] (the intercept last), "r_squared", "n_obs": [N]}, one OLS per symbol
