@@ -860,6 +860,53 @@ pq_status pq_factor_combine_weights(pq_ctx *, const double *ic /* device [k][len
 pq_status pq_factor_combine(pq_ctx *, const pq_batch *, const double *const *factors, int32_t k, const double *weights /* device [k][len] */,
                             int32_t normalize, double *out);
 
+/* ---- rank 3, continued: the risk model on the series of pq_xsec_regress_wls, Factor.risk_model / Factor.portfolio_risk (beyond the
+ * README; decision D-33 in DESIGN.md section 2).  Everything is evaluated on `count` AS-OF days t_d = day0 + d * step, d = 0 .. count - 1
+ * (day0 >= 0, step >= 1, count >= 0, day0 + (count - 1) * step < len, else PQ_ERR_ARG); the model of day t reads the rows t-w+1 .. t of its
+ * inputs and nothing later.
+ * The one arithmetic, rk_wcov(a, b) of two windows a[0 .. w), b[0 .. w) (oldest to newest) under the weights omega[0 .. w) (omega[w-1]
+ * weights the as-of day): the sample P is every k whose day t-w+1+k >= 0, whose a[k] and b[k] are both non-null and finite and whose
+ * omega[k] > 0; n = |P|.  Over P in ascending k from 0.0, every product rounded before it is added: W = sum omega, W2 = sum (omega omega),
+ * Sa = sum (omega a), Sb = sum (omega b), ma = Sa / W, mb = Sb / W, C = sum (omega (a - ma)) (b - mb).  cov = C / (W - W2 / W) when
+ * unbiased (reliability weights; n - 1 for equal weights), C / W otherwise.  NULL where n < min_periods, where unbiased and n < 2, where
+ * the denominator is not > 0 and where the result is NaN (+-inf passes).  With every omega 1.0, unbiased, min_periods = w and a full
+ * window this is pq_factor_ts_pair's op 0 bit for bit; doubling every omega changes no bit; cov(a, b) and cov(b, a) are bit-identical where omega (a - ma) is exact (equal weights) and may
+ * differ in the last bit otherwise, which is why the matrix is written from one evaluation per unordered pair.
+ * omega is a DEVICE array of `window` doubles that the entry points do not read (finite, >= 0 and not all 0 is the caller's to check).
+ * 1 <= window <= PQ_FACTOR_ROLLING_MAX_WINDOW, 1 <= min_periods <= window, min_periods >= 2 when unbiased; a null required pointer and an
+ * output that overlaps an input or another output are PQ_ERR_ARG; ragged batches and suite recording are refused (PQ_ERR_UNSUPPORTED);
+ * count = 0, len = 0 or n_series = 0 launches nothing.  No workspace.
+ *   pq_risk_factor_cov:   the batch is the M = n_series series [M][stride] (D-32's coef block), 1 <= M <= PQ_RISK_MAX_SERIES.  cov_out
+ *                         [count][M][M]: entry [d][j][l], l <= j, is rk_wcov(f_j, f_l), mirrored to [d][l][j] (one evaluation per unordered
+ *                         pair: exactly symmetric).  n_out (NULL: not written) [count][M]: the n of the diagonal.
+ *   pq_risk_specific_var: the batch is [n_series][stride]; var_out[s * out_stride + d] = rk_wcov(x_s, x_s), out_stride >= count; n_out
+ *                         (NULL: not written) on the same layout. */
+#define PQ_RISK_MAX_SERIES (PQ_REGRESS_MAX_K + PQ_IC_MAX_GROUPS)
+pq_status pq_risk_factor_cov(pq_ctx *, const pq_batch *, const double *f, const double *omega /* device [window] */, int64_t window,
+                             int64_t min_periods, int32_t unbiased, int64_t day0, int64_t step, int64_t count,
+                             double *cov_out /* [count][M][M] */, int32_t *n_out /* [count][M] */);
+pq_status pq_risk_specific_var(pq_ctx *, const pq_batch *, const double *x, const double *omega /* device [window] */, int64_t window,
+                               int64_t min_periods, int32_t unbiased, int64_t day0, int64_t step, int64_t count, double *var_out,
+                               int64_t out_stride, int32_t *n_out);
+/* The predicted risk of the holdings [n_series][stride] on the as-of days.  exposures is a HOST array of 0 <= k <= PQ_REGRESS_MAX_K device
+ * pointers on the batch's row pitch; industry / group_stride / n_groups = G are pq_xsec_regress_wls's (NULL: G = 1 and every symbol in
+ * group 0, so row k is the net weight); cov [count][M][M] with M = k + G and specific_var [n_series][sv_stride] (sv_stride >= count) are
+ * the two calls' outputs, indexed by d.  Per as-of day: the held set H is every symbol whose holding h is non-null, finite and != 0;
+ * a held symbol is UNCOVERED where an exposure is null or not finite, a given code lies outside [0, G), or its specific variance is not
+ * >= 0 (NULL, NaN or negative).  n_out [2][count]: |H| and the uncovered count.  With |H| = 0 or anything uncovered every f64 output of
+ * the day is NULL.  X[j] = sum_H (h x_j), X[k + g] = sum over H in g of h, S = sum_H (h h) s^2, each D-12's blocked sum (blocks of 256 symbol
+ * indices, ascending from 0.0, block sums in ascending order).  For every row j with X[j] != 0: v_j = sum_l cov[j][l] X[l] over ascending l
+ * with X[l] != 0 from 0.0, c_j = X[j] v_j; c_j = 0.0 where X[j] == 0; a NULL cov[j][l] that a sum needs makes the day NULL.  factor_var =
+ * sum_j c_j (ascending from 0.0), total = factor_var + S, vol = sqrt(total), NULL where total < 0 (pairwise-complete covariances need
+ * not be positive semi-definite).  A value that comes out NaN is NULL.  exposure_out / contribution_out: [M][count]; risk_out
+ * [4][count]: factor_var, specific_var, total_var, volatility.  k, n_groups, group_stride, sv_stride or the as-of days out of range and a
+ * null pointer are PQ_ERR_ARG; ragged batches and suite recording are refused; count = 0 launches nothing.  Uses the context workspace
+ * (~8 (M + 1) bytes per (as-of day, block of 256 symbols)). */
+pq_status pq_risk_portfolio(pq_ctx *, const pq_batch *, const double *holdings, const double *const *exposures, int32_t k,
+                            const int32_t *industry, int64_t group_stride, int32_t n_groups, const double *cov, const double *specific_var,
+                            int64_t sv_stride, int64_t day0, int64_t step, int64_t count, double *exposure_out, double *contribution_out,
+                            double *risk_out, int32_t *n_out);
+
 /* ---- suites: record many calls, replay them as a few chip-filling grids ----
  * One indicator over N symbols is only N/64 wavefronts -- far too few for 256 CUs -- but a DataFrame query asks
  * for many indicators at once (df.with_columns([...]) in the reference; Polars then calls the plugin once per

@@ -156,6 +156,9 @@ factor_ts              i pBpilip
 factor_ts_pair         i pBppilp
 factor_combine_weights i ppilillp
 factor_combine         i pBpipip
+risk_factor_cov        i pBppllilllpp
+risk_specific_var      i pBppllilllplp
+risk_portfolio         i pBppiplippllllpppp
 suite_begin            i pB
 suite_end              i pp
 suite_abort            i p

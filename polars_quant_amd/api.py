@@ -1205,6 +1205,167 @@ def factor_combine(factors, weights, normalize: bool = True):
     return out[:, :T]
 
 
+RISK_MAX_SERIES = REGRESS_MAX_K + IC_MAX_GROUPS                # PQ_RISK_MAX_SERIES: the rows of xsec_regress_wls's coef block
+
+
+def risk_weights(window: int, halflife=None) -> np.ndarray:
+    """D-33: the weight vector of a risk window, numpy f64 [window], oldest day first: 0.5 ** ((window - 1 - k) / halflife), so the
+    as-of day weighs 1.0 and the day `halflife` days before it 0.5; halflife=None: ones (equal weights)"""
+    if isinstance(window, bool) or not isinstance(window, (int, np.integer)) or not 1 <= window <= ROLLING_MAX_WINDOW:
+        raise ValueError(f"window must be an integer in 1..{ROLLING_MAX_WINDOW}, not {window!r}")
+    if halflife is None:
+        return np.ones(int(window), dtype=np.float64)
+    hl = float(halflife)
+    if not (0.0 < hl < float("inf")):
+        raise ValueError(f"halflife must be finite and > 0, not {halflife!r}")
+    return 0.5 ** ((int(window) - 1 - np.arange(int(window), dtype=np.float64)) / hl)
+
+
+def _risk_args(weights, min_periods, unbiased):
+    """argument checks of risk_factor_cov / risk_specific_var that need no device -> the weights as a numpy f64 [window] array"""
+    if isinstance(weights, torch.Tensor):
+        weights = weights.detach().cpu().numpy()
+    w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64))
+    if w.ndim != 1:
+        raise ValueError(f"weights must be one-dimensional [window], not {w.shape}")
+    if not 1 <= w.shape[0] <= ROLLING_MAX_WINDOW:
+        raise ValueError(f"the window (the number of weights) must be in 1..{ROLLING_MAX_WINDOW}, not {w.shape[0]}")
+    if not np.isfinite(w).all() or (w < 0.0).any() or not (w > 0.0).any():
+        raise ValueError("weights must be finite and >= 0, with at least one > 0")
+    if isinstance(min_periods, bool) or not isinstance(min_periods, (int, np.integer)):
+        raise ValueError(f"min_periods must be an integer, not {min_periods!r}")
+    lo = 2 if unbiased else 1
+    if not lo <= min_periods <= w.shape[0]:
+        raise ValueError(f"min_periods must be in {lo}..{w.shape[0]} (the window){' for the unbiased estimate' if unbiased else ''}, "
+                         f"not {min_periods!r}")
+    return w
+
+
+def _risk_days(T, day0, step, count):
+    """the as-of days day0, day0 + step, ... of a series of T days -> (day0, step, count); count=None: every one that fits"""
+    for nm, v in (("day0", day0), ("step", step)) + ((("count", count),) if count is not None else ()):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+            raise ValueError(f"{nm} must be an integer, not {v!r}")
+    day0, step = int(day0), int(step)
+    if day0 < 0 or step < 1:
+        raise ValueError(f"the as-of days need day0 >= 0 and step >= 1, not day0 = {day0}, step = {step}")
+    fit = 0 if day0 >= T else (T - 1 - day0) // step + 1
+    if count is None:
+        return day0, step, fit
+    if not 0 <= count <= fit:
+        raise ValueError(f"count must be in 0..{fit}: the as-of days day0 + d * step must lie inside the {T} days, not {count!r}")
+    return day0, step, int(count)
+
+
+def _risk_windowed(fn_name, x, weights, min_periods, day0, step, count, unbiased, counts, max_series):
+    """the common path of risk_factor_cov (max_series given: [D, M, M]) and risk_specific_var ([N, D])"""
+    w = _risk_args(weights, min_periods, unbiased)
+    s = _shape(x)
+    if len(s) not in (1, 2):
+        raise ValueError(f"the series must be [M, T] or [T], not {s}")
+    M, T = (1, s[0]) if len(s) == 1 else s
+    if max_series is not None and M > max_series:
+        raise ValueError(f"at most {max_series} series, not {M}")
+    day0, step, D = _risk_days(T, day0, step, count)
+    t = _to_device(x)[0]
+    dev = t.device
+    if max_series is not None:
+        out = torch.empty((D, M, M), dtype=torch.float64, device=dev)
+        n = torch.empty((D, M), dtype=torch.int32, device=dev) if counts else None
+        extra = ()
+    else:
+        out = torch.empty((M, D), dtype=torch.float64, device=dev)
+        n = torch.empty((M, D), dtype=torch.int32, device=dev) if counts else None
+        extra = (D,)
+    if M and D:
+        om = torch.from_numpy(w).to(dev)
+        _call(fn_name, dev, _batch(t), t, om, len(w), int(min_periods), 1 if unbiased else 0, day0, step, D, out, *extra, n)
+    return (out, n) if counts else out
+
+
+def risk_factor_cov(series, weights, min_periods: int, day0: int = 0, step: int = 1, count=None, unbiased: bool = True,
+                    counts: bool = False):
+    """D-33: the weighted covariance matrix of M series [M, T] (the factor and industry returns of xsec_regress_wls: its coef block,
+    M <= 264) on the as-of days day0, day0 + step, ... (count of them; None: every one inside the T days) -> device tensor [D, M, M],
+    with counts=True (cov, n [D, M] int32: the sample size of the diagonal).  weights [window] (risk_weights), oldest day first, the last
+    one weighs the as-of day.  Entry [d, j, l] runs over the days of the window on which BOTH series are non-null and finite and the
+    weight is > 0 (pairwise-complete): C / (W - W2 / W) with unbiased (reliability weights), C / W otherwise, C the weighted sum of
+    products of deviations from the pair's own weighted means; NULL below min_periods such days.  Exactly symmetric.
+    The model of as-of day t reads the rows t - window + 1 .. t and nothing later.  xsec_regress_wls regresses the NEXT return, so its
+    row t -- and a model "as of t" -- is known one day later: shifting is the caller's (Factor.delay)."""
+    return _risk_windowed("pq_risk_factor_cov", series, weights, min_periods, day0, step, count, unbiased, counts, RISK_MAX_SERIES)
+
+
+def risk_specific_var(x, weights, min_periods: int, day0: int = 0, step: int = 1, count=None, unbiased: bool = True, counts: bool = False):
+    """D-33: the weighted variance of every symbol's series x [N, T] (the specific returns: xsec_regress_wls's resid) on the as-of days
+    -> device tensor [N, D], with counts=True (var, n [N, D] int32).  risk_factor_cov's diagonal arithmetic, bit for bit: the days of
+    the window on which the symbol is non-null and finite and the weight is > 0; NULL below min_periods of them.  The as-of days, the
+    weights and the one-day shift of a next-return regression are risk_factor_cov's."""
+    return _risk_windowed("pq_risk_specific_var", x, weights, min_periods, day0, step, count, unbiased, counts, None)
+
+
+def risk_portfolio(holdings, exposures, cov, specific_var, industry=None, day0: int = 0, step: int = 1):
+    """D-33: the predicted risk of the holdings [N, T] (weights or values; NULL or 0: not held) on the D as-of days day0 + d * step of
+    cov [D, M, M] (risk_factor_cov's) and specific_var [N, D] (risk_specific_var's).  exposures: a list of K [N, T] arrays or one
+    [K, N, T] array (0 <= K <= 8; None: K = 0), the factors of the regression; industry int codes [N] or [N, T] as in xsec_regress_wls,
+    M = K + G (None: G = 1, row K is the net weight, matching the intercept row).
+    -> dict of device tensors: exposure / contribution [M, D] (X = the holdings' exposure to every row, c_j = X_j (cov X)_j, which sum to
+    factor_var), factor_var / specific_var / total_var / volatility [D], n_held / n_uncovered [D] (int32).  A day is NULL where nothing
+    is held, where a held symbol is uncovered (an exposure that is NULL or not finite, a code outside [0, G), a specific variance that is
+    NULL or negative) and where a covariance that the product needs (both exposures != 0) is NULL.  Pairwise-complete covariances need not
+    be positive semi-definite: volatility is NULL where total_var < 0."""
+    hs = _shape(holdings)
+    if len(hs) != 2:
+        raise ValueError(f"holdings must be [N, T], not {hs}")
+    n, T = hs
+    cols = [] if exposures is None else _columns(exposures, "the number of exposures", 0, REGRESS_MAX_K, 3,
+                                                 "exposures must be a list of [N, T] arrays or one [K, N, T] array")
+    K = len(cols)
+    for j, c in enumerate(cols):
+        if _shape(c) != hs:
+            raise ValueError(f"exposure {j} must have the holdings' shape {hs}, not {_shape(c)}")
+    cs, vs = _shape(cov), _shape(specific_var)
+    if len(cs) != 3 or cs[1] != cs[2]:
+        raise ValueError(f"cov must be [D, M, M], not {cs}")
+    D, M = cs[0], cs[1]
+    G = M - K
+    ind = None
+    if industry is not None:
+        ind = _int_codes(industry, "industry")
+        if tuple(ind.shape) not in ((n,), (n, T)):
+            raise ValueError(f"industry must be [N] or [N, T] with N = {n}, T = {T}, not {tuple(ind.shape)}")
+        if not 1 <= G <= MAX_INDUSTRIES or _n_codes(ind, "industry", MAX_INDUSTRIES) > G:
+            raise ValueError(f"cov must be [D, K + G, K + G] with K = {K} exposures and G industries (the codes are < G), not {cs}")
+    elif G != 1:
+        raise ValueError(f"cov must be [D, K + 1, K + 1] with K = {K} exposures and no industry codes, not {cs}")
+    if vs != (n, D):
+        raise ValueError(f"specific_var must be [N, D] = {(n, D)}, not {vs}")
+    day0, step, fit = _risk_days(T, day0, step, None)
+    if D > fit:
+        raise ValueError(f"the {D} as-of days of cov do not fit the {T} days of the holdings from day0 = {day0} with step = {step}")
+    mats = _same_layout([_to_device(c)[0] for c in [holdings] + cols])
+    h = mats[0]
+    dev = h.device
+    b = _batch(h)
+    f64 = dict(dtype=torch.float64, device=dev)
+    expo, contrib = (torch.empty((M, D), **f64) for _ in range(2))
+    risk = torch.empty((4, D), **f64)
+    cnt = torch.empty((2, D), dtype=torch.int32, device=dev)
+    if D:
+        cv = (cov if isinstance(cov, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(cov, dtype=np.float64))))
+        cv = cv.to(**f64).contiguous()
+        sv = (specific_var if isinstance(specific_var, torch.Tensor)
+              else torch.from_numpy(np.ascontiguousarray(np.asarray(specific_var, dtype=np.float64)))).to(**f64)
+        if sv.stride(1) != 1 or (n > 1 and sv.stride(0) < D):
+            sv = sv.contiguous()
+        gp, gs = (None, 0) if ind is None else _codes_on_pitch(ind, b, dev)
+        ptrs = (C.c_void_p * max(K, 1))(*[m.data_ptr() for m in mats[1:]]) if n else None
+        _call("pq_risk_portfolio", dev, b, h, ptrs, K, gp, gs, G, cv, sv, max(sv.stride(0), D) if n > 1 else D, day0, step, D,
+              expo, contrib, risk, cnt)
+    return {"exposure": expo, "contribution": contrib, "factor_var": risk[0], "specific_var": risk[1], "total_var": risk[2],
+            "volatility": risk[3], "n_held": cnt[0], "n_uncovered": cnt[1]}
+
+
 ROLLING_REGRESS_MAX_K = 4                                      # PQ_ROLLING_REGRESS_MAX_K
 ROLLING_REGRESS_OUTPUTS = ("beta", "alpha", "resid_std", "r_squared", "resid")   # pq_factor_rolling_regress's output pointers, in order
 

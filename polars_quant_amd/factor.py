@@ -17,6 +17,9 @@ a fee on the traded value, as value curves with the backtest report's statistics
 takes, by equal, trailing-IC, trailing-ICIR or max-IR weights that only use ICs already known on the day the weight is used.
 `double_sort` (decision D-31, beyond the README) is the two-way sort that follows a factor's single sort: a control (size, another
 factor) times the factor, independent or dependent, with the cells' returns and the bucket-averaged spread along each axis.
+`risk_model` and `portfolio_risk` (decision D-33, beyond the README) consume the three series of `pure_factor_return` (decision D-32):
+the exponentially weighted covariance of the factor and industry returns and the specific variance of every symbol on the rebalance
+days, and from the two the predicted variance of a portfolio with its exposures and each factor's contribution.
 """
 from __future__ import annotations
 
@@ -360,6 +363,61 @@ class Factor:
         if specific_return:
             out["specific_return"] = r["resid"]
         return out
+
+    # ---- D-33: the risk model on pure_factor_return's three series, and the predicted risk of a portfolio from it
+    def risk_model(self, factor_returns, specific_returns=None, window=252, halflife=None, min_periods=None, start=None, step=1,
+                   unbiased=True, specific_window=None, specific_halflife=None):
+        """factor_returns: an [M, T] array, or the dict that pure_factor_return returns -- its factor_return rows are then stacked with
+        industry_return (or intercept) into the [K + G, T] block, and specific_return is taken from it where it is there and
+        specific_returns is not given.  Exponentially weighted (halflife in days; None: equal weights) over the last `window` days, on
+        the as-of days start, start + step, ... (start=None: window - 1, the first day with a full window); min_periods=None:
+        max(2, window // 2); the specific_* arguments default to the factor ones (and the specific min_periods to max(2,
+        specific_window // 2) where min_periods is not given).
+        -> {"factor_cov": [D, M, M], "specific_var": [N, D] (if specific returns were given), "n": [D, M] (int32, the days behind each
+        factor variance), "days": [D] (int64, the as-of days), "day0", "step"}.  Pairwise-complete: entry [j, l] uses the days on which
+        both series are non-null and finite (an unsolved day is NULL in every row, a day without a member in that industry's), so the
+        matrix need not be positive semi-definite.  NULL below min_periods days.
+        Look-ahead: the model of as-of day t reads the rows t - window + 1 .. t and nothing later.  pure_factor_return regresses the
+        NEXT return, so its row t, and the model "as of t", is known one day later: shift with Factor.delay where that matters."""
+        sr = specific_returns
+        if isinstance(factor_returns, dict):
+            d = factor_returns
+            rest = d["industry_return"] if "industry_return" in d else d["intercept"]
+            fr, rest = (_api._to_device(x)[0] for x in (d["factor_return"], rest))
+            factor_returns = torch.cat([fr, rest.to(fr.device)])
+            if sr is None:
+                sr = d.get("specific_return")
+        window = int(window)
+        sw = window if specific_window is None else int(specific_window)
+        shl = halflife if specific_halflife is None else specific_halflife
+        mp = max(2, window // 2) if min_periods is None else min_periods
+        smp = max(2, sw // 2) if min_periods is None else min_periods
+        w = _api.risk_weights(window, halflife)
+        ws = _api.risk_weights(sw, shl)
+        T = _api._shape(factor_returns)[-1]
+        day0 = window - 1 if start is None else start
+        if sr is not None and _api._shape(sr)[-1] != T:
+            raise ValueError(f"specific_returns must have the factor returns' {T} days, not {_api._shape(sr)}")
+        cov, n = _api.risk_factor_cov(factor_returns, w, mp, day0, step, None, unbiased, counts=True)
+        D = cov.shape[0]
+        out = {"factor_cov": cov}
+        if sr is not None:
+            out["specific_var"] = _api.risk_specific_var(sr, ws, smp, day0, step, D, unbiased)
+        out.update({"n": n, "days": int(day0) + int(step) * torch.arange(D, dtype=torch.int64, device=cov.device), "day0": int(day0),
+                    "step": int(step)})
+        return out
+
+    def portfolio_risk(self, holdings, exposures, model, industry=None):
+        """holdings [N, T] (weights or values; NULL or 0: not held), exposures the K factors of the regression (a list of [N, T] arrays
+        or one [K, N, T] array), industry its codes, model the dict of risk_model (with its specific_var) -> {"exposure",
+        "contribution": [M, D], "factor_var", "specific_var", "total_var", "volatility": [D], "n_held", "n_uncovered": [D] (int32)} on
+        the model's as-of days: total_var = X' F X + sum h^2 s^2, contribution[j] = X_j (F X)_j.  A day is NULL where nothing is held,
+        where a held symbol lacks an exposure, an industry or a specific variance (n_uncovered counts them), and where a covariance
+        that the product needs is NULL.  The covariances are pairwise-complete and need not be positive semi-definite: volatility is
+        NULL where total_var < 0.  Not annualised."""
+        if "specific_var" not in model:
+            raise ValueError("the model has no specific_var: pass specific returns to risk_model")
+        return _api.risk_portfolio(holdings, exposures, model["factor_cov"], model["specific_var"], industry, model["day0"], model["step"])
 
     def time_series_regression(self, factors, returns):
         """factors: a list of [N, T] or [T] arrays (a [T] series, e.g. a market return, is shared by every symbol) or one [K, N, T]
