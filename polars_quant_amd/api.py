@@ -596,7 +596,8 @@ def factor_portfolio(labels, price, n_groups: int, rebalance_days, weight=None, 
 
 CLEAN_WINSORIZE = {None: 0, "mad": 1, "sigma": 2, "percentile": 3}     # pq_factor_clean's winsorize codes
 CLEAN_WINSORIZE_N = {"mad": 3.0, "sigma": 3.0, "percentile": 1.0}    # the README's defaults
-MAX_INDUSTRIES = 256
+IC_MAX_GROUPS = 256                  # PQ_IC_MAX_GROUPS: the one limit on group (industry) codes, XS_MAX_GROUPS in csrc/xsec
+MAX_INDUSTRIES = IC_MAX_GROUPS       # its older name
 
 
 def _int_codes(codes, what):
@@ -918,7 +919,6 @@ def factor_orthogonalize(factors, mode: int = 0, out=None, keep_first: bool = Fa
 
 
 IC_DECAY_MAX_LAG = 256    # PQ_IC_DECAY_MAX_LAG
-IC_MAX_GROUPS = 256       # PQ_IC_MAX_GROUPS
 IC_SUMMARY_COLS = 5       # PQ_IC_SUMMARY_COLS: n_days, mean, std, t_stat, p_value
 
 

@@ -279,17 +279,16 @@ pq_status pq_factor_portfolio(pq_ctx *ctx, const pq_batch *b, const uint8_t *lab
         if (k + 1 < R && t == rebalance_days[k + 1]) k++; // day d_{k+1} itself still belongs to segment k
     }
     const size_t len = (size_t)d.len, gr = (size_t)ng * (size_t)R, gt = (size_t)ng * len;
-    const size_t o_seg = (size_t)R * 4, o_pa = xs_al(o_seg + len * 4), o_pc = o_pa + xs_al((size_t)nblk * gr * 8),
-                 o_a = o_pc + xs_al((size_t)nblk * gr * 4), o_pg = o_a + xs_al(gr * 8), o_g = o_pg + xs_al((size_t)nblk * gt * 8),
-                 o_pt = o_g + xs_al(gt * 8), o_b = o_pt + xs_al((size_t)nblk * gr * 8), total = o_b + xs_al(gr * 8);
-    PQ_TRY(pq_ws_reserve(ctx, total));
-    unsigned char *w = (unsigned char *)ctx->ws;
-    PQ_HIP_TRY(hipMemcpyAsync(w, host.data(), host.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    int32_t *days, *seg, *pc;
+    double *pa, *A, *pg, *G, *pt, *Bv;
+    PQ_TRY(xs_ws_carve(ctx, "pq_factor_portfolio", [&](XsWs &w) {
+        w.take(days, (size_t)R).take(seg, len).take(pa, nblk * gr).take(pc, nblk * gr).take(A, gr).take(pg, nblk * gt).take(G, gt);
+        w.take(pt, nblk * gr).take(Bv, gr);
+    }));
+    if (R > 0) PQ_HIP_TRY(hipMemcpyAsync(days, host.data(), (size_t)R * 4, hipMemcpyHostToDevice, ctx->stream));
+    PQ_HIP_TRY(hipMemcpyAsync(seg, host.data() + R, len * 4, hipMemcpyHostToDevice, ctx->stream));
     PQ_HIP_TRY(hipStreamSynchronize(ctx->stream)); // the table goes away with this call
-    double *pa = (double *)(w + o_pa), *A = (double *)(w + o_a), *pg = (double *)(w + o_pg), *G = (double *)(w + o_g),
-           *pt = (double *)(w + o_pt), *Bv = (double *)(w + o_b);
-    int32_t *pc = (int32_t *)(w + o_pc);
-    const PfArgs q{labels, price, weight, (const int32_t *)w, (const int32_t *)(w + o_seg), A, G, count, d, R, (int)label_lag, ng};
+    const PfArgs q{labels, price, weight, days, seg, A, G, count, d, R, (int)label_lag, ng};
     if (R > 0) {
         PF_LAUNCH_G(pf_weight_partial_kernel, pf_grid(R, nblk), q, pa, pc);
         hipLaunchKernelGGL(pf_sum_blocks_kernel, pf_grid((int64_t)gr), dim3(64), 0, ctx->stream, (const double *)pa, (const int32_t *)pc, nblk,

@@ -19,8 +19,6 @@
 
 namespace {
 
-constexpr int BD_MAX_G = 256;
-
 enum BdRank { BD_RANK = 0, BD_PCT = 1, BD_MID = 2 };
 enum BdOp { BD_RATIO = 0, BD_DIFF = 1, BD_RELDIFF = 2 };
 
@@ -127,14 +125,12 @@ __global__ __launch_bounds__(64) void bd_minmax_combine_kernel(const double *pmi
 // ---------------------------------------------------------------- weighted
 struct BdW {
     const double *f, *w;
-    const int32_t *grp;   // null = one sum per day
-    int64_t gstride;      // 0: grp is [n], else [n][gstride]
-    int32_t G;            // group codes in [0, G)
+    XsGroups grp;         // null codes = one sum per day
     Dims d;
 };
 
 __device__ __forceinline__ bool bd_w_member(const BdW &in, double x, double w, int32_t g) {
-    return xs_valid(x) && xs_valid(w) && (!in.grp || (g >= 0 && g < in.G));
+    return xs_valid(x) && xs_valid(w) && (!in.grp.codes || (g >= 0 && g < in.grp.G));   // written out: see XsGroups::has
 }
 
 enum BdWPass { BD_W_SUM, BD_W_GSUM, BD_W_WRITE };
@@ -147,11 +143,11 @@ __global__ __launch_bounds__(64) void bd_weighted_kernel(BdW in, double *ps, con
     const Dims d = in.d;
     const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (t >= d.len) return;
-    const int lane = threadIdx.x, G = in.G;
+    const int lane = threadIdx.x, G = in.grp.G;
     double *gs = (double *)bd_lds;
     if (P == BD_W_GSUM)
         for (int g = 0; g < G; g++) gs[g * 64 + lane] = 0.0;
-    const bool grouped = in.grp != nullptr;
+    const bool grouped = in.grp.codes != nullptr;
     const double Wday = (P == BD_W_WRITE && !grouped) ? W[t] : 0.0;
     const int64_t s_lo = (int64_t)blockIdx.y * XS_BLOCK, s_hi = s_lo + XS_BLOCK < d.n ? s_lo + XS_BLOCK : d.n;
     double a0 = 0.0;
@@ -164,7 +160,7 @@ __global__ __launch_bounds__(64) void bd_weighted_kernel(BdW in, double *ps, con
             const int64_t s = s0 + k < s_hi ? s0 + k : s_hi - 1, o = s * d.stride + t;
             x[k] = in.f[o];
             w[k] = in.w[o];
-            g[k] = grouped ? in.grp[in.gstride ? s * in.gstride + t : s] : 0;
+            g[k] = grouped ? in.grp.at(s, t) : 0;
         }
 #pragma unroll
         for (int k = 0; k < B; k++) {
@@ -230,16 +226,15 @@ pq_status pq_factor_rank(pq_ctx *ctx, const pq_batch *b, const double *factor, i
     XsDaySort plan;
     PQ_TRY(xs_day_sort_plan(ctx, d, "pq_factor_rank", &plan));
     // workspace: keys, then values (f64, day-major) | n per day (i32) | wide: sorted keys (f64), offsets (u32), rocPRIM temp
-    const size_t o_cnt = xs_al(cells * 8), o_srt = o_cnt + xs_al(len * 4);
-    PQ_TRY(pq_ws_reserve(ctx, o_srt + plan.bytes));
-    unsigned char *ws = (unsigned char *)ctx->ws;
-    double *key = (double *)ws;
-    int32_t *nv = (int32_t *)(ws + o_cnt);
+    double *key;
+    int32_t *nv;
+    unsigned char *tail;
+    PQ_TRY(xs_ws_carve(ctx, "pq_factor_rank", [&](XsWs &w) { w.take(key, cells).take(nv, len).take(tail, plan.bytes); }));
     hipStream_t st = ctx->stream;
     const dim3 gt((unsigned)((d.len + 31) / 32), (unsigned)((d.n + 31) / 32));
     PQ_HIP_TRY(hipMemsetAsync(nv, 0, len * 4, st));
     hipLaunchKernelGGL((xs_prep_kernel<1, BdKey>), gt, dim3(256), 0, st, BdKey{factor}, d, key, (int64_t)0, nv);
-    PQ_TRY(xs_sort_lookup(ctx, d, plan, ws + o_srt, BdRankOp{key, mode, descending}, nv));
+    PQ_TRY(xs_sort_lookup(ctx, d, plan, tail, BdRankOp{key, mode, descending}, nv));
     hipLaunchKernelGGL(bd_transpose_kernel, gt, dim3(256), 0, st, (const double *)key, d.n, d.len, out, d.stride);
     PQ_HIP_TRY(hipGetLastError());
     return PQ_OK;
@@ -255,10 +250,8 @@ pq_status pq_factor_minmax(pq_ctx *ctx, const pq_batch *b, const double *factor,
     const size_t len = (size_t)d.len;
     const int64_t nblk = xs_nblk(d.n);
     // workspace: block partials min, max [nblk][len] | per-day min, max [len]
-    const size_t part = xs_al((size_t)nblk * len * 8), row = xs_al(len * 8);
-    PQ_TRY(pq_ws_reserve(ctx, 2 * part + 2 * row));
-    unsigned char *ws = (unsigned char *)ctx->ws;
-    double *pmin = (double *)ws, *pmax = (double *)(ws + part), *dmin = (double *)(ws + 2 * part), *dmax = (double *)(ws + 2 * part + row);
+    double *pmin, *pmax, *dmin, *dmax;
+    PQ_TRY(xs_ws_carve(ctx, "pq_factor_minmax", [&](XsWs &w) { w.take(pmin, nblk * len).take(pmax, nblk * len).take(dmin, len).take(dmax, len); }));
     const dim3 gp((unsigned)((d.len + 63) / 64), (unsigned)nblk), gd((unsigned)((d.len + 63) / 64));
     hipStream_t st = ctx->stream;
     hipLaunchKernelGGL(bd_minmax_kernel<false>, gp, dim3(64), 0, st, factor, d, pmin, pmax, (const double *)nullptr, (const double *)nullptr,
@@ -273,8 +266,8 @@ pq_status pq_factor_minmax(pq_ctx *ctx, const pq_batch *b, const double *factor,
 pq_status pq_factor_weighted(pq_ctx *ctx, const pq_batch *b, const double *factor, const double *weight, const int32_t *group,
                              int64_t group_stride, int32_t n_groups, double *out) {
     PQ_TRY(pq_check(ctx, b));
-    PQ_REQUIRE(!group || (n_groups >= 1 && n_groups <= BD_MAX_G), "pq_factor_weighted: n_groups must be in [1, 256]");
-    PQ_REQUIRE(!group || group_stride == 0 || group_stride >= b->len, "pq_factor_weighted: group_stride must be 0 ([n_series] codes) or >= len");
+    XsGroups grp;
+    PQ_TRY(xs_groups_arg("pq_factor_weighted", b, group, group_stride, n_groups, XsGroupsPolicy{XS_G_WITH_CODES, "n_groups", "group"}, &grp));
     PQ_REQUIRE(b->n_series == 0 || b->len == 0 || (factor && weight && out), "pq_factor_weighted: null pointer");
     if (ctx->rec) { pq_set_error("pq_factor_weighted cannot be recorded into a suite"); return PQ_ERR_UNSUPPORTED; }
     PQ_NO_RAGGED(b, "pq_factor_weighted (a cross-section needs every symbol on every day)");
@@ -283,12 +276,10 @@ pq_status pq_factor_weighted(pq_ctx *ctx, const pq_batch *b, const double *facto
     const size_t len = (size_t)d.len;
     const int G = group ? n_groups : 1;
     const int64_t nblk = xs_nblk(d.n);
-    const BdW in{factor, weight, group, group ? group_stride : 0, group ? n_groups : 0, d};
+    const BdW in{factor, weight, grp, d};
     // workspace: block partials [nblk][G][len] | W [G][len]
-    const size_t part = xs_al((size_t)nblk * (size_t)G * len * 8);
-    PQ_TRY(pq_ws_reserve(ctx, part + xs_al((size_t)G * len * 8)));
-    unsigned char *ws = (unsigned char *)ctx->ws;
-    double *ps = (double *)ws, *W = (double *)(ws + part);
+    double *ps, *W;
+    PQ_TRY(xs_ws_carve(ctx, "pq_factor_weighted", [&](XsWs &w) { w.take(ps, (size_t)nblk * G * len).take(W, G * len); }));
     const dim3 gp((unsigned)((d.len + 63) / 64), (unsigned)nblk), gc((unsigned)((d.len + 63) / 64), (unsigned)G);
     hipStream_t st = ctx->stream;
     if (group) {

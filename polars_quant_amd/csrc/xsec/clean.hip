@@ -17,8 +17,6 @@
 
 namespace {
 
-constexpr int CL_MAX_G = 256;
-
 enum ClWinsor { CL_WIN_NONE = 0, CL_WIN_MAD = 1, CL_WIN_SIGMA = 2, CL_WIN_PCT = 3 };
 
 // pass kinds: what a (day, block) thread sums
@@ -36,8 +34,7 @@ enum ClPass {
 
 struct ClIn {
     const double *f, *z;    // z: null = size neutralization off
-    const int32_t *ind;     // null = industry neutralization off
-    int32_t G;              // industry codes in [0, G)
+    XsGroups ind;           // the industry codes, on the batch's stride; null codes = industry neutralization off
     int32_t standardize;
     Dims d;
 };
@@ -53,7 +50,7 @@ struct ClDay {
 };
 
 __device__ __forceinline__ bool cl_member(const ClIn &in, double x, double z, int32_t g) {
-    return xs_valid(x) && (!in.z || xs_valid(z)) && (!in.ind || (g >= 0 && g < in.G));
+    return xs_valid(x) && (!in.z || xs_valid(z)) && (!in.ind.codes || (g >= 0 && g < in.ind.G));   // written out: see XsGroups::has
 }
 
 // clip by comparisons: a value equal to a bound keeps its own bits (so -0 / +0 never depend on which bound is hit)
@@ -67,7 +64,7 @@ struct ClKey {
     ClIn in;
     __device__ void operator()(int64_t o, double (&k)[1]) const {
         const double x = in.f[o];
-        if (cl_member(in, x, in.z ? in.z[o] : 0.0, in.ind ? in.ind[o] : 0)) k[0] = x == 0.0 ? 0.0 : x;
+        if (cl_member(in, x, in.z ? in.z[o] : 0.0, in.ind.codes ? in.ind.at_cell(o) : 0)) k[0] = x == 0.0 ? 0.0 : x;
     }
 };
 
@@ -156,7 +153,7 @@ __global__ __launch_bounds__(64) void cl_pass_kernel(ClIn in, ClDay day, double 
     const Dims d = in.d;
     const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (t >= d.len) return;
-    const int lane = threadIdx.x, G = in.G;
+    const int lane = threadIdx.x, G = in.ind.G;
     double *gs = (double *)cl_lds;
     uint16_t *gc = (uint16_t *)(cl_lds + (size_t)G * 64 * 8);
     if (P == CL_IND)
@@ -164,7 +161,7 @@ __global__ __launch_bounds__(64) void cl_pass_kernel(ClIn in, ClDay day, double 
     const int nv = day.n[t];
     const double lo = day.lo[t], hi = day.hi[t];
     const double m0 = P == CL_VAR0 ? day.m0[t] : 0.0;
-    const bool cap = in.z != nullptr, ind = in.ind != nullptr, stdz = in.standardize != 0;
+    const bool cap = in.z != nullptr, ind = in.ind.codes != nullptr, stdz = in.standardize != 0;
     const double xbar = cap && P >= CL_CAP2 ? day.xbar[t] : 0.0, zbar = cap && P >= CL_CAP2 ? day.zbar[t] : 0.0,
                  beta = cap && P >= CL_IND ? day.beta[t] : 0.0;
     const double smean = P >= CL_STD2 ? day.smean[t] : 0.0, sstd = P == CL_WRITE && stdz ? day.sstd[t] : 1.0;
@@ -181,7 +178,7 @@ __global__ __launch_bounds__(64) void cl_pass_kernel(ClIn in, ClDay day, double 
             const int64_t o = (s0 + k < s_hi ? s0 + k : s_hi - 1) * d.stride + t;
             x[k] = in.f[o];
             z[k] = cap ? in.z[o] : 0.0;
-            g[k] = ind ? in.ind[o] : 0;
+            g[k] = ind ? in.ind.at_cell(o) : 0;
         }
 #pragma unroll
         for (int k = 0; k < B; k++) {
@@ -292,15 +289,16 @@ pq_status pq_factor_clean(pq_ctx *ctx, const pq_batch *b, const double *factor, 
         w.qlo = p;
         w.qhi = 1.0 - p;
     }
-    PQ_REQUIRE(!industry || (n_industries >= 1 && n_industries <= CL_MAX_G), "pq_factor_clean: n_industries must be in [1, 256]");
+    XsGroups ind;   // no stride parameter: the codes lie on the batch's
+    PQ_TRY(xs_groups_arg("pq_factor_clean", b, industry, b->stride, n_industries, XsGroupsPolicy{XS_G_WITH_CODES, "n_industries", "industry"}, &ind));
     PQ_REQUIRE(standardize == 0 || standardize == 1, "pq_factor_clean: standardize must be 0 or 1");
     PQ_REQUIRE((b->n_series == 0 || factor) && (b->n_series == 0 || b->len == 0 || out), "pq_factor_clean: null pointer");
     if (ctx->rec) { pq_set_error("pq_factor_clean cannot be recorded into a suite"); return PQ_ERR_UNSUPPORTED; }
     PQ_NO_RAGGED(b, "pq_factor_clean (a cross-section needs every symbol on every day)");
     if (b->len == 0 || b->n_series == 0) return PQ_OK;
     const Dims d = dims_of(b);
-    const int G = industry ? n_industries : 0;
-    const ClIn in{factor, cap_z, industry, G, standardize, d};
+    const int G = ind.G;
+    const ClIn in{factor, cap_z, ind, standardize, d};
     const size_t cells = (size_t)d.len * (size_t)d.n, len = (size_t)d.len;
     const int64_t nblk = xs_nblk(d.n);
     const bool sorted = winsorize == CL_WIN_MAD || winsorize == CL_WIN_PCT;
@@ -309,21 +307,16 @@ pq_status pq_factor_clean(pq_ctx *ctx, const pq_batch *b, const double *factor, 
     // workspace: per-day n (i32) and 8 parameter rows (f64) | industry means [G][len] | block partials: 2 sums (f64) + count (i32) |
     // industry partials: sums (f64) + counts (u16) [nblk][G][len] | sorted modes: keys day-major (f64) | wide: sorted keys, offsets, rocPRIM temp
     const size_t part = (size_t)nblk * len, gpart = part * (size_t)G;
-    const size_t o_par = xs_al(len * 4), o_gm = o_par + 8 * xs_al(len * 8), o_ps = o_gm + xs_al((size_t)G * len * 8),
-                 o_pc = o_ps + 2 * xs_al(part * 8), o_gs = o_pc + xs_al(part * 4), o_gc = o_gs + xs_al(gpart * 8),
-                 o_key = o_gc + xs_al(gpart * 2), o_srt = o_key + (sorted ? xs_al(cells * 8) : 0);
-    PQ_TRY(pq_ws_reserve(ctx, o_srt + plan.bytes));
-    unsigned char *ws = (unsigned char *)ctx->ws;
     ClDay day;
-    day.n = (int32_t *)ws;
-    double *par[8];
-    for (int k = 0; k < 8; k++) par[k] = (double *)(ws + o_par + k * xs_al(len * 8));
-    day.lo = par[0]; day.hi = par[1]; day.m0 = par[2]; day.xbar = par[3]; day.zbar = par[4]; day.beta = par[5]; day.smean = par[6];
-    day.sstd = par[7];
-    day.gmean = (double *)(ws + o_gm);
-    double *ps0 = (double *)(ws + o_ps), *ps1 = (double *)(ws + o_ps + xs_al(part * 8)), *gs = (double *)(ws + o_gs);
-    int32_t *pc = (int32_t *)(ws + o_pc);
-    uint16_t *gc = (uint16_t *)(ws + o_gc);
+    double *ps0, *ps1, *gs, *key;
+    int32_t *pc;
+    uint16_t *gc;
+    unsigned char *tail;
+    PQ_TRY(xs_ws_carve(ctx, "pq_factor_clean", [&](XsWs &w) {
+        w.take(day.n, len).take(day.lo, len).take(day.hi, len).take(day.m0, len).take(day.xbar, len).take(day.zbar, len);
+        w.take(day.beta, len).take(day.smean, len).take(day.sstd, len).take(day.gmean, (size_t)G * len);
+        w.take(ps0, part).take(ps1, part).take(pc, part).take(gs, gpart).take(gc, gpart).take(key, sorted ? cells : 0).take(tail, plan.bytes);
+    }));
     const dim3 gp((unsigned)((d.len + 63) / 64), (unsigned)nblk), gd((unsigned)((d.len + 63) / 64)), g256((unsigned)((d.len + 255) / 256));
     const double wn = winsorize == CL_WIN_SIGMA ? winsorize_n : 0.0;
     hipStream_t st = ctx->stream;
@@ -342,7 +335,6 @@ pq_status pq_factor_clean(pq_ctx *ctx, const pq_batch *b, const double *factor, 
         CL_PASS(CL_SUM0);
         CL_PASS(CL_VAR0);
     } else if (sorted) {
-        double *key = (double *)(ws + o_key);
         PQ_HIP_TRY(hipMemsetAsync(day.n, 0, len * 4, st));
         hipLaunchKernelGGL((xs_prep_kernel<1, ClKey>), dim3((unsigned)((d.len + 31) / 32), (unsigned)((d.n + 31) / 32)), dim3(256), 0, st,
                            ClKey{in}, d, key, (int64_t)0, day.n);
@@ -352,7 +344,7 @@ pq_status pq_factor_clean(pq_ctx *ctx, const pq_batch *b, const double *factor, 
             hipLaunchKernelGGL(cl_bounds_lds_kernel, dim3((unsigned)d.len), dim3(L.nthr), L.bytes, st, (const double *)key, d.n, L.P, w, day);
         } else {
             const double *srt;
-            PQ_TRY(xs_day_sort_wide(ctx, d, plan, ws + o_srt, key, &srt));
+            PQ_TRY(xs_day_sort_wide(ctx, d, plan, tail, key, &srt));
             hipLaunchKernelGGL(cl_bounds_sorted_kernel, gd, dim3(64), 0, st, srt, d.n, d.len, w, day);
         }
     }

@@ -127,16 +127,14 @@ pq_status ds_run(pq_ctx *ctx, const pq_batch *b, const double *control, const do
     const int C = rule.qa * rule.qb;
     XsDaySort plan;
     PQ_TRY(xs_day_sort_plan(ctx, d, "factor double sort", &plan));
-    const XsCellsWs ws = xs_cells_layout(d, 2, C, labels != nullptr, plan); // key rows: A | B, then the composite keys
-    PQ_TRY(pq_ws_reserve(ctx, ws.bytes));
-    unsigned char *w = (unsigned char *)ctx->ws;
-    double *keyA = (double *)w, *keyB = keyA + ws.key_pitch;
-    int32_t *nv = (int32_t *)(w + ws.o_nv);
+    XsCellsWs ws; // key rows: A | B, then the composite keys
+    PQ_TRY(xs_ws_carve(ctx, "factor double sort", [&](XsWs &w) { ws = xs_cells_layout(w, d, 2, C, labels != nullptr, plan); }));
+    double *keyA = ws.key, *keyB = keyA + ws.key_pitch;
     if (d.n > 0) {
-        PQ_HIP_TRY(hipMemsetAsync(nv, 0, (size_t)d.len * 4, ctx->stream));
+        PQ_HIP_TRY(hipMemsetAsync(ws.nv, 0, (size_t)d.len * 4, ctx->stream));
         hipLaunchKernelGGL((xs_prep_kernel<2, DsKeys>), dim3((unsigned)((d.len + 31) / 32), (unsigned)((d.n + 31) / 32)), dim3(256), 0,
-                           ctx->stream, DsKeys{control, factor, fwd_return}, d, keyA, (int64_t)ws.key_pitch, nv);
-        PQ_TRY(xs_sort_lookup(ctx, d, plan, w + ws.o_tail, DsLabelOp{keyA, keyB, rule, w + ws.o_ldm}, nv));
+                           ctx->stream, DsKeys{control, factor, fwd_return}, d, keyA, (int64_t)ws.key_pitch, ws.nv);
+        PQ_TRY(xs_sort_lookup(ctx, d, plan, ws.tail, DsLabelOp{keyA, keyB, rule, ws.ldm}, ws.nv));
     }
     PQ_TRY(xs_cells_stats(ctx, d, ws, C, labels, fwd_return, mean, count, tov));
     hipLaunchKernelGGL(ds_spread_kernel, dim3((unsigned)((d.len + 63) / 64)), dim3(64), 0, ctx->stream, (const double *)mean, d.len,

@@ -252,17 +252,16 @@ struct LnOut {
     double *pred, *resid;
 };
 
-// workspace: n (i64), ok (i32) | 3 (K + 1) + 1 + LN_MAX_NA f64: mean, b, v, syy, sums | tile partials [NA][ntile] (f64)
+// workspace: n (i64) | ok (i32) | 3 (K + 1) + 1 + LN_MAX_NA f64: mean, b, v, syy, sums | tile partials [NA][ntile] (f64)
 template <int K, bool FLAT, bool OUT>
 pq_status ln_run(pq_ctx *ctx, const LnIn &in, const LnOut &out) {
     const int64_t ntile = in.rows > LN_TILE ? (in.rows + LN_TILE - 1) / LN_TILE : 1;   // at least one: an empty column still gets its zero sums
     constexpr int NS = 3 * (K + 1) + 1 + LN_MAX_NA;
     static_assert(LnNa<K>::P1 <= LnNa<K>::P2 && LnNa<K>::P3 <= LnNa<K>::P2, "every pass's partials fit the carve of pass 2");
-    const size_t o_sc = xs_al(16), o_ps = o_sc + xs_al((size_t)NS * 8), total = o_ps + xs_al((size_t)ntile * LnNa<K>::P2 * 8);
-    PQ_TRY(pq_ws_reserve(ctx, total));
-    unsigned char *ws = (unsigned char *)ctx->ws;
-    double *sc = (double *)(ws + o_sc), *ps = (double *)(ws + o_ps);
-    const LnState st{(int64_t *)ws, (int32_t *)(ws + 8), sc, sc + (K + 1), sc + 2 * (K + 1), sc + 3 * (K + 1), sc + 3 * (K + 1) + 1};
+    LnState st;
+    double *ps;
+    PQ_TRY(xs_ws_carve(ctx, "pq_linear", [&](XsWs &w) { w.take(st.n, 1).take(st.ok, 1).take(st.mean, NS).take(ps, (size_t)ntile * LnNa<K>::P2); }));
+    st.b = st.mean + (K + 1); st.v = st.b + (K + 1); st.syy = st.v + (K + 1); st.sums = st.syy + 1;
     const dim3 gp((unsigned)ntile), blk(LN_THREADS);
     hipStream_t sm = ctx->stream;
     hipLaunchKernelGGL((ln_pass_kernel<K, LN_P1, FLAT, false>), gp, blk, 0, sm, in, st, ps, ntile, (double *)nullptr, (double *)nullptr);

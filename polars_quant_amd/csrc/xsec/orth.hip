@@ -171,7 +171,7 @@ pq_status or_run(pq_ctx *ctx, const OrIn &in) {
     const int64_t units = d.len;
     const int64_t nblk = xs_nblk(d.n);
     XoWs w;
-    PQ_TRY(xo_workspace(ctx, units, nblk, K, K + OrNa<K, NEUT>::NB, OrNa<K, NEUT>::P2, &w));   // own rows: b [NB]
+    PQ_TRY(xo_workspace(ctx, "factor orthogonalization", units, nblk, K, K + OrNa<K, NEUT>::NB, OrNa<K, NEUT>::P2, &w));   // own rows: b [NB]
     const OrDay day{w.n, w.flag, w.mean, w.own};
     double *ps = w.ps;
     int32_t *pc = w.pcnt;

@@ -183,7 +183,7 @@ pq_status rg_run(pq_ctx *ctx, const RgIn &in, const RgOut &out) {
     const int64_t units = TS ? d.n : d.len, span = TS ? d.len : d.n;
     const int64_t nblk = xs_nblk(span);
     XoWs w;
-    PQ_TRY(xo_workspace(ctx, units, nblk, K + 1, 3 * (K + 1) + 1, RgNa<K>::P2, &w));   // own rows: b, v [K + 1] and srr
+    PQ_TRY(xo_workspace(ctx, "factor regression", units, nblk, K + 1, 3 * (K + 1) + 1, RgNa<K>::P2, &w));   // own rows: b, v [K + 1] and srr
     const RgUnit un{w.n, w.flag, w.mean, w.own, w.own + (K + 1) * w.row, w.own + 2 * (K + 1) * w.row};
     double *ps = w.ps;
     int32_t *pc = w.pcnt;

@@ -31,8 +31,7 @@ namespace {
 
 constexpr int RK_MAX_SERIES = PQ_RISK_MAX_SERIES;
 constexpr int RK_MAX_K = PQ_REGRESS_MAX_K;
-constexpr int RK_MAX_G = PQ_IC_MAX_GROUPS;
-static_assert(RK_MAX_SERIES == RK_MAX_K + RK_MAX_G, "the rows of D-32's coef block");
+static_assert(RK_MAX_SERIES == RK_MAX_K + XS_MAX_GROUPS, "the rows of D-32's coef block");
 
 constexpr int RK_LCHUNK = 8;                                    // columns l per workgroup of the covariance: column j is restaged once per 8
 constexpr int RK_STAGE = 2048;                                  // staged entries per column at a step > 1 (16 KiB), XW_STAGE at most at step 1
@@ -143,9 +142,7 @@ __global__ __launch_bounds__(XW_TILE) void rk_cov_kernel(const double *f, Dims d
 struct RkPf {
     const double *h, *x[RK_MAX_K];
     int32_t K;
-    const int32_t *g;      // null: every symbol in group 0 (G = 1)
-    int64_t gstride;       // 0: g is [n_series]
-    int32_t G;
+    XsGroups grp;          // null codes: every symbol in group 0 (G = 1)
     const double *sv;      // [n_series][sv_stride], by as-of day
     int64_t sv_stride;
     Dims d;
@@ -161,7 +158,7 @@ __global__ __launch_bounds__(64) void rk_pf_pass1_kernel(RkPf in, double *ps, in
     const int lane = threadIdx.x;
     const int64_t D = in.a.count, dd = (int64_t)blockIdx.x * 64 + lane;
     if (dd >= D) return;
-    const int K = in.K, G = in.G, NQ = K + G + 1;
+    const int K = in.K, G = in.grp.G, NQ = K + G + 1;
     for (int q = 0; q < NQ; q++) rk_acc[q * 64 + lane] = 0.0;
     const int64_t t = in.a.day0 + dd * in.a.step;
     const int64_t s_lo = (int64_t)blockIdx.y * XS_BLOCK, s_hi = s_lo + XS_BLOCK < in.d.n ? s_lo + XS_BLOCK : in.d.n;
@@ -169,13 +166,13 @@ __global__ __launch_bounds__(64) void rk_pf_pass1_kernel(RkPf in, double *ps, in
     for (int64_t s = s_lo; s < s_hi; s++) {
         const int64_t o = s * in.d.stride + t;
         const double h = in.h[o], s2 = in.sv[s * in.sv_stride + dd];
-        const int32_t g = in.g ? in.g[in.gstride ? s * in.gstride + t : s] : 0;
+        const int32_t g = in.grp.codes ? in.grp.codes[in.grp.stride ? s * in.grp.stride + t : s] : 0;   // written out, as the test below
         double x[RK_MAX_K];
 #pragma unroll
         for (int j = 0; j < RK_MAX_K; j++) x[j] = j < K ? in.x[j][o] : 0.0;
         if (!(xs_valid(h) && h != 0.0)) continue;
         nh++;
-        bool covered = s2 >= 0.0 && g >= 0 && g < G;            // a NULL (or NaN) variance fails the compare
+        bool covered = s2 >= 0.0 && g >= 0 && g < G;            // a NULL (or NaN) variance fails the compare; g: see XsGroups
 #pragma unroll
         for (int j = 0; j < RK_MAX_K; j++) covered = covered && xs_valid(x[j]);
         if (!covered) { nu++; continue; }
@@ -335,15 +332,11 @@ pq_status pq_risk_portfolio(pq_ctx *ctx, const pq_batch *b, const double *holdin
     const char *what = "pq_risk_portfolio";
     PQ_TRY(pq_check(ctx, b));
     if (k < 0 || k > RK_MAX_K) { pq_set_error("%s: k must be in [0, 8]", what); return PQ_ERR_ARG; }
-    if (n_groups < 1 || n_groups > RK_MAX_G) { pq_set_error("%s: n_groups must be in [1, 256]", what); return PQ_ERR_ARG; }
-    if (!industry && n_groups != 1) { pq_set_error("%s: n_groups must be 1 without industry codes", what); return PQ_ERR_ARG; }
+    RkPf in{};
+    PQ_TRY(xs_groups_arg(what, b, industry, group_stride, n_groups, XsGroupsPolicy{XS_G_ALWAYS, "n_groups", "industry"}, &in.grp));
     if (ctx->rec) { pq_set_error("%s cannot be recorded into a suite", what); return PQ_ERR_UNSUPPORTED; }
     if (b->offsets) { pq_set_error("%s: ragged batches are not supported", what); return PQ_ERR_UNSUPPORTED; }
-    if (industry && group_stride != 0 && group_stride < b->len) {
-        pq_set_error("%s: group_stride must be 0 ([n_series] codes) or >= len", what);
-        return PQ_ERR_ARG;
-    }
-    RkPf in{};
+    PQ_TRY(xs_groups_stride(what, b, industry != nullptr, group_stride));
     PQ_TRY(rk_days(what, b->len, day0, step, count, &in.a));
     if (sv_stride < count) { pq_set_error("%s: sv_stride must be >= count", what); return PQ_ERR_ARG; }
     if (count == 0) return PQ_OK;
@@ -355,21 +348,17 @@ pq_status pq_risk_portfolio(pq_ctx *ctx, const pq_batch *b, const double *holdin
     }
     in.h = holdings;
     in.K = k;
-    in.g = industry;
-    in.gstride = industry ? group_stride : 0;
-    in.G = n_groups;
     in.sv = specific_var;
     in.sv_stride = sv_stride;
     in.d = dims_of(b);
     const int M = k + n_groups, NQ = M + 1;
     const int64_t D = count, nblk = xs_nblk(in.d.n);
     // workspace: block partials ps [nblk][NQ][D] (f64) | X [NQ][D] | cw [M][D] | block counts pc [nblk][2][D] (i32)
-    const size_t o_x = xs_al((size_t)nblk * NQ * D * 8), o_cw = o_x + xs_al((size_t)NQ * D * 8), o_pc = o_cw + xs_al((size_t)M * D * 8),
-                 total = o_pc + xs_al((size_t)nblk * 2 * D * 4);
-    PQ_TRY(pq_ws_reserve(ctx, total));
-    unsigned char *ws = (unsigned char *)ctx->ws;
-    double *ps = (double *)ws, *X = (double *)(ws + o_x), *cw = (double *)(ws + o_cw);
-    int32_t *pc = (int32_t *)(ws + o_pc);
+    double *ps, *X, *cw;
+    int32_t *pc;
+    PQ_TRY(xs_ws_carve(ctx, what, [&](XsWs &w) {
+        w.take(ps, (size_t)nblk * NQ * D).take(X, (size_t)NQ * D).take(cw, (size_t)M * D).take(pc, (size_t)nblk * 2 * D);
+    }));
     const dim3 gd((unsigned)((D + 63) / 64)), gp(gd.x, (unsigned)nblk), gq(gd.x, (unsigned)NQ), gm(gd.x, (unsigned)M);
     const size_t lds = (size_t)NQ * 64 * 8;                     // at most 265 rows: 132.5 KiB of the CU's 160
     hipStream_t st = ctx->stream;

@@ -33,10 +33,9 @@ __device__ __forceinline__ bool rb_valid(double a, double b) { return xs_valid(a
 
 struct RbIn {
     const double *x, *y;   // factor, forward return
-    const int32_t *code;   // sub-group codes: code[s * cstride + t], or code[s] when cstride == 0
-    int64_t cstride;
+    XsGroups grp;          // sub-group codes (decay: none)
     Dims d;
-    int V;                 // views: lags or groups
+    int V;                 // views: lags or groups (= grp.G)
 };
 
 // ---------------------------------------------------------------- Pearson
@@ -96,8 +95,7 @@ __global__ __launch_bounds__(64) void rb_decay_partial_kernel(RbIn in, const dou
 template <int PASS>
 __global__ __launch_bounds__(64) void rb_group_partial_kernel(RbIn in, const double *means, double *part) {
     const double *x = in.x, *y = in.y;
-    const int32_t *code = in.code;
-    const int64_t cstride = in.cstride;
+    const XsGroups grp = in.grp;
     const Dims d = in.d;
     const int G = in.V;
     __shared__ double acc[3][RB_GT][64];
@@ -116,7 +114,7 @@ __global__ __launch_bounds__(64) void rb_group_partial_kernel(RbIn in, const dou
         for (int k = 0; k < B; k++) {
             const int64_t s = s0 + k < s_hi ? s0 + k : s_hi - 1;
             a[k] = x[s * d.stride + t]; b[k] = y[s * d.stride + t];
-            c[k] = code[cstride ? s * cstride + t : s];
+            c[k] = grp.at(s, t);
         }
 #pragma unroll
         for (int k = 0; k < B; k++) {
@@ -289,7 +287,7 @@ __global__ __launch_bounds__(RB_THR) void rb_decay_rank_kernel(const int32_t *A,
 
 // sub-group, one workgroup per day t: per side, the composite keys g * 2^14 + a_s of the members (valid pair, code in [0, G)) sorted in
 // LDS; 2 x the rank within the group = 2 (lower - group start) + (upper - lower) + 1.  The factor side's ranks wait in R2 (day-major,
-// read back by the thread that wrote them); the group sums are LDS atomics on exact integers.
+// read back by the thread that wrote them); the group sums are LDS atomics on exact integers.  (code, cstride, G), not XsGroups: see there.
 __global__ __launch_bounds__(RB_THR) void rb_group_rank_kernel(const int32_t *A, const int32_t *code, int64_t cstride, Dims d, int G, int P,
                                                                int32_t *R2, double *ic, int32_t *n_valid) {
     extern __shared__ __align__(16) unsigned char rb_lds[];
@@ -383,9 +381,8 @@ pq_status rb_pearson(pq_ctx *ctx, const RbIn &in, int tile, double *ic, int32_t 
     const int V = in.V;
     const int64_t nblk = xs_nblk(d.n);
     const dim3 gp((unsigned)((d.len + 63) / 64), (unsigned)nblk, (unsigned)((V + tile - 1) / tile));
-    const size_t part = (size_t)V * nblk * d.len * 24, mean = (size_t)V * d.len * 24;
-    PQ_TRY(pq_ws_reserve(ctx, xs_al(part) + mean));
-    double *ps = (double *)ctx->ws, *ms = (double *)((unsigned char *)ctx->ws + xs_al(part));
+    double *ps, *ms;
+    PQ_TRY(xs_ws_carve(ctx, GROUP ? "pq_ic_subgroup" : "pq_ic_decay", [&](XsWs &w) { w.take(ps, (size_t)V * nblk * d.len * 3).take(ms, (size_t)V * d.len * 3); }));
     const dim3 gc((unsigned)((d.len + 63) / 64), (unsigned)V);
     hipStream_t st = ctx->stream;
     if (GROUP) hipLaunchKernelGGL(rb_group_partial_kernel<0>, gp, dim3(64), 0, st, in, (const double *)ms, ps);
@@ -398,12 +395,9 @@ pq_status rb_pearson(pq_ctx *ctx, const RbIn &in, int tile, double *ic, int32_t 
     return PQ_OK;
 }
 
-// A (tie-run starts of both sides, [2][len][n] int32) at the start of the workspace, followed by `extra` bytes
-pq_status rb_tie_starts(pq_ctx *ctx, const Dims &d, const double *factor, const double *ret, size_t extra, int32_t *&A, unsigned char *&rest) {
-    const size_t a_bytes = xs_al((size_t)2 * d.len * d.n * 4);
-    PQ_TRY(pq_ws_reserve(ctx, a_bytes + extra));
-    A = (int32_t *)ctx->ws;
-    rest = (unsigned char *)ctx->ws + a_bytes;
+// workspace: A (tie-run starts of both sides, [2][len][n] int32) | `extra` further int32 (R2)
+pq_status rb_tie_starts(pq_ctx *ctx, const Dims &d, const double *factor, const double *ret, size_t extra, int32_t *&A, int32_t *&rest) {
+    PQ_TRY(xs_ws_carve(ctx, extra ? "pq_ic_subgroup" : "pq_ic_decay", [&](XsWs &w) { w.take(A, (size_t)2 * d.len * d.n).take(rest, extra); }));
     const XsLds sh = xs_lds_shape(d.n);
     PQ_HIP_TRY(hipFuncSetAttribute((const void *)rb_tie_start_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh.bytes));
     hipLaunchKernelGGL(rb_tie_start_kernel, dim3((unsigned)d.len, 2), dim3(sh.nthr), sh.bytes, ctx->stream, factor, ret, d, sh.P, A);
@@ -428,10 +422,9 @@ pq_status pq_ic_decay(pq_ctx *ctx, const pq_batch *b, const double *factor, cons
     const int L = max_lag;
     if (d.len > 0) {
         if (method == 0 || d.n == 0) {
-            PQ_TRY(rb_pearson<false>(ctx, RbIn{factor, fwd_return, nullptr, 0, d, L}, RB_LT, ic, n_valid));
+            PQ_TRY(rb_pearson<false>(ctx, RbIn{factor, fwd_return, XsGroups{nullptr, 0, 0}, d, L}, RB_LT, ic, n_valid));
         } else if (d.n <= XS_LDS_MAX) {
-            int32_t *A;
-            unsigned char *rest;
+            int32_t *A, *rest;
             PQ_TRY(rb_tie_starts(ctx, d, factor, fwd_return, 0, A, rest));
             const size_t lds = (size_t)2 * d.n * 4;
             PQ_HIP_TRY(hipFuncSetAttribute((const void *)rb_decay_rank_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -457,20 +450,20 @@ pq_status pq_ic_subgroup(pq_ctx *ctx, const pq_batch *b, const double *factor, c
                          int64_t group_stride, int32_t n_groups, int32_t method, double *ic, int32_t *n_valid, double *summary) {
     PQ_TRY(rb_args(ctx, b, "pq_ic_subgroup", factor, fwd_return, method, n_groups, ic, n_valid, summary));
     PQ_REQUIRE(b->len == 0 || b->n_series == 0 || group, "pq_ic_subgroup: null group pointer");
-    PQ_REQUIRE(group_stride == 0 || group_stride >= b->len, "pq_ic_subgroup: group_stride must be 0 ([n_series] codes) or >= len");
+    XsGroups grp;   // the count is one of rb_args' views
+    PQ_TRY(xs_groups_arg("pq_ic_subgroup", b, group, group_stride, n_groups, XsGroupsPolicy{XS_G_REQUIRED, "n_groups", "group"}, &grp));
     const Dims d = dims_of(b);
     const int G = n_groups;
     if (d.len > 0) {
         if (method == 0 || d.n == 0) {
-            PQ_TRY(rb_pearson<true>(ctx, RbIn{factor, fwd_return, group, group_stride, d, G}, RB_GT, ic, n_valid));
+            PQ_TRY(rb_pearson<true>(ctx, RbIn{factor, fwd_return, grp, d, G}, RB_GT, ic, n_valid));
         } else if (d.n <= XS_LDS_MAX) {
-            int32_t *A;
-            unsigned char *rest;
-            PQ_TRY(rb_tie_starts(ctx, d, factor, fwd_return, (size_t)d.len * d.n * 4, A, rest));
+            int32_t *A, *R2;
+            PQ_TRY(rb_tie_starts(ctx, d, factor, fwd_return, (size_t)d.len * d.n, A, R2));
             const XsLds sh = xs_lds_shape(d.n);   // the row's P and bytes; the workgroup is RB_THR threads whatever P
             PQ_HIP_TRY(hipFuncSetAttribute((const void *)rb_group_rank_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh.bytes));
-            hipLaunchKernelGGL(rb_group_rank_kernel, dim3((unsigned)d.len), dim3(RB_THR), sh.bytes, ctx->stream, (const int32_t *)A, group,
-                               group_stride, d, G, sh.P, (int32_t *)rest, ic, n_valid);
+            hipLaunchKernelGGL(rb_group_rank_kernel, dim3((unsigned)d.len), dim3(RB_THR), sh.bytes, ctx->stream, (const int32_t *)A, grp.codes,
+                               grp.stride, d, G, sh.P, R2, ic, n_valid);
             PQ_HIP_TRY(hipGetLastError());
         } else { // wide: D-12's own Rank-IC on the factor masked to each group
             double *masked = nullptr;
@@ -480,7 +473,7 @@ pq_status pq_ic_subgroup(pq_ctx *ctx, const pq_batch *b, const double *factor, c
             pq_status st = PQ_OK;
             const int64_t cells = d.n * d.len;
             for (int g = 0; g < G && st == PQ_OK; g++) {
-                hipLaunchKernelGGL(rb_mask_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ctx->stream, factor, group, group_stride,
+                hipLaunchKernelGGL(rb_mask_kernel, dim3((unsigned)((cells + 255) / 256)), dim3(256), 0, ctx->stream, factor, grp.codes, grp.stride,
                                    d, g, masked);
                 st = hipGetLastError() == hipSuccess ? PQ_OK : PQ_ERR_HIP;
                 if (st != PQ_OK) pq_set_error("pq_ic_subgroup: mask launch failed");

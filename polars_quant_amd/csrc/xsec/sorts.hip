@@ -254,40 +254,30 @@ __global__ __launch_bounds__(256) void xs_coverage_final_kernel(const int32_t *c
 } // namespace
 
 // ---------------------------------------------------------------- host side of the cells stage (declared in xsec_dev.h)
-XsCellsWs xs_cells_layout(const Dims &d, int nkey, int ncell, bool caller_labels, const XsDaySort &plan) {
+XsCellsWs xs_cells_layout(XsWs &w, const Dims &d, int nkey, int ncell, bool caller_labels, const XsDaySort &plan) {
     const size_t cells = (size_t)d.len * (size_t)d.n, len = (size_t)d.len, part = (size_t)xs_nblk(d.n) * (size_t)ncell * len;
-    XsCellsWs ws;
-    ws.key_pitch = xs_al(cells * 8) / 8;
-    ws.o_nv = (size_t)nkey * ws.key_pitch * 8;
-    ws.o_ldm = ws.o_nv + xs_al(len * 4);
-    ws.o_lsm = ws.o_ldm + xs_al(cells);
-    ws.o_ps = ws.o_lsm + (caller_labels ? 0 : xs_al(cells));
-    ws.o_pc = ws.o_ps + xs_al(part * 8);
-    ws.o_pn = ws.o_pc + xs_al(part * 4);
-    ws.o_tail = ws.o_pn + xs_al(part * 4);
-    ws.bytes = ws.o_tail + plan.bytes;
+    XsCellsWs ws{nullptr, XsWs::pitch<double>(cells)};
+    w.take(ws.key, cells, nkey).take(ws.nv, len).take(ws.ldm, cells).take(ws.lsm, caller_labels ? 0 : cells);
+    w.take(ws.ps, part).take(ws.pc, part).take(ws.pn, part).take(ws.tail, plan.bytes);
     return ws;
 }
 
 pq_status xs_cells_stats(pq_ctx *ctx, const Dims &d, const XsCellsWs &ws, int ncell, uint8_t *labels, const double *ret, double *mean,
                          int32_t *count, double *tov) {
-    unsigned char *w = (unsigned char *)ctx->ws;
-    const uint8_t *lsm = labels ? labels : w + ws.o_lsm;
+    const uint8_t *lsm = labels ? labels : ws.lsm;
     const int64_t lstride = labels ? d.stride : d.len, nblk = xs_nblk(d.n);
-    double *psum = (double *)(w + ws.o_ps);
-    int32_t *pcnt = (int32_t *)(w + ws.o_pc), *pnew = (int32_t *)(w + ws.o_pn);
     const unsigned gx = (unsigned)((d.len + 63) / 64);
     if (d.n > 0)
         hipLaunchKernelGGL(xs_label_transpose_kernel, dim3(gx, (unsigned)((d.n + 63) / 64)), dim3(256), 0, ctx->stream,
-                           (const uint8_t *)(w + ws.o_ldm), d.n, d.len, (uint8_t *)lsm, lstride);
+                           (const uint8_t *)ws.ldm, d.n, d.len, (uint8_t *)lsm, lstride);
     // the accumulator form belongs to the cell count: registers while the cells fit them, LDS tiles above
     const auto partial = ncell <= 2 ? xs_cell_partial_reg_kernel<2> : ncell <= 5 ? xs_cell_partial_reg_kernel<5>
                        : ncell <= 10 ? xs_cell_partial_reg_kernel<10> : ncell <= 20 ? xs_cell_partial_reg_kernel<20>
                        : xs_cell_partial_lds_kernel;
     hipLaunchKernelGGL(partial, dim3(gx, (unsigned)nblk, ncell <= 20 ? 1u : (unsigned)((ncell + XS_CT - 1) / XS_CT)), dim3(64), 0,
-                       ctx->stream, lsm, lstride, ret, d, ncell, psum, pcnt, pnew);
-    hipLaunchKernelGGL(xs_cell_combine_kernel, dim3(gx, (unsigned)ncell), dim3(64), 0, ctx->stream, (const double *)psum,
-                       (const int32_t *)pcnt, (const int32_t *)pnew, nblk, d.len, ncell, mean, count, tov);
+                       ctx->stream, lsm, lstride, ret, d, ncell, ws.ps, ws.pc, ws.pn);
+    hipLaunchKernelGGL(xs_cell_combine_kernel, dim3(gx, (unsigned)ncell), dim3(64), 0, ctx->stream, (const double *)ws.ps,
+                       (const int32_t *)ws.pc, (const int32_t *)ws.pn, nblk, d.len, ncell, mean, count, tov);
     PQ_HIP_TRY(hipGetLastError());
     return PQ_OK;
 }
@@ -306,16 +296,13 @@ static pq_status xs_groups(pq_ctx *ctx, const pq_batch *b, const double *factor,
     const Dims d = dims_of(b);
     XsDaySort plan;
     PQ_TRY(xs_day_sort_plan(ctx, d, "factor sorts", &plan));
-    const XsCellsWs ws = xs_cells_layout(d, 1, ng, labels != nullptr, plan);
-    PQ_TRY(pq_ws_reserve(ctx, ws.bytes));
-    unsigned char *w = (unsigned char *)ctx->ws;
-    double *key = (double *)w;
-    int32_t *nv = (int32_t *)(w + ws.o_nv);
+    XsCellsWs ws;
+    PQ_TRY(xs_ws_carve(ctx, "factor sorts", [&](XsWs &w) { ws = xs_cells_layout(w, d, 1, ng, labels != nullptr, plan); }));
     if (d.n > 0) {
-        PQ_HIP_TRY(hipMemsetAsync(nv, 0, (size_t)d.len * 4, ctx->stream));
+        PQ_HIP_TRY(hipMemsetAsync(ws.nv, 0, (size_t)d.len * 4, ctx->stream));
         hipLaunchKernelGGL((xs_prep_kernel<1, XsKey>), dim3((unsigned)((d.len + 31) / 32), (unsigned)((d.n + 31) / 32)), dim3(256), 0,
-                           ctx->stream, XsKey{factor, fwd_return}, d, key, (int64_t)ws.key_pitch, nv);
-        PQ_TRY(xs_sort_lookup(ctx, d, plan, w + ws.o_tail, XsLabelOp{key, rule, w + ws.o_ldm}, nv));
+                           ctx->stream, XsKey{factor, fwd_return}, d, ws.key, (int64_t)ws.key_pitch, ws.nv);
+        PQ_TRY(xs_sort_lookup(ctx, d, plan, ws.tail, XsLabelOp{ws.key, rule, ws.ldm}, ws.nv));
     }
     PQ_TRY(xs_cells_stats(ctx, d, ws, ng, labels, fwd_return, mean, count, tov));
     hipLaunchKernelGGL(xs_spread_kernel, dim3((unsigned)((d.len + 63) / 64)), dim3(64), 0, ctx->stream, (const double *)mean, d.len, ng,

@@ -24,7 +24,6 @@
 
 namespace {
 
-constexpr int WL_MAX_G = 256;        // clean.hip's limit
 constexpr int WL_LDS_CELLS = 128;    // (column, industry) pairs of [64]-lane f64 accumulators per pass-1 workgroup: 64 KiB of LDS
 
 // columns of pass 1 per chunk: as many of the ncol as keep chunk * G within WL_LDS_CELLS, at least one.  So a workgroup's LDS is
@@ -38,9 +37,7 @@ inline int wl_chunk(int ncol, int G) {
 struct WlIn {
     const double *f[XO_MAX_K];
     const double *r, *w;   // w null: every weight 1.0
-    const int32_t *g;      // null: every symbol in group 0 (G = 1)
-    int64_t gstride;       // 0: g is [n_series]
-    int32_t G;
+    XsGroups grp;          // null codes: every symbol in group 0 (G = 1)
     Dims d;
 };
 
@@ -54,7 +51,7 @@ struct WlDay {
 
 enum WlTab { WL_CNT = 0, WL_W = 1, WL_R = 2, WL_F = 3 };
 
-__device__ __forceinline__ int64_t wl_tab(const WlIn &in, int q, int g, int64_t t) { return ((int64_t)q * in.G + g) * in.d.len + t; }
+__device__ __forceinline__ int64_t wl_tab(const WlIn &in, int q, int g, int64_t t) { return ((int64_t)q * in.grp.G + g) * in.d.len + t; }
 
 // the cells of one step of a (day, block) thread: B symbols loaded ahead, then their membership
 template <int K, int B> struct WlCells {
@@ -68,11 +65,11 @@ template <int K, int B> struct WlCells {
 #pragma unroll
             for (int j = 0; j < K; j++) f[k][j] = in.f[j][o];
             w[k] = in.w ? in.w[o] : 1.0;
-            g[k] = in.g ? in.g[in.gstride ? s * in.gstride + t : s] : 0;
+            g[k] = in.grp.codes ? in.grp.at(s, t) : 0;
         }
     }
     __device__ __forceinline__ bool member(const WlIn &in, int k) const {
-        bool mem = xs_valid(r[k]) && xs_valid(w[k]) && w[k] > 0.0 && g[k] >= 0 && g[k] < in.G;
+        bool mem = xs_valid(r[k]) && xs_valid(w[k]) && w[k] > 0.0 && in.grp.has(g[k]);
 #pragma unroll
         for (int j = 0; j < K; j++) mem = mem && xs_valid(f[k][j]);
         return mem;
@@ -89,7 +86,7 @@ __global__ __launch_bounds__(64) void wl_pass1_kernel(WlIn in, int c0, int c1, d
     const Dims d = in.d;
     const int64_t t = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (t >= d.len) return;
-    const int lane = threadIdx.x, G = in.G, nq = (c1 - c0) * G;
+    const int lane = threadIdx.x, G = in.grp.G, nq = (c1 - c0) * G;
     for (int q = 0; q < nq; q++) acc[q * 64 + lane] = 0.0;
     const int64_t s_lo = (int64_t)blockIdx.y * XS_BLOCK, s_hi = s_lo + XS_BLOCK < d.n ? s_lo + XS_BLOCK : d.n;
     constexpr int B = xo_ahead(K + 2);
@@ -130,7 +127,7 @@ __global__ __launch_bounds__(64) void wl_day_kernel(WlIn in, WlDay day) {
     if (t >= in.d.len) return;
     int32_t n = 0, gt = 0;
     double sw = 0.0, sr = 0.0;
-    for (int g = 0; g < in.G; g++) {
+    for (int g = 0; g < in.grp.G; g++) {
         const double c = day.tab[wl_tab(in, WL_CNT, g, t)];
         if (c > 0.0) {
             n += (int32_t)c;
@@ -184,7 +181,7 @@ __global__ __launch_bounds__(64) void wl_pass_kernel(WlIn in, WlDay day, double 
         double mr[B], mf[B][K];   // the means of the cell's industry (of industry 0 for a cell outside [0, G): not a member)
 #pragma unroll
         for (int k = 0; k < B; k++) {
-            const int g = c.g[k] >= 0 && c.g[k] < in.G ? c.g[k] : 0;
+            const int g = c.g[k] >= 0 && c.g[k] < in.grp.G ? c.g[k] : 0;   // written out: through has() +2 VGPRs per instantiation (XsGroups)
             mr[k] = day.tab[wl_tab(in, WL_R, g, t)];
 #pragma unroll
             for (int j = 0; j < K; j++) mf[k][j] = day.tab[wl_tab(in, WL_F + j, g, t)];
@@ -320,28 +317,21 @@ __global__ __launch_bounds__(64) void wl_industry_kernel(WlIn in, WlDay day, WlO
 template <int K>
 pq_status wl_run(pq_ctx *ctx, const WlIn &in, const WlOut &out) {
     const Dims d = in.d;
-    const int G = in.G, NC = K + 3, chunk = wl_chunk(NC, G);
+    const int G = in.grp.G, NC = K + 3, chunk = wl_chunk(NC, G);
     const int64_t nblk = xs_nblk(d.n);
-    const size_t len = (size_t)d.len, row = xs_al(len * 8);
+    const size_t len = (size_t)d.len;
     // workspace: n, G_t, ok (i32) | day rows (f64): rbar, srr, stot, s2, b [K], v [K], L [K (K - 1) / 2], D [K] | the table
     // [K + 3][G][len] | block partials: the larger of a pass-1 chunk [nblk][chunk][G][len] and pass 2's [nblk][NA][len]
-    constexpr int NL = K * (K - 1) / 2, ROWS = 4 + 3 * K + NL;
-    const size_t part = (size_t)nblk * len * 8, p1 = part * (size_t)chunk * (size_t)G, p2 = part * (size_t)WlNa<K>::P2;
-    const size_t o_rows = 3 * xs_al(len * 4), o_tab = o_rows + (size_t)ROWS * row, o_ps = o_tab + xs_al((size_t)NC * G * len * 8),
-                 total = o_ps + xs_al(p1 > p2 ? p1 : p2);
-    PQ_TRY(pq_ws_reserve(ctx, total));
-    unsigned char *ws = (unsigned char *)ctx->ws;
-    auto rows = [&](int k) { return (double *)(ws + o_rows + (size_t)k * row); };
+    constexpr int NL = K * (K - 1) / 2;
+    const size_t part = (size_t)nblk * len, p1 = part * (size_t)chunk * (size_t)G, p2 = part * (size_t)WlNa<K>::P2;
     WlDay day;
-    day.n = (int32_t *)ws;
-    day.gt = (int32_t *)(ws + xs_al(len * 4));
-    day.ok = (int32_t *)(ws + 2 * xs_al(len * 4));
-    day.rbar = rows(0); day.srr = rows(1); day.stot = rows(2); day.s2 = rows(3);
-    // b, v, L and D are read `len` doubles apart, so their rows are carved unaligned from one aligned span
-    double *span = rows(4);
-    day.b = span; day.v = span + (size_t)K * len; day.L = span + (size_t)2 * K * len; day.D = span + (size_t)(2 * K + NL) * len;
-    day.tab = (double *)(ws + o_tab);
-    double *ps = (double *)(ws + o_ps);
+    double *ps;
+    PQ_TRY(xs_ws_carve(ctx, "pq_xsec_regress_wls", [&](XsWs &w) {
+        w.take(day.n, len).take(day.gt, len).take(day.ok, len).take(day.rbar, len).take(day.srr, len).take(day.stot, len).take(day.s2, len);
+        // b, v, L and D are read `len` doubles apart, so their rows are carved unaligned from one aligned span
+        w.take(day.b, (size_t)(3 * K + NL) * len).take(day.tab, (size_t)NC * G * len).take(ps, p1 > p2 ? p1 : p2);
+    }));
+    day.v = day.b + (size_t)K * len; day.L = day.b + (size_t)2 * K * len; day.D = day.b + (size_t)(2 * K + NL) * len;
     const dim3 gd((unsigned)((d.len + 63) / 64)), gp(gd.x, (unsigned)nblk), gg(gd.x, (unsigned)G);
     hipStream_t st = ctx->stream;
     PQ_HIP_TRY(hipFuncSetAttribute((const void *)wl_pass1_kernel<K>, hipFuncAttributeMaxDynamicSharedMemorySize, chunk * G * 64 * 8));
@@ -374,17 +364,13 @@ pq_status pq_xsec_regress_wls(pq_ctx *ctx, const pq_batch *b, const double *cons
     const char *what = "pq_xsec_regress_wls";
     PQ_TRY(pq_check(ctx, b));
     if (k < 1 || k > XO_MAX_K) { pq_set_error("%s: k must be in [1, 8]", what); return PQ_ERR_ARG; }
-    if (n_groups < 1 || n_groups > WL_MAX_G) { pq_set_error("%s: n_groups must be in [1, 256]", what); return PQ_ERR_ARG; }
-    if (!group && n_groups != 1) { pq_set_error("%s: n_groups must be 1 without group codes", what); return PQ_ERR_ARG; }
+    WlIn in{};
+    PQ_TRY(xs_groups_arg(what, b, group, group_stride, n_groups, XsGroupsPolicy{XS_G_ALWAYS, "n_groups", "group"}, &in.grp));
     if (ctx->rec) { pq_set_error("%s cannot be recorded into a suite", what); return PQ_ERR_UNSUPPORTED; }
     if (b->offsets) { pq_set_error("%s: ragged batches are not supported", what); return PQ_ERR_UNSUPPORTED; }
-    if (group && group_stride != 0 && group_stride < b->len) {
-        pq_set_error("%s: group_stride must be 0 ([n_series] codes) or >= len", what);
-        return PQ_ERR_ARG;
-    }
+    PQ_TRY(xs_groups_stride(what, b, group != nullptr, group_stride));
     const bool empty = b->n_series == 0 || b->len == 0;
     if (!empty && (!factors || !fwd_return)) { pq_set_error("%s: null pointer", what); return PQ_ERR_ARG; }
-    WlIn in{};
     for (int j = 0; j < k && !empty; j++) {
         if (!factors[j]) { pq_set_error("%s: null factor pointer", what); return PQ_ERR_ARG; }
         in.f[j] = factors[j];
@@ -396,9 +382,6 @@ pq_status pq_xsec_regress_wls(pq_ctx *ctx, const pq_batch *b, const double *cons
     if (b->len == 0) return PQ_OK;
     in.r = fwd_return;
     in.w = weight;
-    in.g = group;
-    in.gstride = group ? group_stride : 0;
-    in.G = n_groups;
     in.d = dims_of(b);
     const WlOut out{coef, t_stat, p_value, r2, n_obs, n_groups_present, resid, summary};
     return xo_with_k<XO_MAX_K>(k, [&](auto K) { return wl_run<decltype(K)::value>(ctx, in, out); });

@@ -4,9 +4,11 @@
 // sort-then-look-up kernel pair with its host dispatch (sorts.hip, double_sort.hip, build.hip), and the host interface of daysort.hip for
 // rows too wide for LDS --, the host interface of the cells stage of sorts.hip (labels -> per-cell statistics -> summary; also
 // double_sort.hip), D-12's rank closed form (robust.hip) and the sequential summaries (sorts.hip, xsec_ttest.h).  The OLS core of
-// regress.hip (D-17) and orth.hip (D-19) is xsec_ols.h.
+// regress.hip (D-17) and orth.hip (D-19) is xsec_ols.h.  Host scaffolding of the entry points: xs_ws_carve reserves and binds a call's workspace
+// from one description of its spans (XsWs, xsec_ws.h); XsGroups and xs_groups_arg are the group (industry) codes argument (fetch, membership, checks).
 #pragma once
 #include "../pq_dev.h"
+#include "xsec_ws.h"
 
 namespace {
 
@@ -234,10 +236,48 @@ __device__ __forceinline__ double xs_rank_corr(int nv, unsigned long long sx, un
     return vx > 0.0 && vy > 0.0 ? (nn * Sxy - Sx * Sy) / (sqrt(vx) * sqrt(vy)) : pq_null();
 }
 
-inline size_t xs_al(size_t x) { return (x + 255) / 256 * 256; }
 // summation blocks over `span` indices, at least one (an empty span still gets its zero sums written)
 inline int64_t xs_nblk(int64_t span) { return span > XS_BLOCK ? (span + XS_BLOCK - 1) / XS_BLOCK : 1; }
-
+// `carve(XsWs &)` takes a call's spans in order: run on a null base to measure, then on ctx->ws to bind (one description, so they agree)
+template <class F> pq_status xs_ws_carve(pq_ctx *ctx, const char *what, F &&carve) {
+    XsWs measure{nullptr}, bind{nullptr};
+    carve(measure);
+    if (measure.bad) { pq_set_error("%s: the workspace does not fit size_t", what); return PQ_ERR_ARG; }
+    PQ_TRY(pq_ws_reserve(ctx, measure.off));
+    bind.base = (unsigned char *)ctx->ws;
+    carve(bind);
+    return PQ_OK;
+}
+constexpr int XS_MAX_GROUPS = PQ_IC_MAX_GROUPS;   // group (industry) codes: the one limit of every entry that takes them
+// int32 codes, one per symbol (stride 0) or per cell, `stride` codes from symbol to symbol; outside [0, G): unclassified.  Null codes keep the
+// file's meaning: group 0 (wls.hip, risk.hip) or no grouping (build.hip, clean.hip).  Kernels that compile to other code through the members keep
+// the fetch or test written out (EXPERIMENTS.md): cl_member, bd_w_member, rk_pf_pass1_kernel, wl_pass_kernel's clamp, rb_group_rank / rb_mask_kernel.
+struct XsGroups {
+    const int32_t *codes; int64_t stride; int32_t G;
+    __device__ __forceinline__ int32_t at(int64_t s, int64_t t) const { return codes[stride ? s * stride + t : s]; }
+    __device__ __forceinline__ int32_t at_cell(int64_t o) const { return codes[o]; }   // codes on the columns' own stride: the cell at offset o
+    __device__ __forceinline__ bool has(int32_t g) const { return g >= 0 && g < G; }
+};
+// The host checks, messages prefixed with `what` and worded with the entry's names for its count and codes.  XS_G_REQUIRED: the entry needs
+// codes and checks the count itself (pq_ic_subgroup, in rb_args), the stride is checked whatever the pointer; XS_G_WITH_CODES: the count is checked
+// with codes, ignored without (G = 0); XS_G_ALWAYS: checked always, 1 without codes, and the entry calls xs_groups_stride behind its own refusals.
+enum XsGroupsCount { XS_G_REQUIRED, XS_G_WITH_CODES, XS_G_ALWAYS };
+struct XsGroupsPolicy { XsGroupsCount mode; const char *count, *codes; };
+inline pq_status xs_groups_stride(const char *what, const pq_batch *b, bool checked, int64_t stride) {
+    if (!checked || stride == 0 || stride >= b->len) return PQ_OK;
+    pq_set_error("%s: group_stride must be 0 ([n_series] codes) or >= len", what);
+    return PQ_ERR_ARG;
+}
+inline pq_status xs_groups_arg(const char *what, const pq_batch *b, const int32_t *codes, int64_t stride, int32_t n_groups,
+                               const XsGroupsPolicy &policy, XsGroups *out) {
+    *out = XsGroups{codes, codes ? stride : 0, policy.mode == XS_G_WITH_CODES && !codes ? 0 : n_groups};
+    if ((policy.mode == XS_G_ALWAYS || (policy.mode == XS_G_WITH_CODES && codes)) && (n_groups < 1 || n_groups > XS_MAX_GROUPS))
+        pq_set_error("%s: %s must be in [1, %d]", what, policy.count, XS_MAX_GROUPS);
+    else if (policy.mode == XS_G_ALWAYS && !codes && n_groups != 1)
+        pq_set_error("%s: %s must be 1 without %s codes", what, policy.count, policy.codes);
+    else return policy.mode == XS_G_ALWAYS ? PQ_OK : xs_groups_stride(what, b, codes || policy.mode == XS_G_REQUIRED, stride);
+    return PQ_ERR_ARG;
+}
 } // namespace
 
 // ---------------------------------------------------------------- host side of the day sort (daysort.hip)
@@ -249,9 +289,9 @@ inline XsLds xs_lds_shape(int64_t n) {
     while (P < n) P <<= 1;
     return XsLds{P, P / 16 < 64 ? 64 : (P / 16 > 1024 ? 1024 : P / 16), (size_t)(P + P / 16) * 8};
 }
-// n > XS_LDS_MAX: rocPRIM's segmented radix sort in global memory.  The caller appends `bytes` to its workspace (0 when !wide) and hands
-// the start of that tail to xs_day_sort_wide; the offsets are relative to it: sorted keys (f64), segment offsets (u32), rocPRIM temp.
-struct XsDaySort { bool wide; size_t tmp_bytes, o_off, o_tmp, bytes; };
+// n > XS_LDS_MAX: rocPRIM's segmented radix sort in global memory.  The caller appends one span of `bytes` unsigned char to its workspace
+// (0 when !wide) and hands that tail's start to xs_day_sort_wide, which carves it: sorted keys (f64), segment offsets (u32), rocPRIM temp.
+struct XsDaySort { bool wide; size_t tmp_bytes, bytes; };
 // the width limits (PQ_ERR_ARG, the message prefixed with `who`) and rocPRIM's size query
 pq_status xs_day_sort_plan(pq_ctx *ctx, const Dims &d, const char *who, XsDaySort *plan);
 // sorts every day-major row of key[len][n] on ctx->stream; *sorted = the sorted rows (inside the tail)
@@ -279,12 +319,12 @@ pq_status xs_sort_lookup(pq_ctx *ctx, const Dims &d, const XsDaySort &plan, unsi
 } // namespace
 
 // ---------------------------------------------------------------- host side of the cells stage (sorts.hip)
-// workspace of a sort into cells, offsets in bytes: nkey key rows (f64, day-major, key_pitch doubles apart, from 0) | n per day (i32) |
-// labels day-major (u8) | labels symbol-major (u8, only when the caller passes none) | block partials: sums (f64), counts, new members
-// (i32) | the wide tail of xs_day_sort_plan
-struct XsCellsWs { size_t key_pitch, o_nv, o_ldm, o_lsm, o_ps, o_pc, o_pn, o_tail, bytes; };
-XsCellsWs xs_cells_layout(const Dims &d, int nkey, int ncell, bool caller_labels, const XsDaySort &plan);
-// day-major labels at ctx->ws + ws.o_ldm (cells 0 .. ncell-1, PQ_LABEL_MID, PQ_LABEL_OUT) -> labels symbol-major (into `labels`, or the
+// workspace of a sort into cells: nkey key rows (f64, day-major, key_pitch doubles apart) | n per day (i32) | labels day-major (u8) |
+// labels symbol-major (u8, only when the caller passes none) | block partials: sums (f64), counts, new members (i32) | the wide tail
+// of xs_day_sort_plan
+struct XsCellsWs { double *key; size_t key_pitch; int32_t *nv; uint8_t *ldm, *lsm; double *ps; int32_t *pc, *pn; unsigned char *tail; };
+XsCellsWs xs_cells_layout(XsWs &w, const Dims &d, int nkey, int ncell, bool caller_labels, const XsDaySort &plan);
+// day-major labels at ws.ldm (cells 0 .. ncell-1, PQ_LABEL_MID, PQ_LABEL_OUT) -> labels symbol-major (into `labels`, or the
 // workspace) -> mean / count / turnover [ncell][len] of `ret`, on ctx->stream
 pq_status xs_cells_stats(pq_ctx *ctx, const Dims &d, const XsCellsWs &ws, int ncell, uint8_t *labels, const double *ret, double *mean,
                          int32_t *count, double *tov);

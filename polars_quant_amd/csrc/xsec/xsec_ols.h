@@ -163,15 +163,12 @@ struct XoWs {
     double *ps;
     int32_t *pcnt;
 };
-inline pq_status xo_workspace(pq_ctx *ctx, int64_t units, int64_t nblk, int nv, int rows, int na, XoWs *w) {
+inline pq_status xo_workspace(pq_ctx *ctx, const char *who, int64_t units, int64_t nblk, int nv, int rows, int na, XoWs *w) {
     const size_t U = (size_t)units, part = (size_t)nblk * U;
-    const size_t o_flag = xs_al(U * 4), o_rows = o_flag + xs_al(U * 4), row = xs_al(U * 8), o_ps = o_rows + (size_t)rows * row,
-                 o_pc = o_ps + xs_al(part * na * 8), total = o_pc + xs_al(part * 4);
-    PQ_TRY(pq_ws_reserve(ctx, total));
-    unsigned char *ws = (unsigned char *)ctx->ws;
-    *w = XoWs{(int32_t *)ws, (int32_t *)(ws + o_flag), (double *)(ws + o_rows), (double *)(ws + o_rows + nv * row), row / 8,
-              (double *)(ws + o_ps), (int32_t *)(ws + o_pc)};
-    return PQ_OK;
+    w->row = XsWs::pitch<double>(U);
+    return xs_ws_carve(ctx, who, [&](XsWs &c) {
+        c.take(w->n, U).take(w->flag, U).take(w->mean, U, nv).take(w->own, U, rows - nv).take(w->ps, part * na).take(w->pcnt, part);
+    });
 }
 
 } // namespace
