@@ -906,6 +906,37 @@ pq_status pq_risk_portfolio(pq_ctx *, const pq_batch *, const double *holdings, 
                             const int32_t *industry, int64_t group_stride, int32_t n_groups, const double *cov, const double *specific_var,
                             int64_t sv_stride, int64_t day0, int64_t step, int64_t count, double *exposure_out, double *contribution_out,
                             double *risk_out, int32_t *n_out);
+/* Portfolio construction from the risk model (api.risk_solve, Factor.optimal_portfolio; decision D-34 in DESIGN.md section 2): on every
+ * as-of day y_r = Sigma^-1 v_r for n_rhs = R right-hand sides at once, Sigma = B F B^T + diag(s^2) (never built), and the matrix
+ * v_r^T Sigma^-1 v_q.  rhs is a HOST array of 1 <= R <= PQ_RISK_SOLVE_MAX_RHS device pointers [n_series][stride] on the batch's pitch,
+ * read at day t_d; a NULL entry is the vector of ones.  exposures / k, industry / group_stride / n_groups = G, cov [count][M][M] (M = k + G),
+ * specific_var / sv_stride and the as-of days are pq_risk_portfolio's; 1 <= M <= PQ_RISK_SOLVE_MAX_M (a larger M: PQ_ERR_UNSUPPORTED).
+ * The universe U of a day: every given rhs non-null and finite, every exposure non-null and finite, a given code in [0, G), and s^2 > 0
+ * (NULL, NaN, zero or negative fails).  n_out [2][count]: |U|, and the symbols whose rhs are all valid but that fail another condition
+ * (uncovered): such a symbol is outside U and its y is NULL, the day goes on.  With q_i = 1.0 / s^2_i, every product rounded before it is
+ * added and every sum D-12's blocked sum (blocks of 256 symbol indices, ascending from 0.0, block sums in ascending order):
+ * A[j][l] = sum_U (q x_j) x_l for l <= j < k, mirrored; A[k+g][j] = A[j][k+g] = sum over U in g of q x_j; A[k+g][k+g] = sum over U in g
+ * of q; other industry-industry entries exactly 0.0; p_r[j] = sum_U (q x_j) v_r, p_r[k+g] = sum over U in g of q v_r.  Active rows
+ * J = {j: A[j][j] > 0} ascending (an industry without a member, a factor that is 0 on all of U take no part); a NULL cov[j][l] with j and l
+ * in J makes the day NULL, one outside does not.  Compacted to m = |J|: S[a][b] = sum_c F[a][c] A[c][b] over ascending c from 0.0, then
+ * + 1.0 on the diagonal; c_r[a] = sum_c F[a][c] p_r[c]: (I + F A) u = F p, which needs neither F^-1 nor a positive semi-definite F.
+ * In-place LU with partial pivoting on [S | c_0 .. c_{R-1}]: at column c the pivot is the first row >= c with the largest |S[.][c]| (a NaN
+ * never displaces an entry), swapped in; for i > c: mu = S[i][c] / S[c][c], S[i][l] = S[i][l] - mu S[c][l] for l > c and on every rhs;
+ * then u[a] = (c[a] - sum_{b>a} S[a][b] u[b]) / S[a][a], the sum over ascending b from 0.0.  A pivot that is 0, NaN or infinite, a u that
+ * is not finite and |U| = 0 make the day NULL.  For i in U: y_r,i = q_i (v_r,i - e), e = sum over j < k in J of x_ij u_r[j] (ascending
+ * from 0.0), then + u_r[k + g_i].  y is NULL outside U and on NULL days; a NaN result is NULL.  y_out: a HOST array of R device pointers
+ * [n_series][out_stride], out_stride >= count, indexed by d (specific_var's layout).  quad_out [R][R][count]: entry [r][q], q <= r, is the
+ * blocked sum over U of v_r y_q, mirrored to [q][r] (one evaluation per unordered pair: exactly symmetric), NULL on NULL days.
+ * PQ_ERR_ARG: a null required pointer, k, n_rhs, n_groups, group_stride, sv_stride, out_stride or the as-of days out of range, an output
+ * that overlaps an input or another output; ragged batches and suite recording are refused (PQ_ERR_UNSUPPORTED); count = 0, len = 0 or
+ * n_series = 0 launches nothing.  Uses the context workspace (block partials of at most k (k + 1) / 2 + k R + 128 cells per (as-of day,
+ * block of 256 symbols), and (1 + k + R) G + R M cells per as-of day). */
+#define PQ_RISK_SOLVE_MAX_RHS 4
+#define PQ_RISK_SOLVE_MAX_M 128
+pq_status pq_risk_solve(pq_ctx *, const pq_batch *, const double *const *rhs, int32_t n_rhs, const double *const *exposures, int32_t k,
+                        const int32_t *industry, int64_t group_stride, int32_t n_groups, const double *cov, const double *specific_var,
+                        int64_t sv_stride, int64_t day0, int64_t step, int64_t count, double *const *y_out, int64_t out_stride,
+                        double *quad_out, int32_t *n_out);
 
 /* ---- suites: record many calls, replay them as a few chip-filling grids ----
  * One indicator over N symbols is only N/64 wavefronts -- far too few for 256 CUs -- but a DataFrame query asks

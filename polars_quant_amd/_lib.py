@@ -159,6 +159,7 @@ factor_combine         i pBpipip
 risk_factor_cov        i pBppllilllpp
 risk_specific_var      i pBppllilllplp
 risk_portfolio         i pBppiplippllllpppp
+risk_solve             i pBpipiplippllllplpp
 suite_begin            i pB
 suite_end              i pp
 suite_abort            i p

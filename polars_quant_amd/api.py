@@ -1324,6 +1324,27 @@ def risk_portfolio(holdings, exposures, cov, specific_var, industry=None, day0: 
     for j, c in enumerate(cols):
         if _shape(c) != hs:
             raise ValueError(f"exposure {j} must have the holdings' shape {hs}, not {_shape(c)}")
+    D, M, G, ind, day0, step = _risk_model_args(hs, K, cov, specific_var, industry, day0, step, "holdings")
+    mats = _same_layout([_to_device(c)[0] for c in [holdings] + cols])
+    h = mats[0]
+    dev = h.device
+    b = _batch(h)
+    f64 = dict(dtype=torch.float64, device=dev)
+    expo, contrib = (torch.empty((M, D), **f64) for _ in range(2))
+    risk = torch.empty((4, D), **f64)
+    cnt = torch.empty((2, D), dtype=torch.int32, device=dev)
+    if D:
+        cv, sv, svs, gp, gs = _risk_model_dev(cov, specific_var, ind, n, D, b, dev)
+        ptrs = (C.c_void_p * max(K, 1))(*[m.data_ptr() for m in mats[1:]]) if n else None
+        _call("pq_risk_portfolio", dev, b, h, ptrs, K, gp, gs, G, cv, sv, svs, day0, step, D, expo, contrib, risk, cnt)
+    return {"exposure": expo, "contribution": contrib, "factor_var": risk[0], "specific_var": risk[1], "total_var": risk[2],
+            "volatility": risk[3], "n_held": cnt[0], "n_uncovered": cnt[1]}
+
+
+def _risk_model_args(hs, K, cov, specific_var, industry, day0, step, of):
+    """argument checks of risk_portfolio / risk_solve that need no device: the model's shapes against the [N, T] = hs of the `of` and
+    the K exposures -> (D, M, G, industry as an integer tensor or None, day0, step)"""
+    n, T = hs
     cs, vs = _shape(cov), _shape(specific_var)
     if len(cs) != 3 or cs[1] != cs[2]:
         raise ValueError(f"cov must be [D, M, M], not {cs}")
@@ -1342,28 +1363,74 @@ def risk_portfolio(holdings, exposures, cov, specific_var, industry=None, day0: 
         raise ValueError(f"specific_var must be [N, D] = {(n, D)}, not {vs}")
     day0, step, fit = _risk_days(T, day0, step, None)
     if D > fit:
-        raise ValueError(f"the {D} as-of days of cov do not fit the {T} days of the holdings from day0 = {day0} with step = {step}")
-    mats = _same_layout([_to_device(c)[0] for c in [holdings] + cols])
-    h = mats[0]
-    dev = h.device
-    b = _batch(h)
+        raise ValueError(f"the {D} as-of days of cov do not fit the {T} days of the {of} from day0 = {day0} with step = {step}")
+    return D, M, G, ind, day0, step
+
+
+def _risk_model_dev(cov, specific_var, ind, n, D, b, dev):
+    """the model on the device -> (cov contiguous, specific_var with unit inner stride, its row pitch, the codes on the batch's pitch,
+    their pitch)"""
     f64 = dict(dtype=torch.float64, device=dev)
-    expo, contrib = (torch.empty((M, D), **f64) for _ in range(2))
-    risk = torch.empty((4, D), **f64)
+    cv = (cov if isinstance(cov, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(cov, dtype=np.float64))))
+    cv = cv.to(**f64).contiguous()
+    sv = (specific_var if isinstance(specific_var, torch.Tensor)
+          else torch.from_numpy(np.ascontiguousarray(np.asarray(specific_var, dtype=np.float64)))).to(**f64)
+    if sv.stride(1) != 1 or (n > 1 and sv.stride(0) < D):
+        sv = sv.contiguous()
+    gp, gs = (None, 0) if ind is None else _codes_on_pitch(ind, b, dev)
+    return cv, sv, max(sv.stride(0), D) if n > 1 else D, gp, gs
+
+
+RISK_SOLVE_MAX_RHS = 4        # PQ_RISK_SOLVE_MAX_RHS
+RISK_SOLVE_MAX_M = 128        # PQ_RISK_SOLVE_MAX_M
+
+
+def risk_solve(rhs, exposures, cov, specific_var, industry=None, day0: int = 0, step: int = 1):
+    """D-34: y_r = Sigma^-1 v_r on the D as-of days day0 + d * step under the risk model Sigma = B F B^T + diag(s^2) of cov [D, M, M]
+    (risk_factor_cov's) and specific_var [N, D] (risk_specific_var's), for the R right-hand sides of the list rhs at once (1 <= R <= 4;
+    an entry is an [N, T] array or None for the vector of ones), and the matrix v_r' Sigma^-1 v_q.  exposures (a list of K [N, T] arrays
+    or one [K, N, T] array, 0 <= K <= 8; None: K = 0) and industry are risk_portfolio's, M = K + G <= 128.  Sigma is never built: one
+    pass over the symbols, an M x M solve per day and one more pass.
+    -> (y [R, N, D], quad [R, R, D], n [2, D] int32: the universe and the uncovered symbols) as device tensors.  The universe of a day:
+    every given rhs and every exposure non-null and finite, a code in [0, G) and a specific variance > 0; y is NULL outside it.  A symbol
+    whose rhs are valid but that lacks an exposure, an industry or a variance is uncovered: it gets no y, the day goes on.  A day is
+    NULL where the universe is empty, where a covariance between two rows that take part is NULL, and where the system is singular."""
+    if not isinstance(rhs, (list, tuple)) or not 1 <= len(rhs) <= RISK_SOLVE_MAX_RHS:
+        raise ValueError(f"rhs must be a list of 1..{RISK_SOLVE_MAX_RHS} [N, T] arrays (None: the vector of ones)")
+    cols = [] if exposures is None else _columns(exposures, "the number of exposures", 0, REGRESS_MAX_K, 3,
+                                                 "exposures must be a list of [N, T] arrays or one [K, N, T] array")
+    R, K = len(rhs), len(cols)
+    given = [v for v in rhs if v is not None]
+    if not given and not cols:
+        raise ValueError("with every rhs None and no exposure nothing tells the days: pass one rhs as an [N, T] array of ones")
+    hs = _shape((given + cols)[0])
+    if len(hs) != 2:
+        raise ValueError(f"the columns must be [N, T], not {hs}")
+    n, T = hs
+    for j, v in enumerate(rhs):
+        if v is not None and _shape(v) != hs:
+            raise ValueError(f"rhs {j} must have the columns' shape {hs}, not {_shape(v)}")
+    for j, c in enumerate(cols):
+        if _shape(c) != hs:
+            raise ValueError(f"exposure {j} must have the columns' shape {hs}, not {_shape(c)}")
+    D, M, G, ind, day0, step = _risk_model_args(hs, K, cov, specific_var, industry, day0, step, "columns")
+    if M > RISK_SOLVE_MAX_M:
+        raise ValueError(f"K + G = {M} rows: risk_solve solves at most {RISK_SOLVE_MAX_M} (the system lives in LDS)")
+    mats = _same_layout([_to_device(c)[0] for c in given + cols])
+    dev = mats[0].device
+    b = _batch(mats[0])
+    y = torch.empty((R, n, D), dtype=torch.float64, device=dev)
+    if not (D and n):                                           # nothing is launched: every day's universe is empty
+        return y, torch.from_numpy(np.full((R, R, D), NULL)).to(dev), torch.zeros((2, D), dtype=torch.int32, device=dev)
+    quad = torch.empty((R, R, D), dtype=torch.float64, device=dev)
     cnt = torch.empty((2, D), dtype=torch.int32, device=dev)
-    if D:
-        cv = (cov if isinstance(cov, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(cov, dtype=np.float64))))
-        cv = cv.to(**f64).contiguous()
-        sv = (specific_var if isinstance(specific_var, torch.Tensor)
-              else torch.from_numpy(np.ascontiguousarray(np.asarray(specific_var, dtype=np.float64)))).to(**f64)
-        if sv.stride(1) != 1 or (n > 1 and sv.stride(0) < D):
-            sv = sv.contiguous()
-        gp, gs = (None, 0) if ind is None else _codes_on_pitch(ind, b, dev)
-        ptrs = (C.c_void_p * max(K, 1))(*[m.data_ptr() for m in mats[1:]]) if n else None
-        _call("pq_risk_portfolio", dev, b, h, ptrs, K, gp, gs, G, cv, sv, max(sv.stride(0), D) if n > 1 else D, day0, step, D,
-              expo, contrib, risk, cnt)
-    return {"exposure": expo, "contribution": contrib, "factor_var": risk[0], "specific_var": risk[1], "total_var": risk[2],
-            "volatility": risk[3], "n_held": cnt[0], "n_uncovered": cnt[1]}
+    cv, sv, svs, gp, gs = _risk_model_dev(cov, specific_var, ind, n, D, b, dev)
+    vp = iter(mats[:len(given)])
+    rp = (C.c_void_p * R)(*[None if v is None else next(vp).data_ptr() for v in rhs])
+    xp = (C.c_void_p * max(K, 1))(*[m.data_ptr() for m in mats[len(given):]])
+    yp = (C.c_void_p * R)(*[y[r].data_ptr() for r in range(R)])
+    _call("pq_risk_solve", dev, b, rp, R, xp, K, gp, gs, G, cv, sv, svs, day0, step, D, yp, D, quad, cnt)
+    return y, quad, cnt
 
 
 ROLLING_REGRESS_MAX_K = 4                                      # PQ_ROLLING_REGRESS_MAX_K

@@ -36,8 +36,6 @@ static_assert(RK_MAX_SERIES == RK_MAX_K + XS_MAX_GROUPS, "the rows of D-32's coe
 constexpr int RK_LCHUNK = 8;                                    // columns l per workgroup of the covariance: column j is restaged once per 8
 constexpr int RK_STAGE = 2048;                                  // staged entries per column at a step > 1 (16 KiB), XW_STAGE at most at step 1
 
-struct RkDays { int64_t day0, step, count; };                   // as-of day d = day0 + d * step, d = 0 .. count - 1
-
 // days per tile: XW_TILE as-of days' worth, as far as the tile and its halo stay within RK_STAGE entries, and never below XW_TILE.  With
 // XW_TILE days at every step a workgroup at step 20 would stage 256 + w - 1 entries per column for 13 live lanes.
 inline int rk_tile_days(int64_t step, int w) {
@@ -149,8 +147,6 @@ struct RkPf {
     RkDays a;
 };
 
-__device__ __forceinline__ double rk_nan_null(double v) { return v == v ? v : pq_null(); }
-
 // accumulators [K + G + 1][lane] in LDS: X_0 .. X_{K-1}, the G industry rows, the specific sum; block partials ps[block][K + G + 1][count]
 // and the counts pc[block][2][count] (held, uncovered)
 __global__ __launch_bounds__(64) void rk_pf_pass1_kernel(RkPf in, double *ps, int32_t *pc) {
@@ -256,17 +252,7 @@ __global__ __launch_bounds__(64) void rk_pf_final_kernel(const double *X, const 
     risk[3 * D + dd] = nul || tot < 0.0 ? pq_null() : rk_nan_null(sqrt(tot));
 }
 
-// ---------------------------------------------------------------- host
-// the as-of days against the batch's length; *a gets a step that no kernel can overflow on (a lone day has no step)
-inline pq_status rk_days(const char *what, int64_t len, int64_t day0, int64_t step, int64_t count, RkDays *a) {
-    if (day0 < 0 || step < 1 || count < 0 || (count > 0 && (day0 >= len || (count - 1) > (len - 1 - day0) / step))) {
-        pq_set_error("%s: the as-of days need day0 >= 0, step >= 1, count >= 0 and day0 + (count - 1) * step < len", what);
-        return PQ_ERR_ARG;
-    }
-    *a = RkDays{day0, count > 1 ? step : 1, count};
-    return PQ_OK;
-}
-
+// ---------------------------------------------------------------- host (the as-of days: rk_days, xsec_dev.h)
 template <bool DIAG>
 pq_status rk_windowed(const char *what, pq_ctx *ctx, const pq_batch *b, const double *f, const double *omega, int64_t window,
                       int64_t min_periods, int32_t unbiased, int64_t day0, int64_t step, int64_t count, double *out, int64_t out_stride,

@@ -278,6 +278,18 @@ inline pq_status xs_groups_arg(const char *what, const pq_batch *b, const int32_
     else return policy.mode == XS_G_ALWAYS ? PQ_OK : xs_groups_stride(what, b, codes || policy.mode == XS_G_REQUIRED, stride);
     return PQ_ERR_ARG;
 }
+// The as-of days of the risk entries (risk.hip: D-33, risk_solve.hip: D-34): day d = day0 + d * step, d = 0 .. count - 1, checked against the
+// batch's length; *a gets a step that no kernel can overflow on (a lone day has no step)
+struct RkDays { int64_t day0, step, count; };
+inline pq_status rk_days(const char *what, int64_t len, int64_t day0, int64_t step, int64_t count, RkDays *a) {
+    if (day0 < 0 || step < 1 || count < 0 || (count > 0 && (day0 >= len || (count - 1) > (len - 1 - day0) / step))) {
+        pq_set_error("%s: the as-of days need day0 >= 0, step >= 1, count >= 0 and day0 + (count - 1) * step < len", what);
+        return PQ_ERR_ARG;
+    }
+    *a = RkDays{day0, count > 1 ? step : 1, count};
+    return PQ_OK;
+}
+__device__ __forceinline__ double rk_nan_null(double v) { return v == v ? v : pq_null(); }
 } // namespace
 
 // ---------------------------------------------------------------- host side of the day sort (daysort.hip)

@@ -20,6 +20,8 @@ factor) times the factor, independent or dependent, with the cells' returns and 
 `risk_model` and `portfolio_risk` (decision D-33, beyond the README) consume the three series of `pure_factor_return` (decision D-32):
 the exponentially weighted covariance of the factor and industry returns and the specific variance of every symbol on the rebalance
 days, and from the two the predicted variance of a portfolio with its exposures and each factor's contribution.
+`optimal_portfolio` (decision D-34, beyond the README) is the step after them: the minimum-variance, tangency or mean-variance weights
+under that model on every rebalance day, from Sigma^-1 v through the factor structure (Sigma itself is never built).
 """
 from __future__ import annotations
 
@@ -418,6 +420,60 @@ class Factor:
         if "specific_var" not in model:
             raise ValueError("the model has no specific_var: pass specific returns to risk_model")
         return _api.risk_portfolio(holdings, exposures, model["factor_cov"], model["specific_var"], industry, model["day0"], model["step"])
+
+    # ---- D-34: the portfolio that the risk model itself chooses
+    def optimal_portfolio(self, exposures, model, alpha=None, industry=None, objective="min_variance", risk_aversion=1.0):
+        """The minimum-variance, tangency or mean-variance portfolio under the model Sigma = B F B' + diag(s^2) on each of its as-of days.
+        exposures, industry and model are portfolio_risk's; alpha [N, T] is the expected return of every symbol.  objective:
+        "min_variance" (minimise w' Sigma w subject to 1' w = 1): w = y_1 / q_11; "max_sharpe" (alpha needed): w = y_a / q_1a, NULL where
+        q_1a is not > 0; "mean_variance" (alpha needed; maximise a' w - (risk_aversion / 2) w' Sigma w subject to 1' w = 1):
+        w = (y_a - g y_1) / risk_aversion with g = (q_1a - risk_aversion) / q_11.  Here y_v = Sigma^-1 v and q_uv = u' Sigma^-1 v come
+        from one api.risk_solve call with the right-hand sides [ones] or [ones, alpha]; Sigma is never built.
+        -> {"weights": [N, D], "predicted_var": [D] (w' Sigma w, from the same q: not a second pass), "expected_return": [D] (a' w, NULL
+        without alpha), "n_universe", "n_uncovered": [D] (int32), "days": [D] (int64)}.  A symbol that lacks an exposure, an industry, a
+        specific variance or an alpha on a day gets a NULL weight (n_uncovered counts those whose alpha is there); a day is NULL where no
+        symbol is left, where a covariance that the system needs is NULL and where the system is singular.
+        The weights sum to 1 and are unconstrained in sign: long-only or box constraints need an iterative solver and are not covered.
+        Not annualised.  Look-ahead: pure_factor_return regresses the NEXT return, so a model "as of t" from its series is known one day
+        later (risk_model's note)."""
+        if objective not in ("min_variance", "max_sharpe", "mean_variance"):
+            raise ValueError(f"objective must be 'min_variance', 'max_sharpe' or 'mean_variance', not {objective!r}")
+        if alpha is None and objective != "min_variance":
+            raise ValueError(f"objective {objective!r} needs alpha")
+        lam = float(risk_aversion)
+        if not (0.0 < lam < float("inf")):
+            raise ValueError(f"risk_aversion must be finite and > 0, not {risk_aversion!r}")
+        if "specific_var" not in model:
+            raise ValueError("the model has no specific_var: pass specific returns to risk_model")
+        if alpha is None:       # (the vector of ones as an array: it tells the days where there is no exposure either)
+            T = int(model["day0"]) + max(int(_api._shape(model["factor_cov"])[0]) - 1, 0) * int(model["step"]) + 1
+            first = next(iter(exposures), None) if isinstance(exposures, (list, tuple)) else (None if exposures is None else exposures[0])
+            rhs = [None] if first is not None else [torch.ones((_api._shape(model["specific_var"])[0], T), dtype=torch.float64)]
+        else:
+            rhs = [None, alpha]
+        y, q, n = _api.risk_solve(rhs, exposures, model["factor_cov"], model["specific_var"], industry, model["day0"], model["step"])
+        null = torch.from_numpy(_api.np.full(1, _api.NULL)).to(y.device)[0]   # (a tensor copy keeps NULL's payload)
+        nn = lambda v: torch.where(torch.isnan(v), null, v)   # noqa: E731
+        q11 = q[0, 0]
+        if objective == "min_variance":
+            w, var = y[0] / q11, 1.0 / q11
+            ret = q[1, 0] / q11 if alpha is not None else torch.full_like(q11, float("nan"))
+        else:
+            q1a, qaa = q[1, 0], q[1, 1]
+            if objective == "max_sharpe":
+                bad = ~(q1a > 0.0)
+                w, var, ret = y[1] / q1a, qaa / (q1a * q1a), qaa / q1a
+                w, var, ret = torch.where(bad, null, w), torch.where(bad, null, var), torch.where(bad, null, ret)
+            else:
+                lt = torch.full((), lam, dtype=torch.float64, device=y.device)   # a device divisor: a true division, no reciprocal
+                gam = (q1a - lt) / q11
+                w = (y[1] - gam * y[0]) / lt
+                ret = (qaa - gam * q1a) / lt
+                var = ((qaa - (2.0 * gam) * q1a) + (gam * gam) * q11) / (lt * lt)
+        D = q.shape[2]
+        days = int(model["day0"]) + int(model["step"]) * torch.arange(D, dtype=torch.int64, device=y.device)
+        return {"weights": nn(w), "predicted_var": nn(var), "expected_return": nn(ret), "n_universe": n[0], "n_uncovered": n[1],
+                "days": days}
 
     def time_series_regression(self, factors, returns):
         """factors: a list of [N, T] or [T] arrays (a [T] series, e.g. a market return, is shared by every symbol) or one [K, N, T]
