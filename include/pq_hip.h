@@ -938,6 +938,45 @@ pq_status pq_risk_solve(pq_ctx *, const pq_batch *, const double *const *rhs, in
                         int64_t sv_stride, int64_t day0, int64_t step, int64_t count, double *const *y_out, int64_t out_stride,
                         double *quad_out, int32_t *n_out);
 
+/* ---- rank 3, continued: the backtest of GIVEN target weights, signed and with cash (api.factor_weights, Factor.weights_backtest; decision
+ * D-35 in DESIGN.md section 2): what pq_risk_solve's y_out / Factor.optimal_portfolio's weights, a composite's or the caller's own weights
+ * would have earned, for P = n_portfolios portfolios at once (the price plane is read once for all of them).  Everything not said here is
+ * pq_factor_portfolio's: usable, the held price h(s, t), the ownership of days, the chain.  weights: a HOST array of P device pointers
+ * [n_series][w_stride], column k = rebalance k (pq_risk_solve's y_out layout), w_stride >= n_rebalance; price on the batch's pitch;
+ * rebalance_days d_0 < ... < d_{R-1}: a HOST array, each in [0, len).  Every sum is D-12's blocked sum (blocks of 256 symbols, ascending
+ * from 0.0, block sums ascending from 0.0), every product is rounded before it is added.  For portfolio p and rebalance k:
+ *   target       w = weights[p][s][k] non-null, finite and != 0.0 (NULL, NaN and +-inf are silently not held: NULL is what D-34 writes
+ *                outside its universe)
+ *   member       a target whose price[s][d_k] is usable: M_k; a target without one is DROPPED: counted, it contributes nothing and its
+ *                weight stays in cash.  count [3][P][R]: members with w > 0, members with w < 0, dropped
+ *   exposure     [2][P][R]: net W_k = sum over M_k of w, gross = sum over M_k of |w|; cash c_k = 1.0 - W_k (negative under leverage)
+ *   growth       for d_k < t <= d_{k+1} (the last segment runs to len - 1): L = sum over M_k of w * (h(s, t) / price[s][d_k]),
+ *                G(p, t) = c_k + L; an empty M_k gives L = 0.0 and G = 1.0
+ *   turnover     [P][R]: the sum over ALL symbols of |w_new - w_old|; w_new = the member's w, 0.0 for a non-member; w_old = 0.0 at k = 0,
+ *                else for s in M_{k-1}: (w * (h(s, d_k) / price[s][d_{k-1}])) / G(p, d_k), 0.0 for a symbol not held.  The cash leg is
+ *                not counted
+ *   value        [P][len]: P_0 = initial_capital, P_k = B_{k-1} * G(p, d_k), B_k = P_k * (1 - cost_rate * turnover[p][k]); value[p][t] =
+ *                initial_capital for t < d_0, B_k at t = d_k, B_k * G(p, t) for d_k < t <= d_{k+1}.  Plain IEEE f64, no NULL is written;
+ *                a non-finite or negative result stays as it is
+ *   first_nonpositive [P]: the smallest t whose value[p][t] is not > 0.0 (<= 0 or NaN), -1 if there is none: a signed, levered book can
+ *                be ruined, and the curve after that day means nothing
+ *   holdings     of portfolio holdings_of, holdings_out[s][t] on the batch's pitch (what pq_risk_portfolio reads): 0.0 for t < d_0 and for
+ *                a non-member; at t = d_k the member's w itself; for d_k < t < d_{k+1} (to len - 1 in the last segment)
+ *                (w * (h(s, t) / price[s][d_k])) / G(p, t)
+ * With 2^m members, clean prices and equal weights 1 / 2^m, W_k is exactly 1.0, c_k exactly 0.0 and value and turnover are
+ * pq_factor_portfolio's (one group, equal weights) bit for bit.  1 <= P <= PQ_WEIGHTS_MAX_PORTFOLIOS, cost_rate in [0, 1), initial_capital
+ * > 0 and finite, holdings_of in [-1, P) and set exactly when holdings_out is; a null required pointer and an output that overlaps an
+ * input or another output are PQ_ERR_ARG; ragged batches and suite recording are refused (PQ_ERR_UNSUPPORTED); len == 0 or n_series == 0
+ * returns PQ_OK with nothing launched; n_rebalance == 0 gives every value cell initial_capital, first_nonpositive -1 and holdings 0.0.
+ * Uses the context workspace (8 bytes per portfolio, day and block of 256 symbols). */
+#define PQ_WEIGHTS_MAX_PORTFOLIOS 8
+pq_status pq_factor_weights(pq_ctx *, const pq_batch *, const double *const *weights, int32_t n_portfolios, int64_t w_stride,
+                            const double *price, const int32_t *rebalance_days /* HOST, n_rebalance entries */, int64_t n_rebalance,
+                            double cost_rate, double initial_capital, double *value /* [P][len] */, double *turnover /* [P][R] */,
+                            double *exposure /* [2][P][R]: net, gross */, int32_t *count /* [3][P][R]: long, short, dropped */,
+                            int32_t *first_nonpositive /* [P] */, int32_t holdings_of /* portfolio index, or -1 */,
+                            double *holdings_out /* [n_series][stride], or NULL */);
+
 /* ---- suites: record many calls, replay them as a few chip-filling grids ----
  * One indicator over N symbols is only N/64 wavefronts -- far too few for 256 CUs -- but a DataFrame query asks
  * for many indicators at once (df.with_columns([...]) in the reference; Polars then calls the plugin once per

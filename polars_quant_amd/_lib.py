@@ -160,6 +160,7 @@ risk_factor_cov        i pBppllilllpp
 risk_specific_var      i pBppllilllplp
 risk_portfolio         i pBppiplippllllpppp
 risk_solve             i pBpipiplippllllplpp
+factor_weights         i pBpilpplddpppppip
 suite_begin            i pB
 suite_end              i pp
 suite_abort            i p

@@ -594,6 +594,94 @@ def factor_portfolio(labels, price, n_groups: int, rebalance_days, weight=None, 
     return out
 
 
+WEIGHTS_MAX_PORTFOLIOS = 8    # PQ_WEIGHTS_MAX_PORTFOLIOS
+
+
+def _factor_weights_args(weights, price, rebalance_days, cost_rate, initial_capital, holdings_of):
+    """argument checks of factor_weights that need no device -> (list of P [N, R] weight arrays, (N, T), int32 days [R], cost_rate,
+    initial_capital, holdings_of as -1 or an index)"""
+    shapes = "weights must be one [N, R] array, a list of [N, R] arrays or one [P, N, R] array"
+    if isinstance(weights, (list, tuple)):
+        cols = list(weights)
+    else:
+        ws = _shape(weights)
+        if len(ws) not in (2, 3):
+            raise ValueError(f"{shapes}, not {ws}")
+        cols = [weights] if len(ws) == 2 else [weights[j] for j in range(ws[0])]
+    if not 1 <= len(cols) <= WEIGHTS_MAX_PORTFOLIOS:
+        raise ValueError(f"the number of portfolios must be in 1..{WEIGHTS_MAX_PORTFOLIOS}, not {len(cols)}")
+    ps = _shape(price)
+    if len(ps) != 2:
+        raise ValueError(f"price must be [N, T], not {ps}")
+    n, T = ps
+    days = np.asarray(rebalance_days)
+    if days.size and days.dtype.kind not in "iu":
+        raise ValueError("rebalance_days must hold integer day indices")
+    days = days.reshape(-1).astype(np.int64)
+    if days.size and (days.min() < 0 or days.max() >= T):
+        raise ValueError(f"rebalance_days must lie in [0, T) = [0, {T})")
+    if (np.diff(days) <= 0).any():
+        raise ValueError("rebalance_days must be strictly ascending")
+    for j, c in enumerate(cols):
+        if _shape(c) != (n, days.size):
+            raise ValueError(f"weights {j} must be [N, R] = {(n, days.size)} (one column per rebalance day), not {_shape(c)}")
+    cost, cap = float(cost_rate), float(initial_capital)
+    if not 0.0 <= cost < 1.0:
+        raise ValueError(f"cost_rate must be in [0, 1), not {cost_rate!r}")
+    if not 0.0 < cap < float("inf"):
+        raise ValueError(f"initial_capital must be positive and finite, not {initial_capital!r}")
+    if holdings_of is None:
+        ho = -1
+    else:
+        if not hasattr(holdings_of, "__index__") or isinstance(holdings_of, bool) or not 0 <= int(holdings_of) < len(cols):
+            raise ValueError(f"holdings_of must be None or a portfolio index in 0..{len(cols) - 1}, not {holdings_of!r}")
+        ho = int(holdings_of)
+    return cols, (n, T), np.ascontiguousarray(days.astype(np.int32)), cost, cap, ho
+
+
+def factor_weights(weights, price, rebalance_days, cost_rate: float = 0.001, initial_capital: float = 1_000_000.0, holdings_of=None):
+    """D-35: the backtest of GIVEN target weights.  weights: one [N, R] array, a list of P such arrays or one [P, N, R] array
+    (1 <= P <= 8), column k the weights bought on rebalance_days[k] (risk_solve's / Factor.optimal_portfolio's layout); they are signed,
+    need not sum to one -- the remainder 1 - sum w is cash, negative under leverage -- and a NULL, NaN or infinite weight is not held.
+    price [N, T]; rebalance_days strictly ascending in [0, T).  A target without a usable price on its rebalance day is dropped (counted,
+    its weight stays in cash); holdings drift with their prices (a symbol without a usable price keeps its last one) and every rebalance
+    pays cost_rate on the traded value.  The P portfolios share one pass over the prices.
+    -> dict of device tensors: value [P, T], turnover, net, gross [P, R], n_long, n_short, n_dropped int32 [P, R], first_nonpositive
+    int32 [P] (the first day whose value is not > 0, -1 if none: a signed, levered book can be ruined, and the curve after that day means
+    nothing), rebalance_days int32 [R] and, with holdings_of = p, holdings [N, T]: portfolio p's drifted weights on every day (0.0 where
+    nothing is held), the array that risk_portfolio reads.  The definitions are in include/pq_hip.h."""
+    cols, (n, T), days, cost, cap, ho = _factor_weights_args(weights, price, rebalance_days, cost_rate, initial_capital, holdings_of)
+    P, R = len(cols), days.size
+    p = _to_device(price)[0]
+    dev = p.device
+    if T > 1 and p.stride(1) != 1:
+        p = p.contiguous()
+    b = _batch(p)
+    f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
+    hold = torch.empty((n, b.stride), **f64)[:, :T] if ho >= 0 else None
+    if n == 0 or T == 0 or R == 0:                     # nothing is launched: every portfolio is its capital in cash
+        out = {"value": torch.full((P, T), cap, **f64), "turnover": torch.zeros((P, R), **f64), "net": torch.zeros((P, R), **f64),
+               "gross": torch.zeros((P, R), **f64), "n_long": torch.zeros((P, R), **i32), "n_short": torch.zeros((P, R), **i32),
+               "n_dropped": torch.zeros((P, R), **i32), "first_nonpositive": torch.full((P,), -1, **i32)}
+        if hold is not None:
+            hold.zero_()
+    else:
+        wd = [_to_device(c)[0].to(dev) for c in cols]       # on one row pitch >= R (risk_solve's y passes as it is), else dense
+        ws = wd[0].stride(0) if n > 1 and wd[0].stride(0) >= R else R
+        if not all((R <= 1 or w.stride(1) == 1) and (n <= 1 or w.stride(0) == ws) for w in wd):
+            wd, ws = [w.contiguous() for w in wd], R
+        value, tov = torch.empty((P, T), **f64), torch.empty((P, R), **f64)
+        expo, cnt, first = torch.empty((2, P, R), **f64), torch.empty((3, P, R), **i32), torch.empty((P,), **i32)
+        wp = (C.c_void_p * P)(*[w.data_ptr() for w in wd])
+        _call("pq_factor_weights", dev, b, wp, P, ws, p, days, R, cost, cap, value, tov, expo, cnt, first, ho, hold)
+        out = {"value": value, "turnover": tov, "net": expo[0], "gross": expo[1], "n_long": cnt[0], "n_short": cnt[1],
+               "n_dropped": cnt[2], "first_nonpositive": first}
+    out["rebalance_days"] = torch.from_numpy(days).to(dev)
+    if hold is not None:
+        out["holdings"] = hold
+    return out
+
+
 CLEAN_WINSORIZE = {None: 0, "mad": 1, "sigma": 2, "percentile": 3}     # pq_factor_clean's winsorize codes
 CLEAN_WINSORIZE_N = {"mad": 3.0, "sigma": 3.0, "percentile": 1.0}    # the README's defaults
 IC_MAX_GROUPS = 256                  # PQ_IC_MAX_GROUPS: the one limit on group (industry) codes, XS_MAX_GROUPS in csrc/xsec

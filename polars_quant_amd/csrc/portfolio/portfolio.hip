@@ -9,28 +9,9 @@
 //
 // Workspace: days (i32 [R]) | seg (i32 [len]) | block partials of A (f64) and of the counts (i32), [nblk][ng][R] | A (f64 [ng][R]) |
 // block partials of G (f64 [nblk][ng][len]) | G (f64 [ng][len]) | block partials of the turnover (f64 [nblk][ng][R]) | B (f64 [ng][R])
-#include <vector>
-
-#include "../xsec/xsec_dev.h"
+#include "portfolio_dev.h"   // pf_usable, PfArgs, pf_held, pf_chain_kernel, pf_grid, the day check and tables
 
 namespace {
-
-// a price that can be held, a weight that counts: non-null, finite and > 0
-__device__ __forceinline__ bool pf_usable(double v) { return xs_valid(v) && v > 0.0; }
-
-struct PfArgs {
-    const uint8_t *labels;  // [n][stride]
-    const double *price;    // [n][stride]
-    const double *weight;   // [n][stride] or null: equal weights
-    const int32_t *days;    // [R], ascending
-    const int32_t *seg;     // [len]: the rebalance index whose holdings day t values (d_k < t <= d_{k+1}), -1 up to d_0
-    const double *A;        // [ng][R]: sum of the members' weights
-    const double *G;        // [ng][len]: growth of the group since the rebalance that owns the day
-    const int32_t *count;   // [ng][R]
-    Dims d;
-    int64_t R;
-    int lag, ng;
-};
 
 // the members of rebalance k: label (of day d_k - lag) < ng, usable price and weight on d_k
 struct PfCell { int l; double p0, a; };
@@ -39,12 +20,6 @@ __device__ __forceinline__ PfCell pf_cell(const PfArgs &q, int64_t s, int64_t dk
     return PfCell{q.labels[o - q.lag], q.price[o], q.weight ? q.weight[o] : 1.0};
 }
 __device__ __forceinline__ bool pf_member(const PfArgs &q, const PfCell &c) { return c.l < q.ng && pf_usable(c.p0) && pf_usable(c.a); }
-
-// h(s, t): the price on the latest day in [dk, t] on which it is usable (price[s][dk] is, for a member); p = price[s][t]
-__device__ __forceinline__ double pf_held(const double *row, double p, int64_t t, int64_t dk) {
-    while (!pf_usable(p) && t > dk) p = row[--t];
-    return p;
-}
 
 // weight pass: one thread per (rebalance k, block of 256 symbols) -> per group the block's sum of the members' weights and their number
 template <int G> __global__ __launch_bounds__(64) void pf_weight_partial_kernel(PfArgs q, double *psum, int32_t *pcnt) {
@@ -186,33 +161,6 @@ template <int G> __global__ __launch_bounds__(64) void pf_turnover_partial_kerne
         if (g < q.ng) part[((int64_t)blockIdx.y * q.ng + g) * q.R + k] = tau[g];
 }
 
-// the chain, one 64-lane workgroup per group: P_0 = capital, P_k = B_{k-1} G(g, d_k), B_k = P_k (1 - cost_rate tau_k).  The lanes stage
-// PF_CHAIN steps at a time in LDS -- G(g, d_k) and 1 - cost_rate tau_k, which do not depend on the chain --, lane 0 walks them (two
-// dependent multiplications a step, no global load in between) and leaves B_k in the place of G, and the lanes store the B_k
-constexpr int PF_CHAIN = 1024;
-__global__ __launch_bounds__(64) void pf_chain_kernel(PfArgs q, const double *tau, double cost_rate, double capital, double *Bout) {
-    __shared__ double grow[PF_CHAIN], keep[PF_CHAIN];
-    const int64_t g = blockIdx.x;
-    double B = capital;
-    for (int64_t k0 = 0; k0 < q.R; k0 += PF_CHAIN) {
-        const int m = (int)(q.R - k0 < PF_CHAIN ? q.R - k0 : PF_CHAIN);
-        for (int i = threadIdx.x; i < m; i += 64) {
-            grow[i] = q.G[g * q.d.len + q.days[k0 + i]];
-            keep[i] = 1.0 - cost_rate * tau[g * q.R + k0 + i];
-        }
-        __syncthreads();
-        if (threadIdx.x == 0)
-            for (int i = 0; i < m; i++) {
-                const double P = k0 + i == 0 ? capital : B * grow[i];
-                B = P * keep[i];
-                grow[i] = B;
-            }
-        __syncthreads();
-        for (int i = threadIdx.x; i < m; i += 64) Bout[g * q.R + k0 + i] = grow[i];
-        __syncthreads();
-    }
-}
-
 // one thread per (group, day): the capital before d_0, B_k on d_k, B_k G(g, t) on the days in between and after the last
 __global__ __launch_bounds__(64) void pf_curve_kernel(PfArgs q, const double *Bv, double capital, double *value) {
     const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
@@ -232,8 +180,6 @@ __global__ __launch_bounds__(64) void pf_curve_kernel(PfArgs q, const double *Bv
         else if (ng <= 10) hipLaunchKernelGGL(kern<10>, grid, dim3(64), 0, ctx->stream, __VA_ARGS__);       \
         else hipLaunchKernelGGL(kern<20>, grid, dim3(64), 0, ctx->stream, __VA_ARGS__);                     \
     } while (0)
-
-inline dim3 pf_grid(int64_t threads, int64_t y = 1) { return dim3((unsigned)((threads + 63) / 64), (unsigned)y); }
 
 } // namespace
 
@@ -259,25 +205,8 @@ pq_status pq_factor_portfolio(pq_ctx *ctx, const pq_batch *b, const uint8_t *lab
     const int64_t R = n_rebalance, nblk = xs_nblk(d.n);
     const int ng = n_groups;
     PQ_REQUIRE(d.len <= 0x7fffffffLL && nblk <= 65535, "pq_factor_portfolio: batch too large (len < 2^31, n_series <= 16776960)");
-    for (int64_t k = 0; k < R; k++) {
-        const int64_t dk = rebalance_days[k];
-        if (dk < label_lag || dk >= d.len) {
-            pq_set_error("pq_factor_portfolio: rebalance day %lld (entry %lld) is outside [label_lag, len) = [%d, %lld)", (long long)dk,
-                         (long long)k, (int)label_lag, (long long)d.len);
-            return PQ_ERR_ARG;
-        }
-        if (k > 0 && dk <= rebalance_days[k - 1]) {
-            pq_set_error("pq_factor_portfolio: the rebalance days must be strictly ascending (entry %lld)", (long long)k);
-            return PQ_ERR_ARG;
-        }
-    }
-    // the day table and, behind it, the segment table: seg[t] = k for d_k < t <= d_{k+1} (the last segment runs to len - 1), -1 up to d_0
-    std::vector<int32_t> host((size_t)(R + d.len));
-    for (int64_t k = 0; k < R; k++) host[(size_t)k] = rebalance_days[k];
-    for (int64_t t = 0, k = -1; t < d.len; t++) {
-        host[(size_t)(R + t)] = (int32_t)k;
-        if (k + 1 < R && t == rebalance_days[k + 1]) k++; // day d_{k+1} itself still belongs to segment k
-    }
+    PQ_TRY(pf_check_days("pq_factor_portfolio", rebalance_days, R, label_lag, "label_lag", d.len));
+    const std::vector<int32_t> host = pf_day_tables(rebalance_days, R, d.len);
     const size_t len = (size_t)d.len, gr = (size_t)ng * (size_t)R, gt = (size_t)ng * len;
     int32_t *days, *seg, *pc;
     double *pa, *A, *pg, *G, *pt, *Bv;

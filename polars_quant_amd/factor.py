@@ -22,6 +22,8 @@ the exponentially weighted covariance of the factor and industry returns and the
 days, and from the two the predicted variance of a portfolio with its exposures and each factor's contribution.
 `optimal_portfolio` (decision D-34, beyond the README) is the step after them: the minimum-variance, tangency or mean-variance weights
 under that model on every rebalance day, from Sigma^-1 v through the factor structure (Sigma itself is never built).
+`weights_backtest` (decision D-35, beyond the README) holds such weights -- signed, the remainder in cash -- between the rebalance days:
+the value curve with turnover and costs, and the drifted daily holdings that `portfolio_risk` reads.
 """
 from __future__ import annotations
 
@@ -474,6 +476,56 @@ class Factor:
         days = int(model["day0"]) + int(model["step"]) * torch.arange(D, dtype=torch.int64, device=y.device)
         return {"weights": nn(w), "predicted_var": nn(var), "expected_return": nn(ret), "n_universe": n[0], "n_uncovered": n[1],
                 "days": days}
+
+    # ---- D-35: what given weights would have earned -- signed, with cash, with turnover and costs
+    def weights_backtest(self, weights, price, days=None, lag=0, cost_rate=0.001, initial_capital=1_000_000.0, benchmark=None,
+                         holdings=None):
+        """weights: one [N, R] array, a list of P such arrays or one [P, N, R] array (1 <= P <= 8), column k the target weights of
+        rebalance k -- or the dict that optimal_portfolio returns, whose "weights" and "days" are then taken.  price [N, T]; days [R]: the
+        day each column is known.  The trade day of column k is days[k] + lag; trailing columns whose trade day is >= T are dropped, and
+        the returned "rebalance_days" shows the days that were used.  The weights are signed and need not sum to one: the remainder is
+        cash (negative under leverage), a NULL, NaN or infinite weight is not held, and a target without a usable price on its trade day
+        is dropped (n_dropped counts them, the weight stays in cash).  Holdings drift with their prices, every rebalance pays cost_rate
+        on the traded value; no borrow or financing rate is charged on the short leg or on negative cash.
+        -> {"value": [P, T], "turnover", "net", "gross": [P, R], "n_long", "n_short", "n_dropped": [P, R] (int32), "first_nonpositive":
+        [P] (int32), "rebalance_days": [R], "daily_return": [P, T], "statistics": {name: [P]}, the curve columns of the backtest report
+        and, with a benchmark [T], its benchmark columns} and, with holdings=p, "holdings": [N, T], portfolio p's drifted weights on
+        every day -- what portfolio_risk(holdings=...) takes.  first_nonpositive is the first day whose value is not > 0 (-1: none): a
+        signed, levered book can be ruined, and the curve and the statistics after that day mean nothing.
+        Look-ahead: pure_factor_return regresses the NEXT return, so a model "as of t" from its series, and a portfolio built from it,
+        is known one day later (risk_model's note): trade it with lag=1."""
+        from ._spec import REPORT_COLS
+        if isinstance(weights, dict):
+            if days is None:
+                days = weights["days"]
+            weights = weights["weights"]
+        if days is None:
+            raise ValueError("days is needed: the day each column of weights is known (optimal_portfolio's dict carries its own)")
+        if not hasattr(lag, "__index__") or int(lag) < 0:
+            raise ValueError(f"lag must be a non-negative number of days, not {lag!r}")
+        d = days.cpu().numpy() if isinstance(days, torch.Tensor) else _api.np.asarray(days)
+        if d.size and d.dtype.kind not in "iu":
+            raise ValueError("days must hold integer day indices")
+        d = d.reshape(-1).astype(_api.np.int64) + int(lag)
+        T = _api._shape(price)[-1]
+        stacked = not isinstance(weights, (list, tuple))
+        cols = [weights] if stacked else list(weights)
+        for c in cols:
+            if _api._shape(c)[-1:] != (d.size,):
+                raise ValueError(f"weights must have one column per day: {d.size}, not {_api._shape(c)}")
+        keep = d.size
+        while keep and d[keep - 1] >= T:
+            keep -= 1
+        if keep < d.size:
+            cols = [c[..., :keep] for c in cols]
+        out = _api.factor_weights(cols[0] if stacked else cols, price, d[:keep], cost_rate, initial_capital, holdings)
+        value = out["value"]
+        (daily,) = _api.call("returns", value, period=1)
+        out["daily_return"] = daily
+        rep = _api.backtest_report(value, initial_capital, benchmark)
+        cols = list(range(15)) + (list(range(38, 45)) if benchmark is not None else [])
+        out["statistics"] = {REPORT_COLS[c]: rep[:, c] for c in cols}
+        return out
 
     def time_series_regression(self, factors, returns):
         """factors: a list of [N, T] or [T] arrays (a [T] series, e.g. a market return, is shared by every symbol) or one [K, N, T]
