@@ -977,6 +977,47 @@ pq_status pq_factor_weights(pq_ctx *, const pq_batch *, const double *const *wei
                             int32_t *first_nonpositive /* [P] */, int32_t holdings_of /* portfolio index, or -1 */,
                             double *holdings_out /* [n_series][stride], or NULL */);
 
+/* ---- rank 3, continued: the return attribution of holdings through the factor model (api.return_attribution, Factor.return_attribution;
+ * decision D-36 in DESIGN.md section 2): how much of every day's return of a book came from each style factor, each industry and the
+ * specific returns of pq_xsec_regress_wls (D-32), and how much the model cannot see.  Where something is not said here, pq_risk_portfolio's
+ * rules hold.  holdings [n_series][stride] on the batch's pitch (what pq_factor_weights writes); benchmark_holdings optional, same layout;
+ * exposures a HOST array of 0 <= k <= PQ_REGRESS_MAX_K device pointers; industry / group_stride / n_groups = G are pq_xsec_regress_wls's
+ * (NULL: G = 1, every symbol in group 0); factor_return [M][fr_stride], M = k + G, fr_stride >= len: the k style rows, then the G industry
+ * rows or the intercept (D-32's coef block); specific_return [n_series][stride] (D-32's resid); next_return optional, same layout.  The
+ * call covers EVERY day t in [0, len).
+ *   books        P = 1: the holdings h.  With a benchmark b, P = 3: h, b and the active book a, a_i = h_i - b_i per symbol, where a holding
+ *                that is NULL or not finite counts as 0.0.  A symbol is HELD in a book when its value there is non-null, finite and != 0.0
+ *   covered      every exposure non-null and finite, a given code in [0, G), specific_return[s][t] non-null and finite: membership of
+ *                D-32's sample of the day.  A held symbol that is not covered is UNCOVERED -- the day goes on --, and MISSING when
+ *                next_return is also absent or not valid there.  n_out [3][P][len]: held, uncovered, missing
+ *   sums         each D-12's blocked sum (blocks of 256 symbol indices ascending from 0.0, block sums ascending from 0.0), every product
+ *                rounded before it is added: X[j] = sum over covered of h x_j, X[k + g] = sum over covered in g of h, spec = sum over
+ *                covered of h u, unexplained = sum over uncovered with a valid r of h r, realized = sum over held with a valid r of h r
+ *   contribution c_j = X[j] f_j(t) where X[j] != 0 and 0.0 where X[j] == 0 (D-32 writes NULL for an empty industry: it does not matter);
+ *                a NULL or non-finite f_j(t) with X[j] != 0 and a day on which nothing is held make every f64 output of the book's day NULL
+ *   outputs      exposure_out / contribution_out [P][M][len]; totals_out [P][6][len]: style = sum_{j<k} c_j and industry = sum_g c_{k+g}
+ *                (each ascending from 0.0), specific, unexplained, total = ((style + industry) + specific) + unexplained, and realized
+ *                (NULL without next_return).  A value that comes out NaN is NULL
+ *   aggregates   the series of a book are its M contribution rows, then its 6 totals.  summary_out [P][M + 6][5]: pq_xsec_regress's
+ *                Fama-MacBeth row (n_days, mean, std, t_stat, p_value) over the series' non-NULL days.  With period_bounds, a HOST array
+ *                of n_periods + 1 day indices strictly ascending in [0, len] (period k = the days [bounds[k], bounds[k + 1])):
+ *                period_sum_out [P][M + 6][S], the sum over the period's non-NULL days ascending from 0.0, and period_days_out [P][S], the
+ *                period's days whose total is not NULL.  The sums are arithmetic, not geometrically linked
+ * On a day without uncovered symbols total equals realized up to rounding; doubling the holdings doubles every f64 output bit for bit.
+ * PQ_ERR_ARG: a null required pointer, k, n_groups, group_stride, fr_stride or the bounds out of range, period_bounds without n_periods
+ * > 0 or the reverse, an output that overlaps an input or another output; ragged batches and suite recording are refused
+ * (PQ_ERR_UNSUPPORTED); len == 0 or n_series == 0 launches nothing.  Uses the context workspace (8 P (M + 3) + 12 P bytes per (day, block
+ * of 256 symbols)). */
+#define PQ_ATTRIBUTION_TOTALS 6
+pq_status pq_return_attribution(pq_ctx *, const pq_batch *, const double *holdings, const double *benchmark_holdings /* or NULL */,
+                                const double *const *exposures, int32_t k, const int32_t *industry, int64_t group_stride, int32_t n_groups,
+                                const double *factor_return /* [M][fr_stride] */, int64_t fr_stride, const double *specific_return,
+                                const double *next_return /* or NULL */, const int64_t *period_bounds /* HOST, n_periods + 1, or NULL */,
+                                int64_t n_periods, double *exposure_out /* [P][M][len] */, double *contribution_out /* [P][M][len] */,
+                                double *totals_out /* [P][6][len] */, int32_t *n_out /* [3][P][len] */,
+                                double *summary_out /* [P][M + 6][5] */, double *period_sum_out /* [P][M + 6][S], or NULL */,
+                                int32_t *period_days_out /* [P][S], or NULL */);
+
 /* ---- suites: record many calls, replay them as a few chip-filling grids ----
  * One indicator over N symbols is only N/64 wavefronts -- far too few for 256 CUs -- but a DataFrame query asks
  * for many indicators at once (df.with_columns([...]) in the reference; Polars then calls the plugin once per

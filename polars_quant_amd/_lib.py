@@ -161,6 +161,7 @@ risk_specific_var      i pBppllilllplp
 risk_portfolio         i pBppiplippllllpppp
 risk_solve             i pBpipiplippllllplpp
 factor_weights         i pBpilpplddpppppip
+return_attribution     i pBpppipliplppplppppppp
 suite_begin            i pB
 suite_end              i pp
 suite_abort            i p

@@ -1521,6 +1521,121 @@ def risk_solve(rhs, exposures, cov, specific_var, industry=None, day0: int = 0, 
     return y, quad, cnt
 
 
+ATTRIBUTION_TOTALS = ("style", "industry", "specific", "unexplained", "total", "realized")   # the rows of pq_return_attribution's totals_out
+
+
+def _attribution_bounds(T, periods):
+    """periods of return_attribution -> the S + 1 bounds as an int64 numpy array, or None: an int n is numpy.array_split(range(T), n)
+    (split_periods), anything else the bounds themselves, strictly ascending in [0, T]"""
+    if periods is None:
+        return None
+    if isinstance(periods, (int, np.integer)) and not isinstance(periods, bool):
+        start, end = split_periods(T, periods)
+        return np.ascontiguousarray(np.concatenate([start, end[-1:] + 1]).astype(np.int64))
+    if isinstance(periods, torch.Tensor):
+        periods = periods.detach().cpu().numpy()
+    b = np.asarray(periods)
+    if b.ndim != 1 or b.size < 2 or b.dtype.kind not in "iu":
+        raise ValueError("periods must be an integer number of splits or S + 1 >= 2 integer day bounds")
+    b = np.ascontiguousarray(b.astype(np.int64))
+    if b[0] < 0 or b[-1] > T or (np.diff(b) <= 0).any():
+        raise ValueError(f"the period bounds must be strictly ascending in [0, T] (T = {T})")
+    return b
+
+
+def _attribution_args(holdings, exposures, factor_return, specific_return, industry, next_return, benchmark, periods):
+    """argument checks of return_attribution that need no device -> (exposure columns, (N, T), K, G, industry as an integer tensor or
+    None, the period bounds or None)"""
+    hs = _shape(holdings)
+    if len(hs) != 2:
+        raise ValueError(f"holdings must be [N, T], not {hs}")
+    n, T = hs
+    cols = [] if exposures is None else _columns(exposures, "the number of exposures", 0, REGRESS_MAX_K, 3,
+                                                 "exposures must be a list of [N, T] arrays or one [K, N, T] array")
+    K = len(cols)
+    for j, c in enumerate(cols):
+        if _shape(c) != hs:
+            raise ValueError(f"exposure {j} must have the holdings' shape {hs}, not {_shape(c)}")
+    for nm, v in (("specific_return", specific_return), ("next_return", next_return), ("benchmark", benchmark)):
+        if v is None and nm == "specific_return":
+            raise ValueError("specific_return is needed: pure_factor_return(..., specific_return=True)'s residuals")
+        if v is not None and _shape(v) != hs:
+            raise ValueError(f"{nm} must have the holdings' shape {hs}, not {_shape(v)}")
+    fs = _shape(factor_return)
+    if len(fs) != 2 or fs[1] != T:
+        raise ValueError(f"factor_return must be [K + G, T] with T = {T}, not {fs}")
+    G = fs[0] - K
+    ind = None
+    if industry is not None:
+        ind = _int_codes(industry, "industry")
+        if tuple(ind.shape) not in ((n,), (n, T)):
+            raise ValueError(f"industry must be [N] or [N, T] with N = {n}, T = {T}, not {tuple(ind.shape)}")
+        if not 1 <= G <= MAX_INDUSTRIES or _n_codes(ind, "industry", MAX_INDUSTRIES) > G:
+            raise ValueError(f"factor_return must be [K + G, T] with K = {K} exposures and G industries (the codes are < G), not {fs}")
+    elif G != 1:
+        raise ValueError(f"factor_return must be [K + 1, T] with K = {K} exposures and no industry codes, not {fs}")
+    return cols, hs, K, G, ind, _attribution_bounds(T, periods)
+
+
+def return_attribution(holdings, exposures, factor_return, specific_return, industry=None, next_return=None, benchmark=None, periods=None):
+    """D-36: the return attribution of the holdings [N, T] (weights or values; NULL or 0: not held) through the factor model, on every
+    day.  exposures: a list of K [N, T] arrays or one [K, N, T] array (0 <= K <= 8; None: K = 0); factor_return [K + G, T], the K style
+    rows and then the G industry rows (or the intercept) of xsec_regress_wls's coef; specific_return [N, T], its resid; industry int
+    codes [N] or [N, T] (None: G = 1); next_return [N, T] (optional) the return that was regressed; benchmark [N, T] (optional) gives
+    P = 3 books -- the portfolio, the benchmark and the active book h - b -- instead of P = 1; periods: an int (numpy.array_split of the
+    days) or S + 1 day bounds strictly ascending in [0, T].
+    -> dict of device tensors, the book axis first: exposure / contribution [P, M, T] (X_j = sum h x_j over the covered symbols, c_j =
+    X_j f_j), style / industry / specific / unexplained / total / realized [P, T], n_held / n_uncovered / n_missing [P, T] (int32),
+    summary [P, M + 6, 5] (n_days, mean, std, t_stat, p_value of the M contributions and the six totals over their non-NULL days) and,
+    with periods, period_sum [P, M + 6, S], period_days [P, S] (int32) and period_bounds [S + 1] (int64).  A held symbol without an
+    exposure, an industry or a specific return is uncovered: its h r goes to `unexplained` where next_return is valid, and it is counted
+    missing where not.  A book's day is NULL where nothing is held and where a factor return that a non-zero exposure needs is NULL.  On
+    a day without uncovered symbols total equals realized up to rounding.  The definitions are in include/pq_hip.h."""
+    cols, (n, T), K, G, ind, bounds = _attribution_args(holdings, exposures, factor_return, specific_return, industry, next_return,
+                                                         benchmark, periods)
+    M, NS = K + G, K + G + len(ATTRIBUTION_TOTALS)
+    P = 1 if benchmark is None else 3
+    S = 0 if bounds is None else bounds.size - 1
+    planes = [holdings] + ([benchmark] if benchmark is not None else []) + cols + [specific_return] + \
+        ([next_return] if next_return is not None else [])
+    mats = _same_layout([_to_device(c)[0] for c in planes])
+    h = mats[0]
+    dev = h.device
+    f64, i32 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int32, device=dev)
+    if n == 0 or T == 0:                                        # nothing is launched: nothing is held on any day
+        null = lambda *s: torch.from_numpy(np.full(s, NULL)).to(dev)   # noqa: E731
+        expo, contrib, tot = null(P, M, T), null(P, M, T), null(P, 6, T)
+        cnt = torch.zeros((3, P, T), **i32)
+        summ = null(P, NS, REGRESS_SUMMARY_COLS)
+        summ[:, :, 0] = 0.0
+        psum, pdays = torch.zeros((P, NS, S), **f64), torch.zeros((P, S), **i32)
+    else:
+        b = _batch(h)
+        it = iter(mats[1:])
+        bm = next(it) if benchmark is not None else None
+        xs = [next(it) for _ in range(K)]
+        u = next(it)
+        r = next(it) if next_return is not None else None
+        fr = _to_device(factor_return)[0].to(dev)
+        if (T > 1 and fr.stride(1) != 1) or (M > 1 and fr.stride(0) < T):
+            fr = fr.contiguous()
+        frs = fr.stride(0) if M > 1 and fr.stride(0) >= T else T
+        gp, gs = (None, 0) if ind is None else _codes_on_pitch(ind, b, dev)
+        expo, contrib, tot = torch.empty((P, M, T), **f64), torch.empty((P, M, T), **f64), torch.empty((P, 6, T), **f64)
+        cnt = torch.empty((3, P, T), **i32)
+        summ = torch.empty((P, NS, REGRESS_SUMMARY_COLS), **f64)
+        psum, pdays = (torch.empty((P, NS, S), **f64), torch.empty((P, S), **i32)) if S else (None, None)
+        ptrs = (C.c_void_p * max(K, 1))(*[m.data_ptr() for m in xs])
+        bp = bounds if S else None                             # a host array: the entry point copies it
+        _call("pq_return_attribution", dev, b, h, bm, ptrs, K, gp, gs, G, fr, frs, u, r, bp, S, expo, contrib, tot, cnt, summ, psum, pdays)
+    out = {"exposure": expo, "contribution": contrib}
+    out.update({nm: tot[:, i] for i, nm in enumerate(ATTRIBUTION_TOTALS)})
+    out.update({"n_held": cnt[0], "n_uncovered": cnt[1], "n_missing": cnt[2], "summary": summ})
+    if bounds is not None:
+        out.update({"period_sum": psum, "period_days": pdays, "period_bounds": torch.from_numpy(bounds).to(dev)})
+    return out
+
+
 ROLLING_REGRESS_MAX_K = 4                                      # PQ_ROLLING_REGRESS_MAX_K
 ROLLING_REGRESS_OUTPUTS = ("beta", "alpha", "resid_std", "r_squared", "resid")   # pq_factor_rolling_regress's output pointers, in order
 

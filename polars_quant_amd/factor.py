@@ -34,6 +34,14 @@ from . import api as _api
 IC_METHODS = {"pearson": 0, "spearman": 1}
 
 
+def _stack_factor_returns(d):
+    """pure_factor_return's dict -> (its factor_return rows stacked with industry_return (or intercept) into the [K + G, T] block, its
+    specific_return or None): the one stacking of risk_model and return_attribution"""
+    rest = d["industry_return"] if "industry_return" in d else d["intercept"]
+    fr, rest = (_api._to_device(x)[0] for x in (d["factor_return"], rest))
+    return torch.cat([fr, rest.to(fr.device)]), d.get("specific_return")
+
+
 class Factor:
     def __init__(self):
         # Factor().clean (D-19) is bound per instance, the way the README calls it (`factor = Factor(); factor.clean(df, ...)`).  The
@@ -368,6 +376,42 @@ class Factor:
             out["specific_return"] = r["resid"]
         return out
 
+    # ---- D-36: which factor, industry and specific returns the return of a book came from
+    def return_attribution(self, holdings, exposures, returns, industry=None, next_return=None, benchmark=None, periods=None):
+        """holdings [N, T] (weights or values; NULL or 0: not held) or the dict of weights_backtest(..., holdings=p), whose "holdings"
+        is taken; exposures the K factors of the regression (a list of [N, T] arrays or one [K, N, T] array), industry its codes;
+        returns: the dict of pure_factor_return(..., specific_return=True), or a pair (factor_return [K + G, T], specific_return
+        [N, T]); next_return [N, T] (optional): the return that was regressed; benchmark (optional): a second [N, T] book or such a dict,
+        which gives the three books portfolio, benchmark, active (= h - b) instead of one; periods: an int, read as
+        numpy.array_split(range(T), periods) like subsample_test, or S + 1 explicit day bounds strictly ascending in [0, T].
+        -> {"exposure", "contribution": [P, M, T]; "style", "industry", "specific", "unexplained", "total", "realized": [P, T];
+        "n_held", "n_uncovered", "n_missing": [P, T] (int32); "summary": [P, M + 6, 5] (n_days, mean, std, t_stat, p_value of the M
+        contributions and the six totals over their non-NULL days); with periods "period_sum": [P, M + 6, S], "period_days": [P, S],
+        "period_bounds": [S + 1]}.  total = style + industry + specific + unexplained; a held symbol that lacks an exposure, an
+        industry or a specific return is uncovered, its h r is the unexplained part (n_missing: it has no next return either); on a
+        day without uncovered symbols total equals realized up to rounding.  A book's day is NULL where nothing is held and where a
+        factor return that a non-zero exposure needs is NULL.  The period sums are arithmetic, not geometrically linked.
+        Alignment: row t pairs the holdings at the close of day t with the return from t to t + 1, which is pure_factor_return's
+        convention (it regresses the NEXT return on the exposures of day t): pass the same exposures, industry and next_return.
+        Look-ahead: pure_factor_return regresses the NEXT return, so its row t -- and the attribution of day t -- is known one day
+        later (risk_model's note)."""
+        def book(x, what):
+            if isinstance(x, dict):
+                if "holdings" not in x:
+                    raise ValueError(f"the {what} dict has no \"holdings\": call weights_backtest(..., holdings=p)")
+                return x["holdings"]
+            return x
+        if isinstance(returns, dict):
+            fr, sr = _stack_factor_returns(returns)
+            if sr is None:
+                raise ValueError("returns has no specific_return: call pure_factor_return(..., specific_return=True)")
+        elif isinstance(returns, (list, tuple)) and len(returns) == 2:
+            fr, sr = returns
+        else:
+            raise ValueError("returns must be pure_factor_return's dict or a pair (factor_return [K + G, T], specific_return [N, T])")
+        return _api.return_attribution(book(holdings, "holdings"), exposures, fr, sr, industry, next_return,
+                                       None if benchmark is None else book(benchmark, "benchmark"), periods)
+
     # ---- D-33: the risk model on pure_factor_return's three series, and the predicted risk of a portfolio from it
     def risk_model(self, factor_returns, specific_returns=None, window=252, halflife=None, min_periods=None, start=None, step=1,
                    unbiased=True, specific_window=None, specific_halflife=None):
@@ -385,12 +429,9 @@ class Factor:
         NEXT return, so its row t, and the model "as of t", is known one day later: shift with Factor.delay where that matters."""
         sr = specific_returns
         if isinstance(factor_returns, dict):
-            d = factor_returns
-            rest = d["industry_return"] if "industry_return" in d else d["intercept"]
-            fr, rest = (_api._to_device(x)[0] for x in (d["factor_return"], rest))
-            factor_returns = torch.cat([fr, rest.to(fr.device)])
+            factor_returns, own = _stack_factor_returns(factor_returns)
             if sr is None:
-                sr = d.get("specific_return")
+                sr = own
         window = int(window)
         sw = window if specific_window is None else int(specific_window)
         shl = halflife if specific_halflife is None else specific_halflife
